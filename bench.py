@@ -4,6 +4,8 @@ render, N_sample=64 + N_importance=128, synthetic inputs.
 
     python bench.py --gpus N --steps K --warmup W           (N > 1: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --full                                  (+ the side measurements, see --full)
+    python bench.py --dump-outputs DIR                      (+ the last timed step's outputs as DIR/<name>.npy)
 
 A step = one full frame through the hot path (ray generation -> coarse PE+MLP ->
 compositing -> inverse-CDF sampling -> fine PE+MLP -> compositing).  With N ranks the
@@ -224,6 +226,27 @@ def cpu_baseline(syn, pc, pf, gpu_rgb_band, band_row0, n_rays=4096, runs=3):
         mse = float(((gpu_rgb_band[:nrows].cpu() - ref["rgb_map"]) ** 2).mean())
         psnr = 10.0 * torch.log10(torch.tensor(1.0 / max(mse, 1e-20))).item()
     return out, psnr
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs`: each tensor of `arrays` as path/<name>.npy in float32, at most `limit` bytes in all.  Every
+    array is per pixel ([..., pixels] or [..., pixels, 3]); past the limit each keeps every k-th pixel (the same fixed
+    k for all of them, flattened to [pixels / k] or [pixels / k, 3]), so runs with the same arguments stay comparable.
+    Returns k."""
+    import numpy as np
+    host = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    pixels = {k: a.reshape(-1, 3) if a.ndim > 1 and a.shape[-1] == 3 else a.reshape(-1) for k, a in host.items()}
+    nbytes = lambda k: sum(-(-p.shape[0] // k) * p[:1].nbytes for p in pixels.values())
+    stride = 1
+    while nbytes(stride) > limit:
+        stride += 1
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a if stride == 1 else np.ascontiguousarray(pixels[name][::stride]))
+    return stride
 
 
 def init_ranks(need_gpu=True):
@@ -570,9 +593,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements of a one-rank frame run: the other arithmetic "
+                         "modes and kernel arrangements, Network.forward, the train step, the head+torso composite and the "
+                         "CPU-oracle baseline (off by default: a plain run times only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="frame workload: write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all): "
+                         "frame_rgb = the gathered [H, W, 3] frame, the others = render_rays_fwd's per-ray outputs of rank 0's band")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
     ap.add_argument("--no-f32-mode", "--no-side-mode", dest="no_f32_mode", action="store_true",
-                    help="skip the side measurement of the other arithmetic mode (profiling runs)")
+                    help="with --full: skip the side measurements of the other modes, Network.forward, train and torso (profiling runs)")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--soak", action="store_true",
                     help="compare every timed frame with the first one bit for bit (the path is deterministic: a mismatch is "
@@ -593,6 +623,10 @@ def main():
     args.precision_given = any(a.startswith("--precision") for a in sys.argv[1:]) or "IDN_PRECISION" in os.environ
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "frame":
+        ap.error("--dump-outputs is implemented for the frame workload")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             # plain `python bench.py --gpus N`: this process only starts the ranks (no GPU call before here)
@@ -649,7 +683,7 @@ def main():
         frame = parallel.gather_rows(tile, H, force=collective)
         if i is not None:
             marks[i][2].record()   # the collective is ordered into this stream: the event fires when the gathered frame is usable
-        return frame, tile
+        return frame, tile, out
 
     def fence():
         if collective:
@@ -666,7 +700,7 @@ def main():
         first, mismatched = None, torch.zeros((), dtype=torch.int64, device=dev)
         t0 = time.perf_counter()
         for i_step in range(args.steps):
-            frame, tile = step(i_step)
+            frame, tile, out = step(i_step)
             if args.soak:
                 if first is None:
                     first = tile.clone()
@@ -674,6 +708,8 @@ def main():
                     mismatched += (tile != first).any().to(torch.int64)
         fence()
         dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # what the last timed step computed, after the clock stopped
+        dump_outputs(args.dump_outputs, {"frame_rgb": frame, **out})
     import ctypes as C
     k_ms, k_n, k_pts = C.c_double(), C.c_int64(), C.c_int64()
     lib.idealnerf_profile_end(C.byref(k_ms), C.byref(k_n), C.byref(k_pts))
@@ -734,7 +770,7 @@ def main():
                                  "1.8-2.0 GHz; an LDS-fed bf16 MFMA loop on random data tops out at 1.3-1.5 PFLOP/s of "
                                  "issued MFMAs (tools/mfma_shape_ubench.hip, DESIGN.md section 3)"},
         }
-        if world == 1 and not args.no_f32_mode:
+        if world == 1 and args.full and not args.no_f32_mode:
             # the other arithmetic modes of the same kernel family on the same box and scene, measured after the
             # timed region (2 frames each): mixed and bf16x3 beside the fp32 headline, fp32 beside anything else
             notes = {"f32": "IDN_PREC_F32: v_mfma_f32_32x32x2_f32, exact fp32 fma chains",
@@ -807,7 +843,7 @@ def main():
                                      "launches": k_n.value, "avg_launch_ms": (k_ms.value / k_n.value) if k_n.value else None,
                                      "traffic": pmc_traffic("f32", fused=arr)[0]},
                         "note": ARRANGEMENT_NOTE}
-        if world == 1 and not args.no_f32_mode:
+        if world == 1 and args.full and not args.no_f32_mode:
             res["network_api"] = network_api_measurement(args, syn, coarse, fine, value, tile)
             res["network_api_perturb1"] = network_api_measurement(args, syn, coarse, fine, value, tile, frames=2, perturb=1.0)
             # BASELINE configs[2] and configs[4] beside the headline, each with its own roofline block, after the timed region
@@ -818,7 +854,7 @@ def main():
             res["torso_composite"] = {k: to[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "frames_per_s", "config",
                                                          "roofline", "finite", "psnr_vs_fp32_frame_db")}
             res["side_blocks_s"] = time.perf_counter() - t_side
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             pc = {k: v.detach().cpu() for k, v in coarse.state_dict().items()}
             pf = {k: v.detach().cpu() for k, v in fine.state_dict().items()}
             res["cpu_baseline"], psnr = cpu_baseline(syn, pc, pf, tile, r0)

@@ -754,6 +754,32 @@ def test_bench_parent_never_touches_the_gpu_before_launching():
     assert "os.exec" not in open(os.path.join(ROOT, "bench.py")).read()
 
 
+def test_bench_dump_outputs_keep_every_kth_pixel_under_the_limit(tmp_path):
+    """`--dump-outputs`: float32 .npy files of the given shapes while they fit; past the byte limit every array keeps
+    the same every-k-th pixel, and all files together stay within the limit."""
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    arrays = {"frame_rgb": torch.rand(8, 8, 3, generator=g), "rgb_map": torch.rand(64, 3, generator=g),
+              "disp_map": torch.rand(64, generator=g, dtype=torch.float64)}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == 1
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == tuple(v.shape) and np.array_equal(a, v.float().numpy())
+    limit = 300   # 64 pixels x (3 + 3 + 1) floats = 1792 bytes: every 7th pixel (10 of them, 280 bytes) is the first stride that fits
+    assert bench.dump_outputs(str(tmp_path / "few"), arrays, limit=limit) == 7
+    got = {k: np.load(tmp_path / "few" / f"{k}.npy") for k in arrays}
+    assert sum(a.nbytes for a in got.values()) <= limit
+    assert np.array_equal(got["frame_rgb"], arrays["frame_rgb"].reshape(-1, 3)[::7].numpy())
+    assert np.array_equal(got["rgb_map"], arrays["rgb_map"][::7].numpy())
+    assert np.array_equal(got["disp_map"], arrays["disp_map"][::7].float().numpy())
+
+
+def test_bench_refuses_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--workload", "rendezvous"],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--steps must be >= 1" in p.stderr
+
+
 def test_bench_rejects_a_world_size_that_contradicts_gpus():
     env = dict(os.environ, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "rendezvous"],

@@ -703,6 +703,45 @@ def test_bench_two_ranks_from_a_plain_start(dev):
     assert r1["n_gpus"] == 1 and r1["ranks"] == 1 and r1["config"]["rays_per_step"] == res["config"]["rays_per_step"]
 
 
+def test_bench_plain_line_dumps_reproducible_outputs_and_full_adds_the_side_blocks(dev, tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline and no side measurement; `--dump-outputs` writes the last
+    timed frame's outputs, bit for bit the same from run to run; `--full` adds the side blocks back."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "IDN_DIST_BACKEND", "IDN_FORCE_DEVICE", "IDN_PRECISION"):
+        env.pop(k, None)
+
+    def run(*extra):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--size", "96", *extra],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0])
+
+    side = ("bf16x6_mode", "mixed_mode", "network_api", "train_step", "torso_composite", "cpu_baseline")
+    dumps = []
+    for name in ("a", "b"):
+        res = run("--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / name))
+        assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+        assert res["unit"] == "ray-samples/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        assert not any(k in res for k in side), sorted(res)
+        dumps.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = dumps
+    assert set(a) == {"frame_rgb", "rgb_map", "disp_map", "acc_map", "rgb0", "disp0", "acc0", "z_std", "last_weight"}
+    assert a["frame_rgb"].shape == (96, 96, 3) and a["disp_map"].shape == (96 * 96,)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert np.array_equal(a["frame_rgb"].reshape(-1, 3), a["rgb_map"]) and a["frame_rgb"].std() > 0.01
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    full = run("--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline")
+    assert all(k in full for k in side[:-1]) and "cpu_baseline" not in full
+    arrangements = [full[k] for k in ("kernel_sequence_mode", "fused_march", "fused_split") if k in full]
+    assert len(arrangements) == 2 and all(x["identical_to_headline_frame"] is True for x in arrangements)
+    assert np.isfinite(full["train_step"]["final_loss"]) and full["torso_composite"]["finite"] is True
+
+
 def _two_rank_env():
     import os
     env = dict(os.environ, IDN_DIST_BACKEND="gloo", IDN_FORCE_DEVICE="0", IDN_DIST_TIMEOUT_S="90", OMP_NUM_THREADS="4")

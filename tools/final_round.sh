@@ -50,8 +50,8 @@ mkdir -p profiles
 for P in f32 bf16x6; do cp $F/pmc_mlp_${P}_final.json profiles/${ROUND:-r04}_pmc_mlp_${P}_final.json; done
 cp $F/pmc_render_fused_final.json profiles/${ROUND:-r04}_pmc_render_fused_final.json
 cp $F/pmc_render_split_final.json profiles/${ROUND:-r04}_pmc_render_split_final.json
-python bench.py > $F/bench_default.json 2> $F/bench_default.err
-python bench.py --precision bf16x6 --no-cpu-baseline > $F/bench_bf16x6.json 2>> $F/bench_default.err
+python bench.py --full > $F/bench_default.json 2> $F/bench_default.err
+python bench.py --full --precision bf16x6 --no-cpu-baseline > $F/bench_bf16x6.json 2>> $F/bench_default.err
 python bench.py --workload train --steps 12 --warmup 4 > $F/bench_train.json 2>> $F/bench_default.err
 python bench.py --workload torso > $F/bench_torso_bf16.json 2>> $F/bench_default.err
 IDN_DIST_BACKEND=gloo IDN_FORCE_DEVICE=0 python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $F/bench_n2_gloo_rehearsal.json 2>> $F/bench_default.err
