@@ -197,9 +197,7 @@ __global__ __launch_bounds__(256, 1) void X3_KERNEL(MlpArgs a) {
     for (int i = tid; i < kBiasFloats; i += 256) bias_s[i] = a.bias[i];
     __syncthreads();  // the bias block is read (by other waves) before the first slice barrier
 
-    Diag dg;
     WStream ws;
-    ws.dg = &dg;
     ws.init(a.wstream, kNumSlices, ring, tid, wave);
     PeLane pln;
     pln.init(h);
@@ -213,9 +211,6 @@ __global__ __launch_bounds__(256, 1) void X3_KERNEL(MlpArgs a) {
     PointIn cur, nxt;
     load_point<MODE>(a, blockIdx.x, wave, m, cur);
     nxt = cur;
-#ifdef IDN_TIMING_PE_ONCE
-    f32x4 pe_hi[4], pe_lo[4], pd_hi[2], pd_lo[2];
-#endif
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long P = tile * 128 + wave * 32 + m;
         const bool valid = P < a.n_points;
@@ -223,10 +218,7 @@ __global__ __launch_bounds__(256, 1) void X3_KERNEL(MlpArgs a) {
 
         // ---- inputs: this lane's half of the 64 point features and 32 direction features.
         // Element j of k-step s, lane half h = feature 16s + (j&3) + 8(j>>2) + 4h.
-#ifdef IDN_TIMING_PE_ONCE   // timing-only (wrong results): the encoding of the block's first tile serves every pass
-#else
         f32x4 pe_hi[4], pe_lo[4], pd_hi[2], pd_lo[2];
-#endif
         auto pack_feats = [&](auto&& feat, f32x4* ohi, f32x4* olo, auto NKS) {
             static_for<decltype(NKS)::value>([&](auto S_) {
                 constexpr int s = decltype(S_)::value;
@@ -241,9 +233,6 @@ __global__ __launch_bounds__(256, 1) void X3_KERNEL(MlpArgs a) {
                 });
             });
         };
-#ifdef IDN_TIMING_PE_ONCE
-        if (tile == blockIdx.x)
-#endif
         input_features<MODE>(a, Pc, h, pln, cur, [&](auto&& fpt, auto&& fdir) {
             pack_feats(fpt, pe_hi, pe_lo, ic<4>{});
             pack_feats(fdir, pd_hi, pd_lo, ic<2>{});
@@ -424,15 +413,17 @@ __device__ __forceinline__ void run_layer_plain(Out&& out, Def&& deferred, f32x1
     fr.pref1 = a1;
 }
 
-// NW waves per workgroup, PT point sets of 32 points per wave (32 NW PT points per pass).
-//   NW = 8, PT = 1: two waves on each SIMD; the kernel fits 256 registers in this mode (a few spills), one
-//     wave's conversions / encoding / piece issue run in the shadow of the other wave's MFMAs.  Same-box A/B
-//     against NW = 4, PT = 1: +14 %.  The accumulators then live in VGPRs, so nothing that reads an MFMA
-//     result may be inline asm (the hazard recogniser does not look inside).
-//   NW = 4, PT = 2: one wave per SIMD with 512 registers; every weight fragment read from LDS feeds two
-//     MFMAs (see SidePlain), and two independent accumulators alternate on the pipe.
-template <int MODE, int NW, int PT>
-__global__ __launch_bounds__(64 * NW, 1) void mlp_bf16_kernel(MlpArgs a) {
+// NW = 8 waves per workgroup, PT = 1 point set of 32 points per wave (32 NW PT points per pass): two waves on
+// each SIMD; the kernel fits 256 registers in this mode (a few spills), one wave's conversions / encoding / piece
+// issue run in the shadow of the other wave's MFMAs.  Same-box A/B against NW = 4, PT = 1: +14 %.  The
+// accumulators then live in VGPRs, so nothing that reads an MFMA result may be inline asm (the hazard recogniser
+// does not look inside).  NW = 4, PT = 2 (one wave per SIMD with 512 registers, every weight fragment read from
+// LDS feeding two MFMAs) made no gain (profiles/r02_ab_plain_bf16_two_sets.log).  The set dimension stays in the
+// code at PT = 1: written without it, the same kernel compiles to a different instruction schedule.
+constexpr int kPlainWaves = 8, kPlainSets = 1;
+template <int MODE>
+__global__ __launch_bounds__(64 * kPlainWaves, 1) void mlp_bf16_kernel(MlpArgs a) {
+    constexpr int NW = kPlainWaves, PT = kPlainSets;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;
     float* bias_s = reinterpret_cast<float*>(smem + kRingFrags * kFragBytes);
@@ -443,9 +434,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bf16_kernel(MlpArgs a) {
     for (int i = tid; i < kBiasFloats; i += 64 * NW) bias_s[i] = a.bias[i];
     __syncthreads();
 
-    Diag dg;
     WStreamT<NW> ws;
-    ws.dg = &dg;
     ws.init(a.wstream, kPlainNumSlices, ring, tid, wave);
     PeLane pln;
     pln.init(h);
@@ -463,15 +452,10 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bf16_kernel(MlpArgs a) {
         load_point<MODE, kSets>(a, blockIdx.x, wave * PT + q, m, cur[q]);
         nxt[q] = cur[q];
     });
-#ifdef IDN_TIMING_PE_ONCE   // timing-only (wrong results): the encoding of the block's first tile serves every pass
-    f32x4 pe_v[PT][4], pd_v[PT][2];
-#endif
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         long P[PT];
         bool valid[PT];
-#ifndef IDN_TIMING_PE_ONCE
         f32x4 pe_v[PT][4], pd_v[PT][2];
-#endif
         auto pack_feats = [&](auto&& feat, f32x4* o, auto NKS) {
             static_for<decltype(NKS)::value>([&](auto S_) {
                 constexpr int s = decltype(S_)::value;
@@ -488,9 +472,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bf16_kernel(MlpArgs a) {
             P[q] = tile * kTilePts + (wave * PT + q) * 32 + m;
             valid[q] = P[q] < a.n_points;
             const long Pc = valid[q] ? P[q] : a.n_points - 1;
-#ifdef IDN_TIMING_PE_ONCE
-            if (tile == blockIdx.x)
-#endif
             input_features<MODE>(a, Pc, h, pln, cur[q], [&](auto&& fpt, auto&& fdir) {
                 pack_feats(fpt, pe_v[q], ic<4>{});
                 pack_feats(fdir, pd_v[q], ic<2>{});
@@ -563,24 +544,18 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bf16_kernel(MlpArgs a) {
     __syncthreads();
 }
 
-#ifndef IDN_PLAIN_WAVES
-#define IDN_PLAIN_WAVES 8
-#endif
-#ifndef IDN_PLAIN_SETS
-#define IDN_PLAIN_SETS 1
-#endif
 int launch_mlp_bf16(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                     const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s) {
-    constexpr int NW = IDN_PLAIN_WAVES, PT = IDN_PLAIN_SETS;
+    constexpr int NW = kPlainWaves, PT = kPlainSets;
     if (n_points <= 0) return IDN_OK;
     static LaunchSetup setup;
     int num_cu = 0;
     if (int e = setup.get([]() -> int {
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModeRays, NW, PT>),
+            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModeRays>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModeX, NW, PT>),
+            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModeX>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModePts, NW, PT>),
+            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModePts>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
             return IDN_OK;
         }, &num_cu))
@@ -590,11 +565,11 @@ int launch_mlp_bf16(const float* packed, const float* folded, const float* x, co
     MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, nullptr, 0};
     ProfScope prof(s, n_points);
     if (x)
-        hipLaunchKernelGGL((mlp_bf16_kernel<kModeX, NW, PT>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
+        hipLaunchKernelGGL((mlp_bf16_kernel<kModeX>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
     else if (pts)
-        hipLaunchKernelGGL((mlp_bf16_kernel<kModePts, NW, PT>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
+        hipLaunchKernelGGL((mlp_bf16_kernel<kModePts>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
     else
-        hipLaunchKernelGGL((mlp_bf16_kernel<kModeRays, NW, PT>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
+        hipLaunchKernelGGL((mlp_bf16_kernel<kModeRays>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
     IDN_HIP_CHECK(hipGetLastError());
     return IDN_OK;
 }

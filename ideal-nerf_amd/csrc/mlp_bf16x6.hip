@@ -58,9 +58,6 @@ __device__ __forceinline__ void convert_word(f32x16& acc, KP& out, const Recorde
 }
 template <int T, int Q>
 __device__ __forceinline__ void store_quad(const f32x16& acc, const Recorder& rec) {
-#ifdef IDN_TIMING_NO_ROW_STORES   // timing-only experiment (wrong results): what do the row stores cost?
-    return;
-#endif
     *reinterpret_cast<f32x4*>(rec.row + 32 * T + 8 * Q) = f32x4{acc[4 * Q], acc[4 * Q + 1], acc[4 * Q + 2], acc[4 * Q + 3]};
 }
 
@@ -113,14 +110,8 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x6_kernel(MlpArgs a) {
     for (int i = tid; i < kBiasFloats; i += 256) bias_s[i] = a.bias[i];
     __syncthreads();  // the bias block is read (by other waves) before the first slice barrier
 
-    Diag dg;
     WS ws;
-    ws.dg = &dg;
-#ifdef IDN_TIMING_STREAM_WRAP   // timing-only (wrong results): the stream wraps after this many slices -- is anything left of the L2 question?
-    ws.init(a.wstream, IDN_TIMING_STREAM_WRAP, ring, tid, wave);
-#else
     ws.init(a.wstream, kX6NumSlices, ring, tid, wave);
-#endif
     PeLane pln;
     pln.init(h);
 
@@ -136,7 +127,6 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x6_kernel(MlpArgs a) {
     nxt = cur;
     f32x4 pref[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        DIAG_ONLY(const unsigned long long t_tile = clock64(); dg.begin();)
         const long P = tile * 128 + wave * 32 + m;
         const bool valid = P < a.n_points;
         const long Pc = valid ? P : a.n_points - 1;
@@ -184,7 +174,6 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x6_kernel(MlpArgs a) {
             pack_feats(pe_f, pe_p, ic<4>{});
             pack_feats(pd_f, pd_p, ic<2>{});
         }
-        DIAG_END(dg, kDgInput);
 
         f32x16 X[8], Y[8];   // two sets of accumulator tiles: output and input of consecutive layers, alternating
         using Views0Stores = Views0StoresT<SAVE>;
@@ -326,28 +315,13 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x6_kernel(MlpArgs a) {
             o.w = sigma;
             *reinterpret_cast<f32x4*>(a.raw + P * 4) = o;
         }
-        DIAG_ONLY(dg.acc[kDgTotal] += clock64() - t_tile;)
         cur = nxt;
     }
-#ifdef IDN_DIAG   // diagnostic build only: per-wave cycle totals by category (tools/diag_mlp_x6.py)
-    if (lane == 0)
-        for (int c = 0; c < 5; ++c) atomicAdd(&g_diag[c], dg.acc[c]);
-    if (lane == 0) atomicAdd(&g_diag[5], 1ull);
-#endif
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
 }
 
 }  // namespace x6
-
-#ifdef IDN_DIAG
-extern "C" int idealnerf_diag_read_x6(unsigned long long* out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_diag), 8 * sizeof(unsigned long long)) != hipSuccess) return -3;
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_diag), z, sizeof(z)) != hipSuccess) return -3;
-    return 0;
-}
-#endif
 
 int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                       const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,

@@ -23,31 +23,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-// Diagnostic build only (-DIDN_DIAG): per-wave cycle totals by category, written to a buffer
-// nothing else reads.  Never compiled into the shipped library (cdna_hip_programming.md 7).
-#ifdef IDN_DIAG
-#define DIAG_ONLY(x) x
-__device__ unsigned long long g_diag[8];
-enum { kDgTotal = 0, kDgInput = 1, kDgBarrier = 2, kDgBoundary = 3, kDgStore = 4 };
-struct Diag {
-    unsigned long long acc[5] = {0, 0, 0, 0, 0};
-    unsigned long long t0 = 0;
-    __device__ __forceinline__ void begin() { __builtin_amdgcn_sched_barrier(0); t0 = clock64(); __builtin_amdgcn_sched_barrier(0); }
-    __device__ __forceinline__ void end(int cat) {
-        __builtin_amdgcn_sched_barrier(0);
-        acc[cat] += clock64() - t0;
-        __builtin_amdgcn_sched_barrier(0);
-    }
-};
-#define DIAG_BEGIN(d) (d).begin()
-#define DIAG_END(d, c) (d).end(c)
-#else
-#define DIAG_ONLY(x)
-struct Diag {};
-#define DIAG_BEGIN(d)
-#define DIAG_END(d, c)
-#endif
-
 #define GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
@@ -83,7 +58,6 @@ struct WStreamT {
     static constexpr int kVmcntOpen = (kAheadT - 1) * kPieces;     // younger pieces allowed in flight at a barrier
     static_assert(kSliceBytesT % kPieceBytes == 0 && kPieces % 4 == 0, "a wave's pieces come in groups of four (one M0 / scalar offset per group)");
 
-    Diag* dg;
     __amdgpu_buffer_rsrc_t rsrc;
     uint32_t voff;      // this lane's 16-byte column inside a piece
     uint32_t soff;      // byte offset of the slice currently being fetched (wave-uniform)
@@ -143,12 +117,10 @@ struct WStreamT {
     // so they may stay in flight: a wait for them here would park every wave behind its own burst of writes.
     template <int YOUNGER = 0>
     __device__ __forceinline__ void open_slice() {
-        DIAG_BEGIN(*dg);
         static_assert(kVmcntOpen + YOUNGER <= 63, "vmcnt is a 6-bit field");
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kVmcntOpen + YOUNGER) : "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        DIAG_END(*dg, kDgBarrier);
     }
     // the piece (if any) to issue at the pair-step that consumes fragment F
     template <int F>
@@ -195,10 +167,6 @@ struct FragReader {
     // all but the newest `Newer` LDS reads of this wave have completed => v0, v1 are valid
     template <int Newer>
     static __device__ __forceinline__ void retire(f32x4& v0, f32x4& v1) {
-#ifdef IDN_TIMING_NO_FRAG_WAIT   // timing-only experiment (wrong results): is the fragment-read latency exposed?
-        asm volatile("" : "+v"(v0), "+v"(v1)::"memory");
-        return;
-#endif
         if constexpr (Newer == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v0), "+v"(v1)::"memory");
         else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(v0), "+v"(v1)::"memory");
     }

@@ -56,9 +56,6 @@ struct SaveSide {
     template <int T, int Q>
     __device__ __forceinline__ void rows_store(ic<T>, ic<Q>) const {
         asm volatile("" : "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]));   // not before the wait that precedes this call
-#ifdef IDN_TIMING_NO_ROW_STORES   // timing-only experiment (wrong results): what do the row stores cost?
-        return;
-#endif
         static_for<4>([&](auto I) {
             constexpr int i = decltype(I)::value;
             // descriptor + one lane-offset VGPR + a compile-time scalar offset: no per-row address arithmetic or registers
@@ -67,9 +64,6 @@ struct SaveSide {
     }
     template <int T>
     __device__ __forceinline__ void flush_tile(ic<T>) const {   // outside the pair-step pipeline: explicit waits
-#ifdef IDN_TIMING_NO_FLUSH   // timing-only experiment (wrong results): what do the exposed layer-end flushes cost?
-        return;
-#endif
         scatter(ic<T>{});
         static_for<4>([&](auto Q) {
             rows_read(Q);
@@ -118,9 +112,7 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
     for (int i = tid; i < kBiasFloats; i += 256) bias_s[i] = a.bias[i];
     __syncthreads();  // the bias block is read (by other waves) before the first slice barrier
 
-    Diag dg;
     WStream ws;
-    ws.dg = &dg;
     ws.init(a.wstream, kNumSlices, ring, tid, wave);
     PeLane pln;
     pln.init(h);
@@ -135,7 +127,6 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
     load_point<MODE>(a, blockIdx.x, wave, m, cur);
     nxt = cur;
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        DIAG_ONLY(const unsigned long long t_tile = clock64(); dg.begin();)
         const long P = tile * 128 + wave * 32 + m;
         const bool valid = P < a.n_points;
         const long Pc = valid ? P : a.n_points - 1;
@@ -190,7 +181,6 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
                 });
             }
         }
-        DIAG_END(dg, kDgInput);
 
         float rgb[3], sigma;
         if constexpr (!SAVE) {
@@ -228,9 +218,7 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
                     if constexpr (MODE != kModeX && F0 == layer_f0(5)) load_point<MODE>(a, tile + gridDim.x, wave, m, nxt);
                     if constexpr (MODE != kModeX && F0 == layer_f0(6)) touch_point(nxt);
                 };
-                DIAG_BEGIN(dg);
                 load_bias<NT>(out, bias_l);
-                DIAG_END(dg, kDgBoundary);
                 if (save_idx >= 0) {  // hidden layer: ReLU + record, in the MFMA shadow
                     const SaveSide<NT, KG / 2, 32 * NT> side{mk, &out[0], rows_rsrc(a.acts + (long)act_off(save_idx) * a.p_pad + p0 * (32 * NT), 32 * NT),
                                                              (uint32_t)((h * (32 * NT) + m) * 4), stage, rb, raddr, m, h};
@@ -297,7 +285,6 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
                 sigma = bias_s[bias_off(8) + kSigmaChannel] + (part + __shfl_xor(part, 32, 64));   // both lane halves
             }
             {
-                DIAG_BEGIN(dg);
                 f32x16(&V4)[4] = reinterpret_cast<f32x16(&)[4]>(V);
                 static_for<4>([&](auto T) { collect_signs<decltype(T)::value>(V4[decltype(T)::value], mk); });
                 store_mask(kActV1 - kActA1);   // v1 -> 8
@@ -305,7 +292,6 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
                 const SaveSide<4, 1, 128> side{mk, &V4[0], rows_rsrc(a.acts + (long)act_off(kActV1) * a.p_pad + p0 * 128, 128),
                                                (uint32_t)((h * 128 + m) * 4), stage, rb, raddr, m, h};
                 static_for<4>([&](auto T) { side.flush_tile(T); });
-                DIAG_END(dg, kDgBoundary);
             }
             // ---- views_linears.1, .2 : 128 -> 128   (V -> A[0..3] -> V[0..3])
             f32x16(&A4)[4] = reinterpret_cast<f32x16(&)[4]>(A);
@@ -345,7 +331,6 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
             }
         }
 
-        DIAG_BEGIN(dg);
         if (valid && h == 0) {
             f32x4 o;
             o.x = rgb[0];
@@ -354,15 +339,8 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
             o.w = sigma;
             *reinterpret_cast<f32x4*>(a.raw + P * 4) = o;
         }
-        DIAG_END(dg, kDgStore);
-        DIAG_ONLY(dg.acc[kDgTotal] += clock64() - t_tile;)
         cur = nxt;
     }
-#ifdef IDN_DIAG
-    if (lane == 0)
-        for (int c = 0; c < 5; ++c) atomicAdd(&g_diag[c], dg.acc[c]);
-    if (lane == 0) atomicAdd(&g_diag[5], 1ull);
-#endif
     // drain the slice prefetched for a pass that will not happen
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
@@ -402,14 +380,5 @@ int launch_mlp_f32(const float* packed, const float* folded, const float* x, con
     IDN_HIP_CHECK(hipGetLastError());
     return IDN_OK;
 }
-
-#ifdef IDN_DIAG
-extern "C" int idealnerf_diag_read(unsigned long long* out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_diag), 8 * sizeof(unsigned long long)) != hipSuccess) return -3;
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_diag), z, sizeof(z)) != hipSuccess) return -3;
-    return 0;
-}
-#endif
 
 }  // namespace idn

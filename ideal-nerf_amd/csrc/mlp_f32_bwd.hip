@@ -181,9 +181,6 @@ struct MaskSide {
     template <int T, int Q>
     __device__ __forceinline__ void rows_store(ic<T>, ic<Q>) const {
         asm volatile("" : "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]));   // not before the wait that precedes this call
-#ifdef IDN_TIMING_NO_ROW_STORES   // timing-only experiment (wrong results): what do the row stores cost?
-        return;
-#endif
         static_for<4>([&](auto I) {
             constexpr int i = decltype(I)::value;
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rb[i]), rsrc, voff, (2 * (4 * Q + i) * LD + 32 * T) * 4, 0);
@@ -191,9 +188,6 @@ struct MaskSide {
     }
     template <int T>
     __device__ __forceinline__ void flush_tile(ic<T>) const {   // outside the pair-step pipeline: explicit waits
-#ifdef IDN_TIMING_NO_FLUSH   // timing-only experiment (wrong results): what do the exposed layer-end flushes cost?
-        return;
-#endif
         scatter(ic<T>{});
         static_for<4>([&](auto Q) {
             rows_read(Q);
@@ -236,9 +230,7 @@ __global__ __launch_bounds__(256, 1) void delta_chain_kernel(DeltaArgs a) {
     const int m = lane & 31, h = lane >> 5;
     float* stage = reinterpret_cast<float*>(smem + kRingFrags * kFragBytes) + wave * kStageFloats;
 
-    Diag dg;
     WStream ws;
-    ws.dg = &dg;
     ws.init(a.wstream, kBwdNumSlices, ring, tid, wave);
     FragReader fr;
     fr.addr0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring + lane * 16;
@@ -388,6 +380,8 @@ __global__ void pack_bf16x6_bwd_kernel(BwdPackDesc d, uint4* out) {
     out[gid] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// the delta chain's stream buffer (train.hip, carve_bwd) is sized by this and serves the fp32 pipe's stream as well
+static_assert(kBwd6StreamFrags >= kBwdStreamFrags, "the six-piece stream is the larger of the two");
 size_t bwd_stream_floats_x6() { return (size_t)kBwd6StreamFrags * kFragFloats; }
 
 int launch_pack_bf16x6_bwd(const idn_facenerf_params& p, float* packed_bwd, hipStream_t s) {
@@ -465,7 +459,6 @@ struct MaskStoreSide {
     f32x16* O;
     const uint32_t* mk;   // dword k = tiles 2k, 2k+1, value i of the pair at bit 31 - i
     float* row;           // this lane's row of the delta matrix + 4 h
-    float* lin;           // timing-only experiment: first float of this wave's 32 rows + 4 lane
     template <int T>
     __device__ __forceinline__ void apply(ic<T>) const {
         const uint32_t w = mk[T >> 1];
@@ -477,9 +470,6 @@ struct MaskStoreSide {
     }
     template <int T, int Q0>
     __device__ __forceinline__ void store2(ic<T>, ic<Q0>) const {
-#ifdef IDN_TIMING_NO_ROW_STORES   // timing-only experiment (wrong results): what do the row stores cost?
-        return;
-#endif
         static_for<2>([&](auto I) {
             constexpr int q = Q0 + decltype(I)::value;
             *reinterpret_cast<f32x4*>(row + 32 * T + 8 * q) = f32x4{O[T][4 * q], O[T][4 * q + 1], O[T][4 * q + 2], O[T][4 * q + 3]};
@@ -493,13 +483,6 @@ struct MaskStoreSide {
     }
     template <int T, int Q>
     __device__ __forceinline__ void store1(ic<T>, ic<Q>) const {
-#ifdef IDN_TIMING_NO_ROW_STORES
-        return;
-#endif
-#ifdef IDN_TIMING_LINEAR_ROW_STORES   // timing-only (wrong layout): the same bytes into the same 32 rows, 1 KiB contiguous per instruction
-        *reinterpret_cast<f32x4*>(lin + (T * 4 + Q) * 256) = f32x4{O[T][4 * Q], O[T][4 * Q + 1], O[T][4 * Q + 2], O[T][4 * Q + 3]};
-        return;
-#endif
         *reinterpret_cast<f32x4*>(row + 32 * T + 8 * Q) = f32x4{O[T][4 * Q], O[T][4 * Q + 1], O[T][4 * Q + 2], O[T][4 * Q + 3]};
     }
     // A trunk stage's tile is exactly one slice of the stream, and a wave issues its pieces of the next slice in the FIRST
@@ -524,9 +507,7 @@ __global__ __launch_bounds__(256, 1) void delta_chain_x6_kernel(DeltaArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 31, h = lane >> 5;
 
-    Diag dg;
     WStream6 ws;
-    ws.dg = &dg;
     ws.init(a.wstream, kBwd6NumSlices, ring, tid, wave);
     FragReader fr;
     fr.addr0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring + lane * 16;
@@ -577,7 +558,7 @@ __global__ __launch_bounds__(256, 1) void delta_chain_x6_kernel(DeltaArgs a) {
             const u32x4 mv = mask_nxt;
             const uint32_t mk[4] = {mv.x, mv.y, mv.z, mv.w};
             if (next_id >= 0) mask_nxt = mask_load(next_id);
-            const MaskStoreSide<decltype(KSc)::value> side{O, mk, dst + P * LD + 4 * h, dst + (P & ~31L) * LD + 4 * lane};
+            const MaskStoreSide<decltype(KSc)::value> side{O, mk, dst + P * LD + 4 * h};
             // a trunk stage after the first opens its first slice behind the row stores of tiles 6 and 7 of the stage before it
             constexpr bool trunk = decltype(F0c)::value >= bwd6_f0(4);
             run_stage6<decltype(F0c)::value, NT, decltype(KSc)::value, decltype(LASTc)::value != 0, decltype(YOUNGERc)::value, (trunk ? 4 : 0)>(O, bget, ws, fr, pref, side);

@@ -135,9 +135,6 @@ constexpr int store_slot(int nt, int q) { return nt >= 8 ? nt - 2 + q : conv_slo
 template <int NT, int FROM, int TO, bool SAVE>
 struct Stores {
     static constexpr int at(int s, int t) {
-#ifdef IDN_TIMING_NO_ROW_STORES   // the timing-only build issues no row stores: nothing may be counted as in flight
-        return 0;
-#endif
         return (SAVE && s + 1 >= FROM && s + 1 < TO) ? (t == store_slot(NT, 0)) + (t == store_slot(NT, 1)) : 0;
     }
     // stores of the steps [i0, i1] of the layer (clipped to it)

@@ -97,9 +97,7 @@ __global__ __launch_bounds__(256, 1) void render_fused_kernel(FusedArgs a) {
     const int m = lane & 31, h = lane >> 5;
     float* scratch = reinterpret_cast<float*>(uni + kFG * kFS * 16) + wave * kFScratchFloats;
 
-    Diag dg;
     std::conditional_t<kWhole, WStreamDual, WStream> ws;
-    ws.dg = &dg;
     if constexpr (kWhole) ws.init_dual(a.wstream_c, a.wstream_f, kFCoarsePasses, kFPasses, kNumSlices, ring, tid, wave);
     else ws.init(PHASE == kFusedCoarse ? a.wstream_c : a.wstream_f, kNumSlices, ring, tid, wave);
     PeLane pln;

@@ -111,26 +111,19 @@ __device__ __forceinline__ void tn_static_for(F&& f) {
 // row offset (half the issue cost of the per-lane-pointer form), and they have a whole chunk to land: the
 // GEMM reads 2 KiB per point and layer for 131 kFLOP, i.e. it needs 2.5 TB/s of HBM at the MFMA peak.
 constexpr int kTnRows = 16, kTnBufs = 3;
-#ifndef IDN_DELTA_X6
-#define IDN_DELTA_X6 1  // the backward delta chain as six bf16 piece products per fp32 product (delta_chain_x6_kernel); 0: fp32 MFMA
-#endif
-#ifndef IDN_DW_X6
-#define IDN_DW_X6 1    // 256 x 256 dW GEMMs as six bf16 piece products (gemm_tn_x6_kernel); 0: the fp32-MFMA kernel
-#endif
-
-#ifdef IDN_DIAG   // diagnostic build only: where a <4,4> block spends its cycles (tools/diag_tn.py)
-__device__ unsigned long long g_tn_diag[8];   // total, wait (vmcnt + barrier), loop, epilogue, blocks, chunks
-#define TN_STAMP(v) do { __builtin_amdgcn_sched_barrier(0); v = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define TN_STAMP(v)
-#endif
+// The narrow shapes (256 x 64, 128 x 64, 64 x 128 outputs: pts_linears.0, the encoding columns of pts_linears.5, the direction
+// columns of views_linears.0, rgb_linear) are HBM-shaped: ring depth and workgroups per CU decide how many bytes they keep in flight
+constexpr int kTnNarrowBufs = 3;
+// points per chunk of the narrow shapes: 256 x 64 (40 KiB per 32-point chunk) and 128 x 64 / 64 x 128 (48 KiB per 64-point chunk)
+constexpr int kTnRows4x1 = 32, kTnRowsThin = 64;
+constexpr int kTnNarrowSplits = 256;
 
 // NB = LDS buffers of the chunk ring: the pieces of chunk c + NB - 1 are issued while chunk c is multiplied.  The 256 x 256
 // shape (32 KiB per chunk, 16 MFMAs per point pair and wave) runs NB = 3; the narrow shapes do a quarter of the arithmetic per
 // byte (a 256 x 64 chunk is 20 KiB for 4 MFMAs per point pair: 1 us of matrix time, less than a loaded HBM round trip) and
 // run a deeper ring, so that several chunks per workgroup are in flight.
 // R = points per chunk (a multiple of 16).  A chunk costs ~1 000 cycles besides its MFMAs (the barrier and its skew, the first LDS
-// reads behind it with nothing to overlap, the drain of the prefetched reads at its end: in-kernel stamps, tools/diag_tn.py:
+// reads behind it with nothing to overlap, the drain of the prefetched reads at its end: in-kernel stamps, profiles/r04_diag_tn_4x1.log:
 // 3 007 cycles per 16-point chunk of the 256 x 64 shape against 2 048 of MFMAs), so the shapes with few MFMAs per point take
 // larger chunks.
 template <int NTW, int KTW, int NB = kTnBufs, int R = kTnRows>
@@ -157,9 +150,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
         for (int b = 0; b < KTW; ++b)
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-    unsigned long long dg_t0 = 0, dg_a = 0, dg_b = 0, dg_wait = 0, dg_loop = 0, dg_t1 = 0, dg_t2 = 0;
-    (void)dg_t0; (void)dg_a; (void)dg_b; (void)dg_wait; (void)dg_loop; (void)dg_t1; (void)dg_t2;
-    TN_STAMP(dg_t0);
     const long c_begin = (long)split * g.chunks_per_split;
     long c_end = c_begin + g.chunks_per_split;
     const long c_total = g.P / R;
@@ -183,17 +173,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
     // into buffer `buf`: scalar arithmetic only (a piece that had to choose between the two matrices cost a
     // tree of scalar branches per point pair, ~10 % of the loop)
     auto piece_a = [&](long c, int buf, int ja) {
-#ifdef IDN_TN_TIMING_NO_PIECES   // timing-only experiment (wrong results): the GEMM without its HBM traffic
-        if (c > c_begin + 1) return;
-#endif
         const int pc = NPA * w + ja;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (__attribute__((address_space(3))) void*)(tn_smem + buf * kTileFloats + pc * 256), 16, voffA,
                                                  (uint32_t)(((c - c_begin) * R + pc * kRowsPerPieceA) * rowA), 0, 0);
     };
     auto piece_b = [&](long c, int buf, int jb) {
-#ifdef IDN_TN_TIMING_NO_PIECES
-        if (c > c_begin + 1) return;
-#endif
         const int pc = NPB * w + jb;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcB, (__attribute__((address_space(3))) void*)(tn_smem + buf * kTileFloats + R * BN + pc * 256), 16, voffB,
                                                  (uint32_t)(((c - c_begin) * R + pc * kRowsPerPieceB) * rowB), 0, 0);
@@ -212,20 +196,14 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
         for (int j = 0; j < NP; ++j) piece(c_begin + ahead < c_end ? c_begin + ahead : c_end - 1, ahead, j);
     int buf = 0;
     for (long c = c_begin; c < c_end; ++c) {
-        TN_STAMP(dg_a);
         // this wave's pieces of chunk c have landed (those of chunks c + 1 .. c + NB - 2, issued later, may still be in flight)
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 2) * NP) : "memory");
         // everyone's have; everyone is done with chunk c - 1, whose buffer chunk c + 2 now takes.  A raw barrier:
         // __syncthreads() would add its own vmcnt(0) and wait for the pieces of chunk c + 1 as well
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        TN_STAMP(dg_b);
-#ifdef IDN_DIAG
-        dg_wait += dg_b - dg_a;
-#endif
         const int buf2 = buf >= 1 ? buf - 1 : NB - 1;   // (buf + NB - 1) % NB: the buffer chunk c - 1 has just left
         const long cnext = c + NB - 1 < c_end ? c + NB - 1 : c_end - 1;   // clamped: the re-read of the last chunk is never used
-        constexpr bool more = true;
         // The delta tile is in LDS anyway: its column sums are the bias gradient.  The R reads of column
         // `tid` go out first (inline asm, like the operand reads) and are added after the first counted wait of
         // the loop below, which covers them (LDS returns in order): read by plain loads they parked every wave
@@ -278,7 +256,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
             for (int it = 0; it < kSteps / 4; ++it) {
                 step(a0v, b0v,
                      [&]() { a1v.template issue<kStepA>(pa); b1v.template issue<kStepB>(pb); },
-                     [&]() { if (more && 2 * it < NPA) piece_a(cnext, buf2, 2 * it); },
+                     [&]() { if (2 * it < NPA) piece_a(cnext, buf2, 2 * it); },
                      [&]() {
                          if (colsum_block && it < R / 16) {   // batch `it` of the column reads is older than a0v / b0v: retired with them
                              tn_static_for<16>([&](auto Row) { csum += landed(cs[decltype(Row)::value]); });
@@ -288,7 +266,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
                      });
                 step(a1v, b1v,
                      [&]() { a0v.template issue<0>(pa); b0v.template issue<0>(pb); },
-                     [&]() { if (more && 2 * it + 1 < NPA) piece_a(cnext, buf2, 2 * it + 1); },
+                     [&]() { if (2 * it + 1 < NPA) piece_a(cnext, buf2, 2 * it + 1); },
                      [&]() { if (colsum_block && it + 1 < R / 16) cs_issue(it + 1); });
             }
 #pragma unroll 1
@@ -296,7 +274,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
                 const bool last = it == kSteps / 4 - 1;
                 step(a0v, b0v,
                      [&]() { a1v.template issue<kStepA>(pa); b1v.template issue<kStepB>(pb); },
-                     [&]() { if (more && 2 * it < NPB) piece_b(cnext, buf2, 2 * it); },
+                     [&]() { if (2 * it < NPB) piece_b(cnext, buf2, 2 * it); },
                      [&]() {
                          // the pair after next; past the last pair the read is repeated on the current rows (never used):
                          // one loop shape for all iterations keeps the accumulators where they are
@@ -305,7 +283,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
                      });
                 step(a1v, b1v,
                      [&]() { a0v.template issue<0>(pa); b0v.template issue<0>(pb); },
-                     [&]() { if (more && 2 * it + 1 < NPB) piece_b(cnext, buf2, 2 * it + 1); },
+                     [&]() { if (2 * it + 1 < NPB) piece_b(cnext, buf2, 2 * it + 1); },
                      [&]() {});
             }
         } else {
@@ -348,33 +326,28 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
 #pragma unroll 1
             for (int it = 0; it < kSteps / 8; ++it) {
                 quad(a0v, b0v, a1v, b1v, a2v, b2v, a3v, b3v, false,
-                     [&]() { if (more && 2 * it < NPA) piece_a(cnext, buf2, 2 * it); },
+                     [&]() { if (2 * it < NPA) piece_a(cnext, buf2, 2 * it); },
                      [&]() {
                          if (colsum_block && it < R / 16) {   // batch `it` of the column reads is older than these operand reads: retired with them
                              tn_static_for<16>([&](auto Row) { csum += landed(cs[decltype(Row)::value]); });
                          }
                      });
                 quad(a2v, b2v, a3v, b3v, a0v, b0v, a1v, b1v, false,
-                     [&]() { if (more && 2 * it + 1 < NPA) piece_a(cnext, buf2, 2 * it + 1); },
+                     [&]() { if (2 * it + 1 < NPA) piece_a(cnext, buf2, 2 * it + 1); },
                      [&]() { if (colsum_block && it + 1 < R / 16) cs_issue(it + 1); });
             }
 #pragma unroll 1
             for (int it = 0; it < kSteps / 8; ++it) {
                 quad(a0v, b0v, a1v, b1v, a2v, b2v, a3v, b3v, false,
-                     [&]() { if (more && 2 * it < NPB) piece_b(cnext, buf2, 2 * it); }, [&]() {});
+                     [&]() { if (2 * it < NPB) piece_b(cnext, buf2, 2 * it); }, [&]() {});
                 quad(a2v, b2v, a3v, b3v, a0v, b0v, a1v, b1v, it == kSteps / 8 - 1,
-                     [&]() { if (more && 2 * it + 1 < NPB) piece_b(cnext, buf2, 2 * it + 1); }, [&]() {});
+                     [&]() { if (2 * it + 1 < NPB) piece_b(cnext, buf2, 2 * it + 1); }, [&]() {});
             }
             lds_retire<0>(a1v, b1v);
         }
         lds_retire<0>(a0v, b0v);   // drain the repeated read before these registers are reused
         buf = buf + 1 == NB ? 0 : buf + 1;
-        TN_STAMP(dg_a);
-#ifdef IDN_DIAG
-        dg_loop += dg_a - dg_b;
-#endif
     }
-    TN_STAMP(dg_t1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-reads of the last chunk: nothing may land in LDS after this workgroup has left
     if (do_colsum) g.cpart[(long)split * g.N + n0 + tid] = csum;
     // this lane holds, for tile (x, y) register r: output (n0 + NTW (32 wr + d_row(r, hh)) + x, k0 + KTW (32 wc + i) + y):
@@ -393,21 +366,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TNArgs g) {
                 for (int y = 0; y < KTW; ++y) dst[y] = acc[x][y][r];
             }
         }
-#ifdef IDN_DIAG
-    __builtin_amdgcn_s_waitcnt(0);
-    TN_STAMP(dg_t2);
-#ifndef IDN_DIAG_KTW
-#define IDN_DIAG_KTW 4      // which 4-row-tile shape the stamps are collected for: <4,4> (default) or <4,1> (-DIDN_DIAG_KTW=1)
-#endif
-    if (NTW == 4 && KTW == IDN_DIAG_KTW && tid == 0) {
-        atomicAdd(&g_tn_diag[0], dg_t2 - dg_t0);
-        atomicAdd(&g_tn_diag[1], dg_wait);
-        atomicAdd(&g_tn_diag[2], dg_loop);
-        atomicAdd(&g_tn_diag[3], dg_t2 - dg_t1);
-        atomicAdd(&g_tn_diag[4], 1ull);
-        atomicAdd(&g_tn_diag[5], (unsigned long long)(c_end - c_begin));
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -467,19 +425,7 @@ __device__ __forceinline__ void x6_retire(X6Frag (&f)[3]) {
 }
 
 // One 256 x 256 product (one split of the points) of the batch below.
-#ifdef IDN_DIAG_X6   // diagnostic build only: where a chunk of the bf16-piece dW GEMM spends its cycles (tools/diag_tn_x6.py)
-__device__ unsigned long long g_x6_diag[8];   // row 0, rows 1..3 up to the barrier, barrier, tail, prologue + epilogue, chunks, workgroups
-// s_memtime returns through lgkmcnt, which the kernel counts by hand for its LDS reads: the stamp waits for itself on the spot,
-// at points where no counted read is younger than what the code is about to wait for anyway
-#define X6_STAMP(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory")
-#else
-#define X6_STAMP(v)
-#endif
 __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split, char* x6_smem) {
-#ifdef IDN_DIAG_X6
-    unsigned long long dx_t0 = 0, dx_a = 0, dx_b = 0, dx_c = 0, dx_d = 0, dx_row0 = 0, dx_rows = 0, dx_bar = 0, dx_tail = 0, dx_loop0 = 0, dx_loop1 = 0;
-    X6_STAMP(dx_t0);
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, hh = lane >> 5;
@@ -501,7 +447,7 @@ __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split
     // reload got a fresh register and a copy at the loop end -- behind a wait for the load, a chunk early.  vmcnt is
     // therefore counted by hand: loads are issued in ONE order (delta rows 0..15, activation rows 0..15) everywhere,
     // so when pair j is split, exactly 30 loads are younger than its second row.
-    // (With cache-hot reloads -- -DIDN_X6_TIMING_SAME_ROWS -- the kernel is 8 % faster; a second register set per matrix -- two
+    // (With cache-hot reloads -- a timing-only build, profiles/r04_ab_x6_same_rows.log -- the kernel is 8 % faster; a second register set per matrix -- two
     // chunks in flight, vmcnt(62) -- was built and measured in round 4: no gain, so it is not the prefetch depth.  profiles/HISTORY.md)
     auto make_rsrc = [](const float* ptr) {
         const uint64_t a64 = (uint64_t)(uintptr_t)ptr;
@@ -565,10 +511,7 @@ __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split
     // The fragments of a chunk's FIRST tile row (fa[0], fb[0], fb[1]: nine reads) are issued one chunk EARLY: the chunk barrier
     // sits behind MFMA 59 of the 72 of rows 1..3 -- by then this wave's pieces of the next chunk are stored (slices end at MFMA
     // 51) and fa[0] / fb[0] / fb[1] have had their last use -- so the next chunk's first reads run under the last twelve MFMAs
-    // instead of behind a barrier with nothing to overlap (IDN_X6_EARLY_BARRIER=0: the barrier at the end of the chunk).
-#ifndef IDN_X6_EARLY_BARRIER
-#define IDN_X6_EARLY_BARRIER 1
-#endif
+    // instead of behind a barrier with nothing to overlap (profiles/r04_ab_x6_early_barrier.log).
     X6Frag fa[4][3], fb[4][3];
     auto issue_first_row = [&](uint32_t pa, uint32_t pb) {
         tn_static_for<3>([&](auto Q) { fa[0][decltype(Q)::value].template issue<decltype(Q)::value * kFragBytes>(pa); });
@@ -578,15 +521,12 @@ __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split
             });
         });
     };
-    if (IDN_X6_EARLY_BARRIER) issue_first_row(a_base, b_base);
-    X6_STAMP(dx_loop0);
+    issue_first_row(a_base, b_base);
 #pragma unroll 1
     for (int rc = 0; rc < n_chunks; ++rc) {
-        X6_STAMP(dx_a);
         const int buf = rc & 1;
         const uint32_t pa = a_base + buf * kX6BufBytes, pb = b_base + buf * kX6BufBytes;
         // issue order = consumption order: row 0 (nine of its reads are already in flight), then the other delta tiles
-        if (!IDN_X6_EARLY_BARRIER) issue_first_row(pa, pb);
         tn_static_for<2>([&](auto Y) {
             tn_static_for<3>([&](auto Q) {
                 fb[decltype(Y)::value + 2][decltype(Q)::value].template issue<((decltype(Y)::value + 2) * 3 + decltype(Q)::value) * kFragBytes>(pb);
@@ -615,45 +555,28 @@ __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split
         x6_retire<0>(fa[1]);
         x6_retire<0>(fa[2]);
         x6_retire<0>(fa[3]);
-        X6_STAMP(dx_b);
         // Rows 1..3: 72 MFMAs, each followed by one SLICE of the side work (the next chunk's split + store, the reloads
         // with the chunk after it) and a scheduling fence: at most ~6 vector instructions, two loads or one store behind
         // an MFMA that occupies the pipe for 32 cycles.  (Left alone, hipcc issues 40 MFMAs back to back and then 50
         // vector and memory instructions in a row, during which the matrix pipe runs dry: 57 % busy.)
         const unsigned live_mask = rc + 1 < n_chunks ? 0xffffffffu : 0u;   // the clamped re-read of the last chunk does not count
-#ifdef IDN_X6_TIMING_SAME_ROWS   // timing-only experiment (wrong results): every reload re-reads this split's first chunk (cache hits)
-        const int nbase = 0;
-#else
         const int nbase = (rc + 2 < n_chunks ? rc + 2 : n_chunks - 1) * kTnRows;   // chunk rc + 2, clamped (re-read, never used)
-#endif
         char* const dst = my_slot + (buf ^ 1) * kX6BufBytes;
         unsigned pw[2][3][8];
         float t0 = 0.f, t1 = 0.f;
-        // Timing-only experiments (WRONG results), -DIDN_X6_TIMING_DROP=<bits>: 1 drops the split arithmetic of the slices, 2 their LDS
-        // stores, 4 their reloads -- which part of the side work costs the matrix pipe its idle cycles (profiles/HISTORY.md, round 4)
-#ifndef IDN_X6_TIMING_DROP
-#define IDN_X6_TIMING_DROP 0
-#endif
         auto slice = [&](auto X_, auto S_) {
             constexpr int X = decltype(X_)::value, sl = decltype(S_)::value;
             float (&r)[kTnRows] = *(X ? &rb : &ra);
             auto store = [&](auto Q_, auto H_) {
                 constexpr int q = decltype(Q_)::value, h2 = decltype(H_)::value;
-                if constexpr (IDN_X6_TIMING_DROP & 2) return;
                 *reinterpret_cast<tn_u32x4*>(dst + X * (8 * 3 * kFragBytes) + q * kFragBytes + h2 * 512) =
                     tn_u32x4{pw[X][q][4 * h2], pw[X][q][4 * h2 + 1], pw[X][q][4 * h2 + 2], pw[X][q][4 * h2 + 3]};
             };
             if constexpr (sl < 24) {
                 constexpr int j = sl / 3, ph = sl % 3;
-                if constexpr (ph == 0 && (IDN_X6_TIMING_DROP & 1)) {
-                    if constexpr (!(IDN_X6_TIMING_DROP & 4)) asm volatile("s_waitcnt vmcnt(30)" : "+v"(r[2 * j]), "+v"(r[2 * j + 1])::"memory");
-                    pw[X][0][j] = __float_as_uint(r[2 * j]);
-                    pw[X][1][j] = __float_as_uint(r[2 * j + 1]);
-                    pw[X][2][j] = __float_as_uint(r[2 * j]);
-                } else if constexpr (ph == 1 && (IDN_X6_TIMING_DROP & 1)) {
-                } else if constexpr (ph == 0) {
+                if constexpr (ph == 0) {
                     // rows 2 j, 2 j + 1 of the chunk being split have landed: 30 younger loads may still be in flight
-                    if constexpr (!(IDN_X6_TIMING_DROP & 4)) asm volatile("s_waitcnt vmcnt(30)" : "+v"(r[2 * j]), "+v"(r[2 * j + 1])::"memory");
+                    asm volatile("s_waitcnt vmcnt(30)" : "+v"(r[2 * j]), "+v"(r[2 * j + 1])::"memory");
                     const unsigned p1 = tn_cvt_pk_bf16(r[2 * j], r[2 * j + 1]);
                     pw[X][0][j] = p1;
                     t0 = r[2 * j] - __uint_as_float(p1 << 16);
@@ -672,10 +595,8 @@ __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split
                     t1 = t1 - __uint_as_float(p2 & 0xffff0000u);
                     pw[X][2][j] = tn_cvt_pk_bf16(t0, t1);
                 } else {
-                    if constexpr (!(IDN_X6_TIMING_DROP & 4)) {
-                        load_row_at(r[2 * j], X ? rsrcB : rsrcA, (nbase + 2 * j) * (X ? rowB : rowA), X ? voffB : voff);
-                        load_row_at(r[2 * j + 1], X ? rsrcB : rsrcA, (nbase + 2 * j + 1) * (X ? rowB : rowA), X ? voffB : voff);
-                    }
+                    load_row_at(r[2 * j], X ? rsrcB : rsrcA, (nbase + 2 * j) * (X ? rowB : rowA), X ? voffB : voff);
+                    load_row_at(r[2 * j + 1], X ? rsrcB : rsrcA, (nbase + 2 * j + 1) * (X ? rowB : rowA), X ? voffB : voff);
                     if constexpr (j >= 3 && j < 6) store(ic_<j - 3>{}, ic_<0>{});
                     if constexpr (j == 7) store(ic_<0>{}, ic_<1>{});
                 }
@@ -692,43 +613,24 @@ __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split
             constexpr int qa = t == 2 || t == 3 ? 1 : (t == 5 ? 2 : 0);   // a1 b1, a1 b2, a2 b1, a2 b2, a1 b3, a3 b1
             constexpr int qb = t == 1 || t == 3 ? 1 : (t == 4 ? 2 : 0);
             acc[x][y] = mfma_bf16(fa[x][qa].v, fb[y][qb].v, acc[x][y]);
-            constexpr int kX1 = IDN_X6_EARLY_BARRIER ? 26 : 36;     // where the activation matrix's slices start (each matrix has 26)
+            constexpr int kX1 = 26;     // where the activation matrix's slices start (each matrix has 26)
             if constexpr (k < kX1) slice(ic_<0>{}, ic_<k>{});
             else slice(ic_<1>{}, ic_<k - kX1>{});
-            if constexpr (IDN_X6_EARLY_BARRIER && k == 59) {
+            if constexpr (k == 59) {
                 // everyone's pieces of chunk rc + 1 are in LDS; everyone has read chunk rc's (all 24 fragment reads were retired
                 // before row 1): the chunk barrier, twelve MFMAs early, and behind it the first row of the next chunk
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                X6_STAMP(dx_c);
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                X6_STAMP(dx_d);
-#ifdef IDN_DIAG_X6
-                dx_row0 += dx_b - dx_a;
-                dx_rows += dx_c - dx_b;
-                dx_bar += dx_d - dx_c;
-#endif
                 issue_first_row(a_base + (buf ^ 1) * kX6BufBytes, b_base + (buf ^ 1) * kX6BufBytes);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
-        if (!IDN_X6_EARLY_BARRIER) {
-            // everyone's pieces of chunk rc + 1 are in LDS; everyone has read chunk rc's
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-#ifdef IDN_DIAG_X6
-        X6_STAMP(dx_a);            // (the first-row reads of the next chunk, issued twelve MFMAs ago, are waited for here)
-        dx_tail += dx_a - dx_d;
-        dx_loop1 = dx_a;
-#endif
     }
-    if (IDN_X6_EARLY_BARRIER) {   // the first-row reads issued behind the last chunk's barrier (of a chunk that does not exist): retired, never used
-        x6_retire<0>(fa[0]);
-        x6_retire<0>(fb[0]);
-        x6_retire<0>(fb[1]);
-    }
+    // the first-row reads issued behind the last chunk's barrier (of a chunk that does not exist): retired, never used
+    x6_retire<0>(fa[0]);
+    x6_retire<0>(fb[0]);
+    x6_retire<0>(fb[1]);
     // the clamped re-reads of the last chunk are still in flight into ra / rb: retired here, so that the next item of a batch
     // starts on registers nothing is about to write (the stores below then drain under that item's first loads)
 #pragma unroll
@@ -743,21 +645,6 @@ __device__ __forceinline__ void gemm_tn_x6_item(const TNArgs& g, const int split
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 out[(long)(32 * (4 * wr + x) + d_row(r, hh)) * g.K + 32 * (4 * wc + y) + i] = acc[x][y][r];
-#ifdef IDN_DIAG_X6
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned long long dx_t1;
-    X6_STAMP(dx_t1);
-    if (tid == 0) {
-        atomicAdd(&g_x6_diag[0], dx_row0);
-        atomicAdd(&g_x6_diag[1], dx_rows);
-        atomicAdd(&g_x6_diag[2], dx_bar);
-        atomicAdd(&g_x6_diag[3], dx_tail);
-        atomicAdd(&g_x6_diag[4], (dx_t1 - dx_t0) - (dx_loop1 - dx_loop0));
-        atomicAdd(&g_x6_diag[5], (unsigned long long)n_chunks);
-        atomicAdd(&g_x6_diag[6], 1ull);
-        atomicAdd(&g_x6_diag[7], dx_t1 - dx_t0);
-    }
-#endif
 }
 // The 256 x 256 weight-gradient products of a pass as ONE launch, ONE PRODUCT PER WORKGROUP: workgroup z works on item
 // z / splits over split z % splits of the points, with splits = 2 #CUs / #items (56 for the nine products of a pass on 256 CUs).
@@ -1011,21 +898,6 @@ constexpr int kX6ItemsPerPass = 9;   // pts_linears.1..7, views_linears.0 + alph
 // partial-slab floats of one split over all GEMMs of a pass: 9 of 256x256 (pts_linears.1..7, views_linears.0 + alpha_linear, the
 // views_linears.1 / .2 pair), 2 of 256x64, 1 of 128x64, 1 of 64x128 -- with room for the fp32 pipe's two 128x128
 constexpr size_t kPartFloatsPerSplit = 9 * 65536 + 6 * 16384 + 4 * 8192;   // (the fp32 pipe: 8 + 2 x 16384 for the views pair; the narrow shapes may run 2 x kMaxSplits splits)
-// The narrow shapes (256 x 64, 128 x 64, 64 x 128 outputs: pts_linears.0, the encoding columns of pts_linears.5, the direction
-// columns of views_linears.0, rgb_linear) are HBM-shaped: ring depth and workgroups per CU decide how many bytes they keep in flight
-#ifndef IDN_TN_NARROW_BUFS
-#define IDN_TN_NARROW_BUFS 3
-#endif
-// points per chunk of the narrow shapes: 256 x 64 (40 KiB per 32-point chunk) and 128 x 64 / 64 x 128 (48 KiB per 64-point chunk)
-#ifndef IDN_TN_ROWS_4x1
-#define IDN_TN_ROWS_4x1 32
-#endif
-#ifndef IDN_TN_ROWS_THIN
-#define IDN_TN_ROWS_THIN 64
-#endif
-#ifndef IDN_TN_NARROW_SPLITS
-#define IDN_TN_NARROW_SPLITS 256
-#endif
 
 struct BwdWs {
     float *dA[8], *dV[2], *dV0, *dRGB, *part, *cpart, *wbwd;
@@ -1048,7 +920,7 @@ static BwdWs carve_bwd(char* base, int64_t p_pad) {
     w.dRGB = take((size_t)p_pad * 64);
     w.part = take((size_t)kMaxSplits * kPartFloatsPerSplit);   // one slab per GEMM of the pass: they are all reduced at its end
     w.cpart = take((size_t)kColsumBlocks * 256 * kGemmsPerPass);
-    w.wbwd = take(IDN_DELTA_X6 ? bwd_stream_floats_x6() : (size_t)kBwdStreamFrags * kFragFloats);   // transposed weight stream of the delta chain
+    w.wbwd = take(bwd_stream_floats_x6());   // transposed weight stream of the delta chain (either pipe's: mlp_f32_bwd.hip)
     w.bytes = off;
     return w;
 }
@@ -1061,8 +933,7 @@ size_t bwd_workspace_bytes(int64_t n_points) {
 // part[split][N][K] = A[:, :N]^T . B[:, :K] over point splits; returns the split count
 enum { kPipeX6 = 0, kPipeF32 = 1 };   // which matrix pipe a 256 x 256 GEMM runs on (the other shapes: fp32)
 // The backward's pipe for the delta chain and the 256 x 256 GEMMs: the six-piece bf16 arithmetic unless the process was
-// started with IDN_BACKWARD_PIPE=f32 (read once; the A/B arm and the fallback, exercised by the GPU tests) or the
-// library was built with -DIDN_DELTA_X6=0 / -DIDN_DW_X6=0.
+// started with IDN_BACKWARD_PIPE=f32 (read once; the A/B arm and the fallback, exercised by the GPU tests).
 static int env_pipe_f32() {
     static const int v = [] {
         const char* e = getenv("IDN_BACKWARD_PIPE");
@@ -1070,7 +941,7 @@ static int env_pipe_f32() {
     }();
     return v;
 }
-static int default_gemm_pipe() { return (IDN_DW_X6 && !env_pipe_f32()) ? kPipeX6 : kPipeF32; }
+static int default_gemm_pipe() { return env_pipe_f32() ? kPipeF32 : kPipeX6; }
 // The 256 x 256 bf16-piece products of a pass, collected and launched as one kernel (gemm_tn_x6_kernel walks them)
 struct X6Pending {
     TNBatch b;
@@ -1138,10 +1009,10 @@ static int run_tn_partials(X6Pending& x6, const float* A, int lda, int N, const 
     else return fail(IDN_EUNSUPPORTED, "gemm_tn: no instantiation for %d x %d", N, K);
     const int bx = N / (64 * ntw), by = K / (64 * ktw);
     const bool narrow = ntw * ktw <= 4 && !(ntw == 2 && ktw == 2);     // <4,1>, <2,1>, <1,2>
-    const int rows_per_chunk = !narrow ? kTnRows : (ntw == 4 ? IDN_TN_ROWS_4x1 : IDN_TN_ROWS_THIN);
+    const int rows_per_chunk = !narrow ? kTnRows : (ntw == 4 ? kTnRows4x1 : kTnRowsThin);
     if (P % rows_per_chunk) return fail(IDN_EINVAL, "gemm_tn: %lld rows are not a multiple of the %d-row chunk", (long long)P, rows_per_chunk);
     const long chunks = P / rows_per_chunk;
-    int splits = (narrow ? IDN_TN_NARROW_SPLITS : kMaxSplits) / (bx * by);
+    int splits = (narrow ? kTnNarrowSplits : kMaxSplits) / (bx * by);
     if (ntw == 4 && ktw == 4 && pipe == kPipeX6) {   // one product per workgroup: the CUs are divided among the pass's products
         int cus = 0;
         if (int e = device_cus(&cus)) return e;
@@ -1173,11 +1044,11 @@ static int run_tn_partials(X6Pending& x6, const float* A, int lda, int N, const 
     ProfScope prof(s, P, IDN_PROF_DW_GEMM);
     int e;
     if (ntw == 4 && ktw == 4) e = launch_tn<4, 4, kTnBufs>(g, grid, s);
-    else if (ntw == 4 && ktw == 1) e = launch_tn<4, 1, IDN_TN_NARROW_BUFS, IDN_TN_ROWS_4x1>(g, grid, s);
+    else if (ntw == 4 && ktw == 1) e = launch_tn<4, 1, kTnNarrowBufs, kTnRows4x1>(g, grid, s);
     else if (ntw == 2 && ktw == 4) e = launch_tn<2, 4, kTnBufs>(g, grid, s);
-    else if (ntw == 2 && ktw == 1) e = launch_tn<2, 1, IDN_TN_NARROW_BUFS, IDN_TN_ROWS_THIN>(g, grid, s);
+    else if (ntw == 2 && ktw == 1) e = launch_tn<2, 1, kTnNarrowBufs, kTnRowsThin>(g, grid, s);
     else if (ntw == 2 && ktw == 2) e = launch_tn<2, 2, kTnBufs>(g, grid, s);
-    else e = launch_tn<1, 2, IDN_TN_NARROW_BUFS, IDN_TN_ROWS_THIN>(g, grid, s);
+    else e = launch_tn<1, 2, kTnNarrowBufs, kTnRowsThin>(g, grid, s);
     if (e) return e;
     *splits_out = splits;
     return IDN_OK;
@@ -1290,7 +1161,7 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, 
 #define TRY(x) do { if (int e_ = (x)) return e_; } while (0)
     // All pre-activation deltas in one fused pass over the points (mlp_f32_bwd.hip): dV[0] = delta of
     // views_linears.2, dV[1] = views_linears.1, dV0[:, :128] = views_linears.0 (col 128 = d sigma), dA[l] = pts_linears.l
-    if (IDN_DELTA_X6 && !env_pipe_f32()) {
+    if (!env_pipe_f32()) {
         TRY(launch_pack_bf16x6_bwd(p, w.wbwd, s));
         TRY(launch_delta_chain_x6(w.wbwd, acts, Pp, w.dRGB, w.dV0, w.dV[0], w.dV[1], w.dA, s));
     } else {   // (the workspace's stream buffer is sized for the larger of the two streams)
@@ -1355,21 +1226,5 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, 
     return IDN_OK;
 }
 
-#ifdef IDN_DIAG_X6
-extern "C" int idealnerf_diag_x6_read(unsigned long long* out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_x6_diag), 8 * sizeof(unsigned long long)) != hipSuccess) return -3;
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_x6_diag), z, sizeof(z)) != hipSuccess) return -3;
-    return 0;
-}
-#endif
-#ifdef IDN_DIAG
-extern "C" int idealnerf_diag_tn_read(unsigned long long* out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tn_diag), 8 * sizeof(unsigned long long)) != hipSuccess) return -3;
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_tn_diag), z, sizeof(z)) != hipSuccess) return -3;
-    return 0;
-}
-#endif
 
 }  // namespace idn

@@ -1,10 +1,9 @@
 #!/bin/bash
 # End-of-round measurements on ONE GPU box (one gpurun call; ~12 min): the GPU test log (also with the fp32 kernel as the module
-# default, and with the fused ray kernel as the default arrangement), the PMC / kernel-trace summaries of the fp32 and bf16x6 inference kernels and of the train step, the same-box
-# stream-wrap A/B of the shipped bf16x6 kernel, and the bench lines -- all into gpurun_out/final_<part>/, from where they are
+# default, and with the fused ray kernel as the default arrangement), the PMC / kernel-trace summaries of the fp32 and bf16x6 inference kernels and of the train step,
+# and the bench lines -- all into the directory $F set below, from where they are
 # copied to profiles/r<NN>_* by hand.
 #   ROUND=r04 IDN_COMMIT=$(git rev-parse --short HEAD) bash tools/final_round.sh        (the GPU box has no .git)
-#   (build the A/B arm first: python ideal-nerf_amd/build.py --variant wrap "-DIDN_TIMING_STREAM_WRAP=8" mlp_bf16x6.hip)
 #   Two gpurun calls (a call is limited to 20 minutes): `bash tools/final_round.sh tests` (the three suites, ~14 min) and
 #   `bash tools/final_round.sh profiles` (rocprofv3 summaries + bench lines, ~10 min; run it LAST: bench.py reports `traffic` only
 #   from PMC summaries taken on the sources that are running).
@@ -43,8 +42,6 @@ bash tools/profile_train.sh > $F/profile_train.log 2>&1
 cp gpurun_out/prof_train/kernel_stats.csv $F/kernel_stats_train_final.csv
 for j in gpurun_out/prof_train/pmc_*.json; do cp $j $F/pmc_train_$(basename $j | sed 's/^pmc_//'); done
 echo "profile train done"
-# does the (now L2-resident) 3.375 MiB stream still cost anything?  wrap = the stream wraps after 8 slices (384 KiB; wrong results)
-if [ -f ideal-nerf_amd/libidealnerf_wrap.so ]; then bash tools/ab_bench.sh wrap - bf16x6 > $F/ab_x6_stream_wrap.log 2>&1; cat $F/ab_x6_stream_wrap.log; fi
 # the PMC summaries must be in profiles/ for bench.py to report `traffic`: stage them where it looks
 mkdir -p profiles
 for P in f32 bf16x6; do cp $F/pmc_mlp_${P}_final.json profiles/${ROUND:-r04}_pmc_mlp_${P}_final.json; done
