@@ -7,11 +7,15 @@ compositing-backward + 11 layers of MFMA GEMMs + the conditioning fold.  Gradien
 every FaceNeRF parameter of both networks, ``aud_para`` (and through it the audio nets,
 which stay ordinary autograd modules) and ``latent_code``.  Sampled depths are detached
 exactly as upstream (:345); ``expr`` is data.
+
+``FaceNeRFFn`` is the same machinery for ``FaceNeRF.forward`` on pre-embedded rows (models/face_nerf.py:40-80): the
+activation-saving forward in the rows' mode, and a backward seeded by dL/d out that also returns d x and d expr.
 """
 import ctypes as C
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._lib import IDN_PREC_F32, check
@@ -21,17 +25,7 @@ PARAM_KEYS = ([f"pts_linears.{i}.{k}" for i in range(8) for k in ("weight", "bia
               [f"views_linears.{i}.{k}" for i in range(3) for k in ("weight", "bias")] +
               ["alpha_linear.weight", "alpha_linear.bias", "rgb_linear.weight", "rgb_linear.bias"])
 
-def _grads_struct(grads):
-    g = _lib.FaceNerfGrads()
-    for i in range(8):
-        g.pts_w[i] = grads[f"pts_linears.{i}.weight"].data_ptr()
-        g.pts_b[i] = grads[f"pts_linears.{i}.bias"].data_ptr()
-    for i in range(3):
-        g.views_w[i] = grads[f"views_linears.{i}.weight"].data_ptr()
-        g.views_b[i] = grads[f"views_linears.{i}.bias"].data_ptr()
-    g.alpha_w, g.alpha_b = grads["alpha_linear.weight"].data_ptr(), grads["alpha_linear.bias"].data_ptr()
-    g.rgb_w, g.rgb_b = grads["rgb_linear.weight"].data_ptr(), grads["rgb_linear.bias"].data_ptr()
-    return g
+_grads_struct = ops.grads_struct
 
 
 # Arithmetic of the training forward: "bf16x6" (six bf16 piece products per fp32 product, weights and activations as
@@ -177,7 +171,62 @@ def render_rays_apply(network, coarse, fine, rays, bc_rgb, aud_para, latent_code
     return ret
 
 
+def _train_code():
+    if TRAIN_PRECISION not in ("f32", "bf16x6"):
+        raise _lib.IdealNerfError(f"IDN_TRAIN_PRECISION must be f32 or bf16x6 (got {TRAIN_PRECISION!r})")
+    return TRAIN_PRECISION, (_lib.IDN_PREC_F32 if TRAIN_PRECISION == "f32" else _lib.IDN_PREC_BF16X6)
+
+
+class FaceNeRFFn(torch.autograd.Function):
+    """FaceNeRF.forward (models/face_nerf.py:40-80) with gradients: one activation-saving forward launch, one C call
+    backward (the render pass's delta chain and weight-gradient products, seeded by dL/d out).  Gradients reach the 24
+    parameters idn_facenerf_params names (feature_linear is never applied upstream and gets none), x, aud, expr and
+    latent_code -- each only if it requires grad.  The forward runs TRAIN_PRECISION (as render training does).
+
+    Memory: the saved activation slab holds 2648 floats per row (10.6 KB; rows rounded up to 128), kept until the
+    backward: 40 000 rows hold about 0.42 GB, 2^19 rows 5.6 GB.  Once differentiable (create_graph=True raises)."""
+
+    @staticmethod
+    def forward(ctx, module, x, aud, expr, latent, *params):
+        prec_name, code = _train_code()
+        f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+        aud_d, expr_d, lat_d = f32(aud), f32(expr), f32(latent)
+        folded = module.folded_bias(aud_d, expr_d, lat_d)
+        out, acts = ops.facenerf_train_fwd(module.packed_weights(prec_name), folded, f32(x), code)
+        ctx.module, ctx.acts, ctx.cond = module, acts, (aud_d, expr_d, lat_d)
+        ctx.like = [None if t is None else (t.dtype, t.shape) for t in (x, aud, expr, latent)]   # gradients come back alike
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        if torch.is_grad_enabled():
+            raise _lib.IdealNerfError("FaceNeRF.forward is once differentiable: create_graph=True (double backward) is not built")
+        return _facenerf_backward(ctx, g_out)
+
+
+@once_differentiable
+def _facenerf_backward(ctx, g_out):
+    module, acts = ctx.module, ctx.acts
+    aud, expr, lat = ctx.cond
+    need = ctx.needs_input_grad        # (module, x, aud, expr, latent, *params)
+    sd = dict(module.named_parameters())
+    dev = acts.device
+    n = g_out.shape[0]
+    zeros = lambda t, want: torch.zeros(t.shape, dtype=torch.float32, device=dev) if want and t is not None else None
+    d_aud, d_expr, d_lat = zeros(aud, need[2]), zeros(expr, need[3]), zeros(lat, need[4])
+    d_x = torch.empty((n, ops.PTS_CH + ops.VIEWS_CH), dtype=torch.float32, device=dev) if need[1] else None
+    grads = {k: (torch.empty_like if n else torch.zeros_like)(sd[k]) for k in PARAM_KEYS}
+    if n:
+        ops.facenerf_bwd(module.kernel_params(), grads, aud, expr, lat, acts, g_out.detach().to(torch.float32).contiguous(),
+                         d_x=d_x, d_aud=d_aud, d_expr=d_expr, d_latent=d_lat)
+    elif d_x is not None:
+        d_x.zero_()
+    ctx.acts = None
+    cast = lambda d, like: None if d is None else d.to(like[0]).view(like[1])
+    fixed = (None, *[cast(d, like) for d, like in zip((d_x, d_aud, d_expr, d_lat), ctx.like)])
+    return (*fixed, *[grads[k] if need[5 + i] else None for i, k in enumerate(PARAM_KEYS)])
+
+
 def facenerf_apply(module, x, aud, expr, latent_code):
-    raise NotImplementedError(
-        "FaceNeRF.forward with gradients on pre-embedded rows is not built: train through Network.render_rays "
-        "(the reference's training path, audio_exp_nerf.py:534), or call under torch.no_grad() for inference")
+    sd = dict(module.named_parameters())
+    return FaceNeRFFn.apply(module, x, aud, expr, latent_code, *[sd[k] for k in PARAM_KEYS])

@@ -290,6 +290,49 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
                            (hipStream_t)stream);
 }
 
+static int check_grads(const idn_facenerf_grads* grads) {
+    if (!grads) return fail(IDN_EINVAL, "grads is NULL");
+    for (int i = 0; i < 8; ++i)
+        if (!grads->pts_w[i] || !grads->pts_b[i]) return fail(IDN_EINVAL, "grad pts_linears.%d is NULL", i);
+    for (int i = 0; i < 3; ++i)
+        if (!grads->views_w[i] || !grads->views_b[i]) return fail(IDN_EINVAL, "grad views_linears.%d is NULL", i);
+    if (!grads->alpha_w || !grads->alpha_b || !grads->rgb_w || !grads->rgb_b) return fail(IDN_EINVAL, "grad head is NULL");
+    return IDN_OK;
+}
+
+int idealnerf_facenerf_train_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
+                                 float* out, float* acts, void* stream) {
+    if (int e = check_precision_train(precision)) return e;
+    if (n < 0) return fail(IDN_EINVAL, "n < 0");
+    if (n == 0) return IDN_OK;
+    if (!packed || !folded || !x || !out || !acts) return fail(IDN_EINVAL, "NULL pointer");
+    if (n > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "n %lld exceeds 2^31-1 per launch", (long long)n);
+    const int64_t p_pad = (n + 127) / 128 * 128;
+    if (precision == IDN_PREC_BF16X6)
+        return launch_mlp_bf16x6(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad);
+    return launch_mlp_f32(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad);
+}
+
+size_t idealnerf_facenerf_bwd_workspace_bytes(int64_t n) {
+    if (n <= 0) return 0;
+    return bwd_workspace_bytes(n);
+}
+
+int idealnerf_facenerf_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud, const float* expr,
+                           const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
+                           float* d_expr, float* d_latent, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_grads(grads)) return e;
+    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
+        (p->dim_latent > 0) != (latent != nullptr))
+        return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
+    if (n < 0) return fail(IDN_EINVAL, "n < 0");
+    if (n == 0) return IDN_OK;
+    if (!acts || !g_out) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_facenerf_bwd(*p, *grads, aud, expr, latent, acts, n, g_out, d_x, d_aud, d_expr, d_latent, workspace,
+                               workspace_bytes, (hipStream_t)stream);
+}
+
 size_t idealnerf_dw_gemm_workspace_bytes(void) { return dw_gemm_workspace_bytes(); }
 
 int idealnerf_dw_gemm(const float* delta, int ld_delta, const float* acts, int ld_acts, int64_t rows, float* dW, float* db,

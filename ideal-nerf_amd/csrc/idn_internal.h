@@ -289,5 +289,10 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, 
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
                     const float* g_acc, float* d_aud, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s);
+// FaceNeRF.forward's backward on pre-embedded rows: head deltas from g_out [n, 4], the same tail as launch_pass_bwd, d expr
+// from the fold and (d_x != null) the input-row gradient d_x [n, 90]
+int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
+                        const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
+                        float* d_expr, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace idn

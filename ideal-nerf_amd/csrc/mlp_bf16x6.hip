@@ -327,7 +327,7 @@ int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, 
                       const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
                       float* acts, int64_t p_pad) {
     if (n_points <= 0) return IDN_OK;
-    if (acts && (x || pts)) return fail(IDN_EUNSUPPORTED, "the activation-saving forward takes rays");
+    if (acts && pts) return fail(IDN_EUNSUPPORTED, "the activation-saving forward takes rays or pre-embedded rows");
     static LaunchSetup setup;
     int num_cu = 0;
     constexpr int kLdsInfer = x6::mlp_lds6<x6::WStream6x3>(), kLdsTrain = kLdsInfer;
@@ -339,6 +339,8 @@ int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, 
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTrain));
             IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModeX, false>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsInfer));
+            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModeX, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTrain));
             IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModePts, false>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsInfer));
             return IDN_OK;
@@ -348,7 +350,9 @@ int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, 
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
     MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad};
     ProfScope prof(s, n_points, acts ? IDN_PROF_MLP_FWD_SAVE_X6 : IDN_PROF_MLP_FWD);
-    if (x)
+    if (x && acts)   // FaceNeRF.forward with gradients: the same instruction sequence as the line below plus the slab stores
+        hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModeX, true>), dim3(grid), dim3(256), kLdsTrain, s, a);
+    else if (x)
         hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModeX, false>), dim3(grid), dim3(256), kLdsInfer, s, a);
     else if (pts)
         hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModePts, false>), dim3(grid), dim3(256), kLdsInfer, s, a);

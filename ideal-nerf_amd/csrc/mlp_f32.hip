@@ -361,6 +361,8 @@ int launch_mlp_f32(const float* packed, const float* folded, const float* x, con
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
             IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeRays, true>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsTrain));
+            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeX, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsTrain));
             return IDN_OK;
         }, &num_cu))
         return e;
@@ -369,8 +371,11 @@ int launch_mlp_f32(const float* packed, const float* folded, const float* x, con
     MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad};
     ProfScope prof(s, n_points, acts ? IDN_PROF_MLP_FWD_SAVE : IDN_PROF_MLP_FWD);
     if (acts) {
-        if (x || pts) return fail(IDN_EUNSUPPORTED, "activation saving is only built for the rays+z input mode");
-        hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, true>), dim3(grid), dim3(256), kMlpLdsTrain, s, a);
+        if (pts) return fail(IDN_EUNSUPPORTED, "activation saving is built for the rays+z and the pre-embedded-row input modes");
+        if (x)   // FaceNeRF.forward with gradients: the slab's x0 / dir matrices hold the rows' own encodings
+            hipLaunchKernelGGL((mlp_f32_kernel<kModeX, true>), dim3(grid), dim3(256), kMlpLdsTrain, s, a);
+        else
+            hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, true>), dim3(grid), dim3(256), kMlpLdsTrain, s, a);
     } else if (x)
         hipLaunchKernelGGL((mlp_f32_kernel<kModeX, false>), dim3(grid), dim3(256), kMlpLds, s, a);
     else if (pts)

@@ -838,6 +838,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
 // conditioning fold backward
 //   dW0[:, 63+c] = db0'[n] cond[c];  dW5[:, 63+c] = db5'[n] cond[c];  dWv0[:, 283+e] = dbv'[n] expr3[e]
 //   d cond[c] = sum_n W0[n][63+c] db0'[n] + W5[n][63+c] db5'[n]   -> d aud, d latent (accumulated)
+//   d expr[e] = (d cond[dim_aud+e] + sum_n Wv0[n][283+e] dbv'[n]) / 3   (expr * 1 / 3 enters all three layers, face_nerf.py:49)
 // ---------------------------------------------------------------------------
 struct FoldBwdArgs {
     idn_facenerf_params p;
@@ -845,6 +846,7 @@ struct FoldBwdArgs {
     const float* db0; const float* db5; const float* dbv;  // [256], [256], [128]
     float* gW0; float* gW5; float* gWv0;                    // gradient tensors (full nn.Linear layout)
     float* d_aud; float* d_latent;                          // accumulated (+=), may be null
+    float* d_expr;                                          // accumulated (+=), may be null (idealnerf_pass_bwd: expr is data)
 };
 __device__ __forceinline__ float cond_val(const FoldBwdArgs& d, int c) {
     if (c < d.p.dim_aud) return d.aud[c];
@@ -878,11 +880,23 @@ __global__ void fold_bwd_kernel(FoldBwdArgs d) {
                  (double)d.p.pts_w[5][(long)n * ld5 + IDN_PTS_CH + c] * (double)d.db5[n];
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) s += shfl_xor_dd(s, m);
+        // an expr column also feeds views_linears.0 (wave-uniform branch; never taken when d_expr is NULL)
+        const int e = c - d.p.dim_aud;
+        const bool want_expr = d.d_expr != nullptr && e >= 0 && e < d.p.dim_expr;
+        double sv = 0.0;
+        if (want_expr) {
+            for (int n = lane; n < IDN_W / 2; n += 64)
+                sv += (double)d.p.views_w[0][(long)n * ldv + IDN_W + IDN_VIEWS_CH + e] * (double)d.dbv[n];
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sv += shfl_xor_dd(sv, m);
+        }
         if (lane != 0) return;
         if (c < d.p.dim_aud) {
             if (d.d_aud) d.d_aud[c] += (float)s;
         } else if (c >= d.p.dim_aud + d.p.dim_expr) {
             if (d.d_latent) d.d_latent[c - d.p.dim_aud - d.p.dim_expr] += (float)s;
+        } else if (want_expr) {
+            d.d_expr[e] += (float)((s + sv) / 3.0);
         }
     }
 }
@@ -1123,41 +1137,17 @@ int launch_dw_gemm(const float* delta, int ld_delta, const float* acts, int ld_a
     return q.flush(s);
 }
 
-int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
-                    const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
-                    const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
-                    const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s) {
-    const int64_t P = n_rays * S;
-    const int64_t Pp = (P + 127) / 128 * 128;
-    if (S < 2 || S > 256) return fail(IDN_EUNSUPPORTED, "pass_bwd: n_samples %d outside [2, 256]", S);
-    const BwdWs w = carve_bwd(reinterpret_cast<char*>(ws_), Pp);
-    if (!ws_ || ws_bytes < w.bytes) return fail(IDN_EWORKSPACE, "backward workspace %zu < %zu", ws_bytes, w.bytes);
+// The part of a backward that follows the head deltas (dRGB columns 0..2, dV0 column kSigmaChannel, zeros in the padding
+// rows): the transposed weight stream, the delta chain, the weight / bias gradient products and the conditioning fold.
+// launch_pass_bwd seeds the head deltas with the compositing backward, launch_facenerf_bwd with the caller's d raw.
+static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
+                    const float* latent, const float* acts, int64_t Pp, const BwdWs& w, float* d_aud, float* d_expr,
+                    float* d_latent, hipStream_t s) {
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
     const int ld0 = IDN_PTS_CH + C, ld5 = IDN_PTS_CH + C + IDN_W, ldv = IDN_W + IDN_VIEWS_CH + p.dim_expr;
     auto act = [&](int i) { return acts + (size_t)act_off(i) * Pp; };
     auto a_l = [&](int l) { return act(kActA1 + l - 1); };  // post-ReLU output of pts_linears.(l-1), l = 1..8
     auto v_l = [&](int l) { return act(kActV1 + l - 1); };  // post-ReLU output of views_linears.(l-1), l = 1..3
-
-    // d(outputs) -> d raw, written straight into the head deltas (zero elsewhere)
-    IDN_HIP_CHECK(hipMemsetAsync(w.dRGB, 0, (size_t)Pp * 64 * 4, s));
-    // dV0: columns 0..127 are written by the delta chain for every row, column 128 (d sigma) by the compositing
-    // backward for every real point; only the padding rows of that column need zeros.  Columns 129..255 are never written
-    // here, but the views_linears.0 + alpha_linear product below READS all 256 columns: what it finds there is whatever an
-    // earlier pass left in this workspace (the host layer hands over a workspace that was zeroed when it was allocated), and
-    // it reaches only output rows / column sums 129..255, which `q.add` never takes
-    if (Pp > P) IDN_HIP_CHECK(hipMemsetAsync(w.dV0 + (size_t)P * 256, 0, (size_t)(Pp - P) * 256 * 4, s));
-    {
-        CompBwdArgs a{reinterpret_cast<const float4*>(raw), z, rays, bc, g_rgb, g_fg, g_lw, g_acc,
-                      w.dRGB, 64, w.dV0 + kSigmaChannel, 256, (long)n_rays, S};
-        const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-        switch ((S + 63) / 64) {
-            case 1: hipLaunchKernelGGL(composite_bwd_kernel<1>, grid, block, 0, s, a); break;
-            case 2: hipLaunchKernelGGL(composite_bwd_kernel<2>, grid, block, 0, s, a); break;
-            case 3: hipLaunchKernelGGL(composite_bwd_kernel<3>, grid, block, 0, s, a); break;
-            default: hipLaunchKernelGGL(composite_bwd_kernel<4>, grid, block, 0, s, a); break;
-        }
-        IDN_HIP_CHECK(hipGetLastError());
-    }
 #define TRY(x) do { if (int e_ = (x)) return e_; } while (0)
     // All pre-activation deltas in one fused pass over the points (mlp_f32_bwd.hip): dV[0] = delta of
     // views_linears.2, dV[1] = views_linears.1, dV0[:, :128] = views_linears.0 (col 128 = d sigma), dA[l] = pts_linears.l
@@ -1216,12 +1206,190 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, 
 #undef TRY
     {
         FoldBwdArgs f{p, aud, expr, latent, gr.pts_b[0], gr.pts_b[5], gr.views_b[0], gr.pts_w[0], gr.pts_w[5],
-                      gr.views_w[0], d_aud, d_latent};
+                      gr.views_w[0], d_aud, d_latent, d_expr};
         const int total = IDN_W * C + (IDN_W / 2) * p.dim_expr + C * 64;   // one wavefront per conditioning column at the end
         if (total > 0) {
             hipLaunchKernelGGL(fold_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, s, f);
             IDN_HIP_CHECK(hipGetLastError());
         }
+    }
+    return IDN_OK;
+}
+
+int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
+                    const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
+                    const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
+                    const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s) {
+    const int64_t P = n_rays * S;
+    const int64_t Pp = (P + 127) / 128 * 128;
+    if (S < 2 || S > 256) return fail(IDN_EUNSUPPORTED, "pass_bwd: n_samples %d outside [2, 256]", S);
+    const BwdWs w = carve_bwd(reinterpret_cast<char*>(ws_), Pp);
+    if (!ws_ || ws_bytes < w.bytes) return fail(IDN_EWORKSPACE, "backward workspace %zu < %zu", ws_bytes, w.bytes);
+
+    // d(outputs) -> d raw, written straight into the head deltas (zero elsewhere)
+    IDN_HIP_CHECK(hipMemsetAsync(w.dRGB, 0, (size_t)Pp * 64 * 4, s));
+    // dV0: columns 0..127 are written by the delta chain for every row, column 128 (d sigma) by the compositing
+    // backward for every real point; only the padding rows of that column need zeros.  Columns 129..255 are never written
+    // here, but the views_linears.0 + alpha_linear product below READS all 256 columns: what it finds there is whatever an
+    // earlier pass left in this workspace (the host layer hands over a workspace that was zeroed when it was allocated), and
+    // it reaches only output rows / column sums 129..255, which `q.add` never takes
+    if (Pp > P) IDN_HIP_CHECK(hipMemsetAsync(w.dV0 + (size_t)P * 256, 0, (size_t)(Pp - P) * 256 * 4, s));
+    {
+        CompBwdArgs a{reinterpret_cast<const float4*>(raw), z, rays, bc, g_rgb, g_fg, g_lw, g_acc,
+                      w.dRGB, 64, w.dV0 + kSigmaChannel, 256, (long)n_rays, S};
+        const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
+        switch ((S + 63) / 64) {
+            case 1: hipLaunchKernelGGL(composite_bwd_kernel<1>, grid, block, 0, s, a); break;
+            case 2: hipLaunchKernelGGL(composite_bwd_kernel<2>, grid, block, 0, s, a); break;
+            case 3: hipLaunchKernelGGL(composite_bwd_kernel<3>, grid, block, 0, s, a); break;
+            default: hipLaunchKernelGGL(composite_bwd_kernel<4>, grid, block, 0, s, a); break;
+        }
+        IDN_HIP_CHECK(hipGetLastError());
+    }
+    return bwd_tail(p, gr, aud, expr, latent, acts, Pp, w, d_aud, nullptr, d_latent, s);
+}
+
+// ---------------------------------------------------------------------------
+// FaceNeRF.forward's backward on pre-embedded rows (models/face_nerf.py:40-80): the head deltas come from the caller's
+// d raw = g_out [n, 4] (rgb_raw, sigma_raw) instead of the compositing backward.  alpha_linear and rgb_linear are linear
+// outputs, so d raw IS the head delta: one kernel writes dRGB (ld 64: columns 0..2, zeros beyond) and dV0 column
+// kSigmaChannel for every row of the p_pad rows, zeros in the padding rows (they then carry zero deltas through the chain).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void head_seed_kernel(const float* g_out, long n, long p_pad, float* d_rgb, float* dv0) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // (row, float4 of the 64-column dRGB row)
+    const long p = idx >> 4;
+    const int q = (int)(idx & 15);
+    if (p >= p_pad) return;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (q == 0 && p < n) v = f32x4{g_out[p * 4 + 0], g_out[p * 4 + 1], g_out[p * 4 + 2], 0.f};
+    *reinterpret_cast<f32x4*>(d_rgb + p * 64 + 4 * q) = v;
+    if (q == 0) dv0[p * 256 + kSigmaChannel] = p < n ? g_out[p * 4 + 3] : 0.f;
+}
+
+// ---------------------------------------------------------------------------
+// Gradient with respect to the input rows x [n, 90] (rays never need it: their encoding is not a leaf):
+//   d_x[:, 0:63]  = dA0 . W0[:, 0:63] + dA5 . W5[:, 0:63]     (pts_linears.0 and the skip layer, K = 512)
+//   d_x[:, 63:90] = dV0[:, 0:128] . Wv0[:, 256:283]           (views_linears.0's direction columns, K = 128)
+// Row-major "NN" products, contraction over the layers' OUTPUT channels, on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32,
+// fp32 operands, fp32 accumulate).  One wave = 32 points: C[col][point] = W^T (A operand, from LDS) x delta^T (B operand,
+// straight from the delta rows: lane (point j, half hh) loads the float4 of channels 8 g + 4 hh .. + 3 of its row and feeds
+// them to four MFMAs; the A fragments hold the same four channels, so each delta row is read exactly once, as 16-byte loads).
+// The three weight blocks are re-laid into fragment order in LDS once per (persistent) workgroup:
+//   fragment 2 g + c (g < 64, c < 2): lane (i, hh) = W[k][32 c + i], k = 8 g + 4 hh + t, t = 0..3  (k < 256: W0 row k,
+//                                      else W5 row k - 256; column 63 = 0)
+//   fragment 128 + g (g < 16):         lane (i, hh) = Wv0[8 g + 4 hh + t][256 + i]  (i >= 27: 0)
+// 144 fragments of 1 KiB: one 16-wave workgroup per CU.  DESIGN.md section 3 ("input gradient").
+// ---------------------------------------------------------------------------
+constexpr int kDxFrags = 2 * 64 + 16;
+constexpr int kDxLds = kDxFrags * kFragBytes;
+constexpr int kDxWaves = 16;
+static_assert(kDxLds <= 160 * 1024, "the fragments must fit a CU's LDS");
+struct DxArgs {
+    const float* w0; int ld0;    // pts_linears.0.weight
+    const float* w5; int ld5;    // pts_linears.5.weight
+    const float* wv; int ldv;    // views_linears.0.weight
+    const float* dA0; const float* dA5; const float* dV0;   // [p_pad, 256] deltas
+    long n, p_pad;
+    float* d_x;                  // [n, 90]
+};
+__global__ __launch_bounds__(64 * kDxWaves, 1) void dx_kernel(DxArgs a) {
+    extern __shared__ __attribute__((aligned(16))) f32x4 dx_frag[];   // [kDxFrags][64 lanes]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, hh = lane >> 5;
+    for (int e = tid; e < kDxFrags * 64; e += 64 * kDxWaves) {
+        const int f = e >> 6, i = e & 31, h = (e >> 5) & 1;
+        float v[4];
+        for (int t = 0; t < 4; ++t) {
+            if (f < 128) {
+                const int g = f >> 1, col = 32 * (f & 1) + i, k = 8 * g + 4 * h + t;
+                const float* row = k < IDN_W ? a.w0 + (long)k * a.ld0 : a.w5 + (long)(k - IDN_W) * a.ld5;
+                v[t] = col < IDN_PTS_CH ? row[col] : 0.f;
+            } else {
+                const int k = 8 * (f - 128) + 4 * h + t;
+                v[t] = i < IDN_VIEWS_CH ? a.wv[(long)k * a.ldv + IDN_W + i] : 0.f;
+            }
+        }
+        dx_frag[e] = f32x4{v[0], v[1], v[2], v[3]};
+    }
+    __syncthreads();
+    const long ntiles = a.p_pad / 32;
+    for (long tile = (long)blockIdx.x * kDxWaves + wave; tile < ntiles; tile += (long)gridDim.x * kDxWaves) {
+        const long p = tile * 32 + j;
+        f32x16 acc0, acc1, accv;
+        for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = accv[r] = 0.f;
+        const float* r0 = a.dA0 + p * 256 + 4 * hh;
+        const float* r5 = a.dA5 + p * 256 + 4 * hh;
+        const float* rv = a.dV0 + p * 256 + 4 * hh;
+#pragma unroll 4
+        for (int g = 0; g < 32; ++g) {
+            const f32x4 d = *reinterpret_cast<const f32x4*>(r0 + 8 * g);
+            const f32x4 w0 = dx_frag[(2 * g) * 64 + lane], w1 = dx_frag[(2 * g + 1) * 64 + lane];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                acc0 = mfma32(w0[t], d[t], acc0);
+                acc1 = mfma32(w1[t], d[t], acc1);
+            }
+        }
+#pragma unroll 4
+        for (int g = 0; g < 32; ++g) {
+            const f32x4 d = *reinterpret_cast<const f32x4*>(r5 + 8 * g);
+            const f32x4 w0 = dx_frag[(64 + 2 * g) * 64 + lane], w1 = dx_frag[(64 + 2 * g + 1) * 64 + lane];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                acc0 = mfma32(w0[t], d[t], acc0);
+                acc1 = mfma32(w1[t], d[t], acc1);
+            }
+        }
+#pragma unroll 4
+        for (int g = 0; g < 16; ++g) {
+            const f32x4 d = *reinterpret_cast<const f32x4*>(rv + 8 * g);
+            const f32x4 w = dx_frag[(128 + g) * 64 + lane];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) accv = mfma32(w[t], d[t], accv);
+        }
+        // lane (j, hh), register r: column d_row(r, hh) of point p (+ 32 for the second pts tile, + 63 for the direction block)
+        if (p < a.n) {
+            float* o = a.d_x + p * (IDN_PTS_CH + IDN_VIEWS_CH);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int col = d_row(r, hh);
+                o[col] = acc0[r];
+                if (col < IDN_PTS_CH - 32) o[32 + col] = acc1[r];
+                if (col < IDN_VIEWS_CH) o[IDN_PTS_CH + col] = accv[r];
+            }
+        }
+    }
+}
+
+int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
+                        const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
+                        float* d_expr, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s) {
+    const int64_t Pp = (n + 127) / 128 * 128;
+    const BwdWs w = carve_bwd(reinterpret_cast<char*>(ws_), Pp);
+    if (!ws_ || ws_bytes < w.bytes) return fail(IDN_EWORKSPACE, "backward workspace %zu < %zu", ws_bytes, w.bytes);
+    {
+        const long threads = (long)Pp * 16;
+        hipLaunchKernelGGL(head_seed_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, g_out, (long)n, (long)Pp,
+                           w.dRGB, w.dV0);
+        IDN_HIP_CHECK(hipGetLastError());
+    }
+    if (int e = bwd_tail(p, gr, aud, expr, latent, acts, Pp, w, d_aud, d_expr, d_latent, s)) return e;
+    if (d_x) {
+        static LaunchSetup setup;
+        int num_cu = 0;
+        if (int e = setup.get([]() -> int {
+                IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDxLds));
+                return IDN_OK;
+            }, &num_cu))
+            return e;
+        const int C = p.dim_aud + p.dim_expr + p.dim_latent;
+        const DxArgs da{p.pts_w[0], IDN_PTS_CH + C, p.pts_w[5], IDN_PTS_CH + C + IDN_W, p.views_w[0], IDN_W + IDN_VIEWS_CH + p.dim_expr,
+                        w.dA[0], w.dA[5], w.dV0, (long)n, (long)Pp, d_x};
+        const int64_t groups = (Pp / 32 + kDxWaves - 1) / kDxWaves;
+        const int grid = (int)(groups < num_cu ? groups : num_cu);
+        hipLaunchKernelGGL(dx_kernel, dim3(grid), dim3(64 * kDxWaves), kDxLds, s, da);
+        IDN_HIP_CHECK(hipGetLastError());
     }
     return IDN_OK;
 }

@@ -148,7 +148,10 @@ class FaceNeRF(nn.Module):
 
     def forward(self, x, aud, expr=None, latent_code=None):
         self._check_cond(aud, expr, latent_code)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        # with gradients whenever anything of the call requires them: parameters, rows, or the per-frame conditioning alone
+        # (frozen weights and per-frame codes being optimised); FaceNeRFFn runs the training kernels (autograd.py)
+        cond_grad = any(t is not None and t.requires_grad for t in (aud, expr, latent_code))
+        if torch.is_grad_enabled() and (x.requires_grad or cond_grad or any(p.requires_grad for p in self.parameters())):
             from ..autograd import facenerf_apply
             return facenerf_apply(self, x, aud, expr, latent_code)
         with torch.no_grad():

@@ -148,6 +148,60 @@ def facenerf_fwd(packed, folded, x, precision=IDN_PREC_F32) -> torch.Tensor:
     return out
 
 
+def facenerf_train_fwd(packed, folded, x, precision=_lib.IDN_PREC_BF16X6):
+    """FaceNeRF.forward that also records the backward's activation slab (idealnerf_facenerf_train_fwd): x [n, 90] ->
+    (out [n, 4], acts [idealnerf_train_acts_floats(n)]).  precision: IDN_PREC_F32 or IDN_PREC_BF16X6 only."""
+    lib = _lib.load()
+    _shape(x, "x", None, PTS_CH + VIEWS_CH)
+    if precision not in (_lib.IDN_PREC_F32, _lib.IDN_PREC_BF16X6):
+        raise IdealNerfError(f"the training forward runs IDN_PREC_F32 or IDN_PREC_BF16X6 only (got {precision})")
+    _net_buffers(lib, packed, folded, precision)
+    n = x.shape[0]
+    with _Launch(packed, folded, x) as L:
+        out = torch.empty((n, 4), dtype=torch.float32, device=x.device)
+        acts = torch.empty(lib.idealnerf_train_acts_floats(n), dtype=torch.float32, device=x.device)
+        check(lib.idealnerf_facenerf_train_fwd(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(x, "x"), n,
+                                               out.data_ptr(), acts.data_ptr(), L.stream))
+    return out, acts
+
+
+def grads_struct(grads: Dict[str, torch.Tensor]):
+    """state_dict-keyed gradient tensors (the 24 of idn_facenerf_params) -> idn_facenerf_grads."""
+    g = _lib.FaceNerfGrads()
+    for i in range(8):
+        g.pts_w[i] = grads[f"pts_linears.{i}.weight"].data_ptr()
+        g.pts_b[i] = grads[f"pts_linears.{i}.bias"].data_ptr()
+    for i in range(3):
+        g.views_w[i] = grads[f"views_linears.{i}.weight"].data_ptr()
+        g.views_b[i] = grads[f"views_linears.{i}.bias"].data_ptr()
+    g.alpha_w, g.alpha_b = grads["alpha_linear.weight"].data_ptr(), grads["alpha_linear.bias"].data_ptr()
+    g.rgb_w, g.rgb_b = grads["rgb_linear.weight"].data_ptr(), grads["rgb_linear.bias"].data_ptr()
+    return g
+
+
+def facenerf_bwd(p, grads, aud, expr, latent, acts, g_out, d_x=None, d_aud=None, d_expr=None, d_latent=None):
+    """Backward of FaceNeRF.forward (idealnerf_facenerf_bwd) from the slab of facenerf_train_fwd.  p: params_struct of the
+    module; grads: state_dict-keyed tensors of the parameters' shapes, OVERWRITTEN; g_out [n, 4] = dL/d out; d_x [n, 90]
+    (overwritten) and d_aud / d_expr / d_latent (accumulated) may each be None."""
+    lib = _lib.load()
+    _shape(g_out, "g_out", None, 4)
+    n = g_out.shape[0]
+    _shape(acts, "acts", lib.idealnerf_train_acts_floats(n))
+    _shape(d_x, "d_x", n, PTS_CH + VIEWS_CH)
+    for t, name, dim in ((aud, "aud", p.dim_aud), (expr, "expr", p.dim_expr), (latent, "latent", p.dim_latent),
+                         (d_aud, "d_aud", p.dim_aud), (d_expr, "d_expr", p.dim_expr), (d_latent, "d_latent", p.dim_latent)):
+        _shape(t, name, dim)
+    for k, t in grads.items():
+        _ptr(t, f"grad {k}")
+    with _Launch(aud, expr, latent, acts, g_out, d_x, d_aud, d_expr, d_latent, *grads.values()) as L:
+        ptrs = [_ptr(t, name) for t, name in ((aud, "aud"), (expr, "expr"), (latent, "latent"), (acts, "acts"))]
+        ptrs += [n, _ptr(g_out, "g_out")]
+        ptrs += [_ptr(t, name) for t, name in ((d_x, "d_x"), (d_aud, "d_aud"), (d_expr, "d_expr"), (d_latent, "d_latent"))]
+        ws = _workspace(lib.idealnerf_facenerf_bwd_workspace_bytes(n), g_out.device, L.stream)
+        check(lib.idealnerf_facenerf_bwd(C.byref(p), C.byref(grads_struct(grads)), *ptrs, ws.data_ptr(), ws.numel(), L.stream))
+    return grads
+
+
 def query_rays_fwd(packed, folded, rays, z, precision=IDN_PREC_F32) -> torch.Tensor:
     lib = _lib.load()
     _shape(z, "z", None, None)

@@ -351,6 +351,36 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
                        float* d_latent, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * FaceNeRF.forward with gradients (models/face_nerf.py:40-80): the module trained on pre-embedded rows, outside
+ * render_rays -- weights, input rows and conditioning vectors.
+ *
+ * idealnerf_facenerf_train_fwd (models/face_nerf.py:40-80): idealnerf_facenerf_fwd that also records what the backward
+ *   needs.  precision: IDN_PREC_F32 or IDN_PREC_BF16X6 (`packed` is that precision's stream).  acts: idealnerf_train_acts_floats(n)
+ *   floats, the slab layout of idealnerf_query_rays_train_fwd; its x0 / dir matrices hold x[:, 0:63] / x[:, 63:90] (zero-padded
+ *   to 64 columns), and every padding row up to n rounded up to 128 is defined (it repeats the last row).
+ *   out[n, 4] equals idealnerf_facenerf_fwd's at the same precision bit for bit: each saving kernel runs the arithmetic of
+ *   its inference kernel (bias first, the same MFMA order, the same head dot products) plus the slab stores.
+ */
+int idealnerf_facenerf_train_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
+                                 float* out, float* acts, void* stream);
+
+/* Workspace of idealnerf_facenerf_bwd for n rows (the size idealnerf_pass_bwd needs for n points). */
+size_t idealnerf_facenerf_bwd_workspace_bytes(int64_t n);
+
+/*
+ * Backward of FaceNeRF.forward (models/face_nerf.py:40-80) for n rows, from the slab idealnerf_facenerf_train_fwd filled.
+ *   g_out [n, 4]: dL / d out, in the (rgb_raw, sigma_raw) order of idealnerf_facenerf_fwd.
+ *   grads: OVERWRITTEN, every entry including the conditioning columns (as idealnerf_pass_bwd); feature_linear has none.
+ *   d_x [n, 90]: OVERWRITTEN with dL / dx; NULL skips its kernel.
+ *   d_aud [dim_aud], d_expr [dim_expr], d_latent [dim_latent]: ACCUMULATED (+=); any may be NULL.  expr enters all three
+ *   layers as expr * 1 / 3 (face_nerf.py:49): d_expr = (db0 . W0[:, expr] + db5 . W5[:, expr] + dbv0 . Wv0[:, expr]) / 3.
+ * n == 0 writes nothing.  Argument errors return IDN_EINVAL before any launch; a short workspace IDN_EWORKSPACE.
+ */
+int idealnerf_facenerf_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud, const float* expr,
+                           const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
+                           float* d_expr, float* d_latent, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Test aid (no reference counterpart): one 256 x 256 weight-gradient product of the training step in isolation,
  *   dW[256][256] = delta[rows, :256]^T . acts[rows, :256],   db[256] = column sums of delta (may be NULL),
  * rows a positive multiple of 128, row pitches >= 256 floats.  pipe = IDN_DW_PIPE_BF16X6: as idealnerf_pass_bwd computes
