@@ -8,7 +8,8 @@ at the repository root makes it importable).  Layout mirrors the reference:
     idealnerf_amd.helper                           <- NeRFs/HeadNeRF/helper.py (render math)
     idealnerf_amd.audio_exp_nerf.Network           <- NeRFs/HeadNeRF/train/audio_exp_nerf.py
     idealnerf_amd.train_torso.Network              <- NeRFs/TorsoNeRF/train_torso.py (composite)
-    idealnerf_amd.parallel                         <- row-band tiling + RCCL all-gather
+    idealnerf_amd.parallel                         <- row-band tiling + RCCL all-gather; frame shares + ordered assembly
+    idealnerf_amd.clip                             <- the eval / test scripts' clip loops (eval_aud_exp_nerf.py, test_torso.py)
 """
 __version__ = "0.1.0"
 

@@ -76,6 +76,7 @@ PROTOTYPES = {
     "idealnerf_frame_rays": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                        C.c_float, C.c_float, C.c_int, C.c_int, fp, fp]),
     "idealnerf_to8b": (C.c_int, [fp, C.c_int64, C.c_int, fp, fp, fp]),
+    "idealnerf_compose_to8b": (C.c_int, [fp, fp, fp, C.c_int64, C.c_int, fp, fp, fp, fp]),
     "idealnerf_philox_uniform": (C.c_int, [C.c_uint64, C.c_int, C.c_int64, C.c_int64, C.c_int, fp, fp]),
     "idealnerf_coarse_depths": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, fp, fp]),
     "idealnerf_composite_fwd": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int64, C.c_int, C.POINTER(CompositeOut), fp]),

@@ -190,6 +190,15 @@ int idealnerf_to8b(const float* rgb, int64_t n_pixels, int swap_rb, uint8_t* out
     return launch_to8b(rgb, n_pixels, swap_rb, out, nonfinite_flag, (hipStream_t)stream);
 }
 
+int idealnerf_compose_to8b(const float* rgb_head, const float* last_weight, const float* rgb_fg, int64_t n_pixels,
+                           int swap_rb, uint8_t* out, uint8_t* fg_out, int* nonfinite_flag, void* stream) {
+    if (n_pixels < 0) return fail(IDN_EINVAL, "n_pixels < 0");
+    if (n_pixels == 0) return IDN_OK;
+    if (!rgb_head || !last_weight || !rgb_fg || !out) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_compose_to8b(rgb_head, last_weight, rgb_fg, n_pixels, swap_rb, out, fg_out, nonfinite_flag,
+                               (hipStream_t)stream);
+}
+
 int idealnerf_composite_fwd(const float* raw, const float* z, const float* rays, const float* bc_rgb,
                             const float* sigma_noise, int white_bkgd, int64_t n_rays, int n_samples,
                             const idn_composite_out* out, void* stream) {

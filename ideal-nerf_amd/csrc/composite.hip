@@ -149,6 +149,112 @@ int launch_to8b(const float* rgb, int64_t n_pixels, int swap_rb, unsigned char* 
     return IDN_OK;
 }
 
+// ---------------------------------------------------------------------------
+// clip tail of the head + torso flow (NeRFs/TorsoNeRF/test_torso.py:523-525):
+//   out = to8b(rgb_head * last_weight[:, None] + rgb_fg),   fg_out = to8b(rgb_fg) (optional)
+// One pass over 28 B/pixel instead of a multiply, an add and to8b with two full-frame temporaries.
+// The product and the sum are separate fp32 operations (this file is built with -ffp-contract=off),
+// so a finite composite gives the bytes of to8b on the eager expression.  A non-finite composite is
+// written as 0 and flagged; any NaN/Inf input makes the composite non-finite, so no input scan is needed.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ unsigned to8b_value(float x) {   // to8b_kernel's arithmetic for one value
+    float c = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
+    if (x != x) c = 0.0f;
+    return (unsigned)(int)(255.0f * c);
+}
+__device__ __forceinline__ unsigned compose_value(float head, float w, float fg, bool& bad) {
+    const float p = head * w;
+    const float x = p + fg;
+    const bool nf = !(fabsf(x) <= 3.402823466e+38f);
+    bad |= nf;
+    return nf ? 0u : to8b_value(x);
+}
+
+// VEC: thread t owns pixels 4t .. 4t+3 = floats 12t .. 12t+11 of each RGB stream (three float4), one float4 of weights
+// and bytes 12t .. 12t+11 of each output (three dwords; 12t is 4-byte aligned whenever the base is).  !VEC: one pixel
+// per thread, starting at pixel `first` (the n % 4 tail, or everything when a base pointer is not 16-byte aligned).
+template <bool VEC, bool FG>
+__global__ __launch_bounds__(256) void compose_to8b_kernel(const float* __restrict__ head, const float* __restrict__ lw,
+                                                           const float* __restrict__ fg, long first, long count, int swap_rb,
+                                                           unsigned char* __restrict__ out, unsigned char* __restrict__ fg_out,
+                                                           int* __restrict__ flag) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (t < count) {
+        if constexpr (VEC) {
+            const float4* h4 = reinterpret_cast<const float4*>(head) + 3 * t;
+            const float4* f4 = reinterpret_cast<const float4*>(fg) + 3 * t;
+            const float4 w4 = reinterpret_cast<const float4*>(lw)[t];
+            const float4 ha = h4[0], hb = h4[1], hc = h4[2];
+            const float4 fa = f4[0], fb = f4[1], fc = f4[2];
+            const float h[12] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w, hc.x, hc.y, hc.z, hc.w};
+            const float f[12] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w, fc.x, fc.y, fc.z, fc.w};
+            const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+            unsigned b[12], g[12];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    b[3 * p + c] = compose_value(h[3 * p + c], w[p], f[3 * p + c], bad);
+                    if constexpr (FG) g[3 * p + c] = to8b_value(f[3 * p + c]);
+                }
+                if (swap_rb) {   // selects on constant register indices, no indexed register array
+                    const unsigned r = b[3 * p];
+                    b[3 * p] = b[3 * p + 2];
+                    b[3 * p + 2] = r;
+                    if constexpr (FG) {
+                        const unsigned q = g[3 * p];
+                        g[3 * p] = g[3 * p + 2];
+                        g[3 * p + 2] = q;
+                    }
+                }
+            }
+            unsigned* o = reinterpret_cast<unsigned*>(out) + 3 * t;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) o[d] = b[4 * d] | (b[4 * d + 1] << 8) | (b[4 * d + 2] << 16) | (b[4 * d + 3] << 24);
+            if constexpr (FG) {
+                unsigned* og = reinterpret_cast<unsigned*>(fg_out) + 3 * t;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) og[d] = g[4 * d] | (g[4 * d + 1] << 8) | (g[4 * d + 2] << 16) | (g[4 * d + 3] << 24);
+            }
+        } else {
+            const long px = first + t;
+            const float w = lw[px];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const long dst = px * 3 + (swap_rb ? 2 - c : c);
+                out[dst] = (unsigned char)compose_value(head[px * 3 + c], w, fg[px * 3 + c], bad);
+                if constexpr (FG) fg_out[dst] = (unsigned char)to8b_value(fg[px * 3 + c]);
+            }
+        }
+    }
+    if (flag && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+int launch_compose_to8b(const float* head, const float* lw, const float* fg, int64_t n_pixels, int swap_rb,
+                        unsigned char* out, unsigned char* fg_out, int* flag, hipStream_t s) {
+    if (n_pixels <= 0) return IDN_OK;
+    const uintptr_t in_bits = (uintptr_t)head | (uintptr_t)lw | (uintptr_t)fg;
+    const uintptr_t out_bits = (uintptr_t)out | (uintptr_t)fg_out;   // fg_out == NULL adds no bits
+    const bool aligned = (in_bits & 15) == 0 && (out_bits & 3) == 0;
+    const long quads = aligned ? (long)(n_pixels / 4) : 0;
+    const long first = quads * 4, rest = (long)n_pixels - first;
+    const dim3 block(256);
+    if (quads > 0) {
+        const dim3 grid((unsigned)((quads + 255) / 256));
+        if (fg_out) hipLaunchKernelGGL((compose_to8b_kernel<true, true>), grid, block, 0, s, head, lw, fg, 0L, quads, swap_rb, out, fg_out, flag);
+        else hipLaunchKernelGGL((compose_to8b_kernel<true, false>), grid, block, 0, s, head, lw, fg, 0L, quads, swap_rb, out, fg_out, flag);
+        IDN_HIP_CHECK(hipGetLastError());
+    }
+    if (rest > 0) {
+        const dim3 grid((unsigned)((rest + 255) / 256));
+        if (fg_out) hipLaunchKernelGGL((compose_to8b_kernel<false, true>), grid, block, 0, s, head, lw, fg, first, rest, swap_rb, out, fg_out, flag);
+        else hipLaunchKernelGGL((compose_to8b_kernel<false, false>), grid, block, 0, s, head, lw, fg, first, rest, swap_rb, out, fg_out, flag);
+        IDN_HIP_CHECK(hipGetLastError());
+    }
+    return IDN_OK;
+}
+
 template <int SPL>
 __global__ __launch_bounds__(256) void composite_kernel(const float4* raw, const float* z, const float* rays,
                                                         const float* bc, long n_rays, int S, const float* noise,

@@ -218,6 +218,8 @@ int launch_audio_net_fwd(const idn_audio_net_params* p, const float* windows, in
 int launch_audio_net_bwd(const idn_audio_net_params* p, const idn_audio_net_grads* g, const float* windows, const float* saved,
                          const float* d_out, int n, hipStream_t s);
 int launch_to8b(const float* rgb, int64_t n_pixels, int swap_rb, unsigned char* out, int* flag, hipStream_t s);
+int launch_compose_to8b(const float* head, const float* lw, const float* fg, int64_t n_pixels, int swap_rb,
+                        unsigned char* out, unsigned char* fg_out, int* flag, hipStream_t s);
 // In-kernel draws (include/idealnerf.h: rng_mode): row `ray0 + r` of the Philox table replaces t_rand[r, :] / u[r, :]
 struct Draws {
     unsigned long long seed;

@@ -171,11 +171,12 @@ class FrameSink:
 
     def __init__(self, path: Optional[str], width: int, height: int, fps: float = 25.0, swap_rb: bool = False,
                  device="cuda", keep_frames: bool = False, codec: str = "MJPG", jpeg_quality: int = 95,
-                 still_every: int = 0, still_path: Optional[str] = None):
+                 still_every: int = 0, still_path: Optional[str] = None, still_ids=None):
         """codec "MJPG" (the reference's fourcc) or "raw" (lossless DIB).  ``still_every=10`` with
         ``still_path="dir/name_{i}.jpg"`` also writes the every-10th-frame JPEG of
-        eval_aud_exp_nerf.py:492-493.  Encoding and file writes run on a worker thread, so submit() only
-        waits for a frame's copy, never for its JPEG."""
+        eval_aud_exp_nerf.py:492-493 (``still_ids``: a sequence whose entry for the frame takes the place of its
+        index in the name, as NeRFs/TorsoNeRF/test_torso.py:526 names its stills by ``aud_ids[j]``).  Encoding and
+        file writes run on a worker thread, so submit() only waits for a frame's copy, never for its JPEG."""
         if torch.device(device).type != "cuda":
             raise IdealNerfError("FrameSink copies from the GPU; the HIP path has no CPU fallback")
         if codec not in ("MJPG", "raw"):
@@ -188,6 +189,7 @@ class FrameSink:
             self.writer = (MjpgAviWriter(path, width, height, fps, jpeg_quality) if codec == "MJPG"
                            else RawAviWriter(path, width, height, fps))
         self.jpeg_quality, self.still_every, self.still_path = int(jpeg_quality), int(still_every), still_path
+        self.still_ids = None if still_ids is None else list(still_ids)
         self.stills: List[str] = []
         self._queue: "queue.Queue" = queue.Queue(maxsize=4)
         self._error: Optional[BaseException] = None
@@ -199,48 +201,75 @@ class FrameSink:
         self.host = [torch.empty((self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.host_flag = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)]
         self.dev_flag = [torch.zeros(1, dtype=torch.int32, device=device) for _ in range(2)]
+        self.fg_host = None      # pinned pair for submit_composite's torso-only stills, made on first use
         self.done = [None, None]
         self.pending: List[int] = []
+        self._slot_of = {}       # frame index -> pinned slot, for the frames in `pending`
+        self._fg_pending = {}    # frame index -> True while the slot's fg_host holds that frame's torso-only still
+        self._dev_count = 0      # frames that went through the pinned pair (host frames of submit_u8 do not)
         self.count = 0
         self.nonfinite_frames: List[int] = []
         self.frames: Optional[List[np.ndarray]] = [] if keep_frames else None
 
-    def _retire(self, slot: int, index: int) -> None:
-        self.done[slot].synchronize()
-        if int(self.host_flag[slot][0]) != 0:
+    def is_still(self, index: int) -> bool:
+        return bool(self.still_every) and index % self.still_every == 0
+
+    def still_name(self, index: int, suffix: str = "") -> str:
+        """Path of frame `index`'s still; `suffix` goes in front of the extension ("_torso")."""
+        name = self.still_path.format(i=index if self.still_ids is None else self.still_ids[index])
+        if suffix:
+            stem, dot, ext = name.rpartition(".")
+            name = stem + suffix + dot + ext if dot else name + suffix
+        return name
+
+    def _enqueue(self, index: int, frame: np.ndarray, nonfinite: bool, fg: Optional[np.ndarray] = None) -> None:
+        if nonfinite:
             self.nonfinite_frames.append(index)
-        frame = self.host[slot].numpy().copy()   # the pinned buffer is reused two submits later
         if self.frames is not None:
             self.frames.append(frame)
         if self._worker is not None:
             if self._error is not None:
                 raise self._error
-            self._queue.put((index, frame))
+            self._queue.put((index, frame, fg))
+
+    def _retire(self, slot: int, index: int) -> None:
+        self.done[slot].synchronize()
+        fg = self.fg_host[slot].numpy().copy() if self._fg_pending.pop(index, False) else None
+        # the pinned buffer is reused two submits later: copy out of it
+        self._enqueue(index, self.host[slot].numpy().copy(), int(self.host_flag[slot][0]) != 0, fg)
+
+    def _retire_through(self, slot: Optional[int]) -> None:
+        """Retire pending frames in order, up to and including the one that holds `slot` (None: all of them)."""
+        while self.pending and (slot is None or slot in self._slot_of.values()):
+            index = self.pending.pop(0)
+            self._retire(self._slot_of.pop(index), index)
 
     def _drain(self) -> None:
         while True:
             item = self._queue.get()
             if item is None:
                 return
-            index, frame = item
+            index, frame, fg = item
             try:
                 if self._error is None:
-                    if self.still_every and index % self.still_every == 0:
-                        name = self.still_path.format(i=index)
-                        with open(name, "wb") as f:
-                            f.write(encode_jpeg(frame, self.jpeg_quality))
-                        self.stills.append(name)
+                    if self.is_still(index):
+                        for name, img in ((self.still_name(index), frame), (self.still_name(index, "_torso"), fg)):
+                            if img is None:
+                                continue
+                            with open(name, "wb") as f:
+                                f.write(encode_jpeg(img, self.jpeg_quality))
+                            self.stills.append(name)
                     if self.writer is not None:
                         self.writer.write(frame)
             except BaseException as e:  # surfaced by the next submit() / release()
                 self._error = e
 
-    def submit(self, rgb: torch.Tensor) -> None:
-        slot = self.count & 1
-        if self.count >= 2:
-            self._retire(slot, self.pending.pop(0))  # the frame that used this slot two submits ago
-        self.dev_flag[slot].zero_()
-        u8 = ops.to8b(rgb.reshape(self.h, self.w, 3), self.swap_rb, self.dev_flag[slot])
+    def _submit_device(self, convert) -> None:
+        """convert(slot) -> (u8 [H, W, 3] on the device, fg u8 or None), enqueued on the current stream; then the copies
+        on the side stream."""
+        slot = self._dev_count & 1
+        self._retire_through(slot)   # the frame that used this slot two device submits ago
+        u8, fg = convert(slot)
         ready = torch.cuda.Event()
         ready.record()
         with torch.cuda.stream(self.copy_stream):
@@ -248,15 +277,62 @@ class FrameSink:
             self.host[slot].copy_(u8, non_blocking=True)
             self.host_flag[slot].copy_(self.dev_flag[slot], non_blocking=True)
             u8.record_stream(self.copy_stream)
+            if fg is not None:
+                if self.fg_host is None:
+                    self.fg_host = [torch.empty((self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
+                self.fg_host[slot].copy_(fg, non_blocking=True)
+                fg.record_stream(self.copy_stream)
+                self._fg_pending[self.count] = True
             self.done[slot] = torch.cuda.Event()
             self.done[slot].record()
         self.pending.append(self.count)
+        self._slot_of[self.count] = slot
+        self.count += 1
+        self._dev_count += 1
+
+    def submit(self, rgb: torch.Tensor) -> None:
+        def convert(slot):
+            self.dev_flag[slot].zero_()
+            return ops.to8b(rgb.reshape(self.h, self.w, 3), self.swap_rb, self.dev_flag[slot]), None
+        self._submit_device(convert)
+
+    def submit_composite(self, rgb_head: torch.Tensor, last_weight: torch.Tensor, rgb_fg: torch.Tensor) -> None:
+        """submit() for the head + torso flow: ``to8b(rgb_head * last_weight[..., None] + rgb_fg)`` as one kernel
+        (ops.compose_to8b).  When the frame is a still, the torso-only image ``to8b(rgb_fg)`` comes out of the same
+        launch and is written beside it as ``<still>_torso.jpg`` (test_torso.py:528-531)."""
+        want_fg = self.is_still(self.count)
+
+        def convert(slot):
+            self.dev_flag[slot].zero_()
+            r = ops.compose_to8b(rgb_head.reshape(self.h, self.w, 3), last_weight.reshape(self.h, self.w),
+                                 rgb_fg.reshape(self.h, self.w, 3), self.swap_rb, self.dev_flag[slot], want_fg)
+            return r if want_fg else (r, None)
+        self._submit_device(convert)
+
+    def submit_u8(self, u8, nonfinite=False) -> None:
+        """A frame that is already uint8 [H, W, 3] in file channel order (converted by another rank, or by a fused tail)
+        enters the same ordered writer.  A device tensor goes through the pinned pair and the side stream like
+        submit(); a host tensor or ndarray is queued to the writer thread directly, behind every frame submitted
+        before it.  `nonfinite`: a bool, or for a device frame the int32 device flag its conversion set."""
+        if isinstance(u8, np.ndarray):
+            u8 = torch.from_numpy(u8)
+        if u8.dtype != torch.uint8 or tuple(u8.shape) != (self.h, self.w, 3):
+            raise ValueError(f"expected uint8 [{self.h},{self.w},3], got {u8.dtype} {tuple(u8.shape)}")
+        if u8.is_cuda:
+            def convert(slot):
+                if isinstance(nonfinite, torch.Tensor):
+                    self.dev_flag[slot].copy_(nonfinite.reshape(-1)[:1].to(torch.int32), non_blocking=True)
+                else:
+                    self.dev_flag[slot].fill_(int(bool(nonfinite)))
+                return u8.contiguous(), None
+            self._submit_device(convert)
+            return
+        self._retire_through(None)   # order: every device frame still in flight precedes this one
+        self._enqueue(self.count, u8.contiguous().numpy().copy(), bool(nonfinite))
         self.count += 1
 
     def release(self) -> None:
-        for index in list(self.pending):
-            self._retire(index & 1, index)
-        self.pending.clear()
+        self._retire_through(None)
         if self._worker is not None:
             self._queue.put(None)
             self._worker.join()

@@ -260,6 +260,29 @@ def to8b(rgb, swap_rb=False, nonfinite_flag=None) -> torch.Tensor:
     return out
 
 
+def compose_to8b(rgb_head, last_weight, rgb_fg, swap_rb=False, nonfinite_flag=None, want_fg=False):
+    """Tail of the head + torso clip loop in one kernel (idealnerf_compose_to8b):
+    ``to8b(rgb_head * last_weight[..., None] + rgb_fg)``, [..., 3] / [...] / [..., 3] fp32 -> [..., 3] uint8, the bytes of
+    `to8b` on the eager expression.  A non-finite composite value is written as 0 and sets `nonfinite_flag`.
+    ``want_fg=True`` returns ``(out, to8b(rgb_fg))``: the torso-only still of the same frame."""
+    lib = _lib.load()
+    if rgb_head.shape[-1] != 3:
+        raise IdealNerfError(f"compose_to8b expects rgb_head [..., 3], got {tuple(rgb_head.shape)}")
+    _shape(rgb_fg, "rgb_fg", *rgb_head.shape)
+    _shape(last_weight, "last_weight", *rgb_head.shape[:-1])
+    if nonfinite_flag is not None and (nonfinite_flag.dtype != torch.int32 or not nonfinite_flag.is_cuda
+                                       or nonfinite_flag.numel() < 1):
+        raise IdealNerfError("nonfinite_flag must be an int32 device tensor")
+    with _Launch(rgb_head, last_weight, rgb_fg, nonfinite_flag) as L:
+        ptrs = (_ptr(rgb_head, "rgb_head"), _ptr(last_weight, "last_weight"), _ptr(rgb_fg, "rgb_fg"))
+        out = torch.empty(rgb_head.shape, dtype=torch.uint8, device=rgb_head.device)
+        fg_out = torch.empty_like(out) if want_fg else None
+        check(lib.idealnerf_compose_to8b(*ptrs, rgb_head.numel() // 3, int(bool(swap_rb)), out.data_ptr(),
+                                         fg_out.data_ptr() if want_fg else None,
+                                         nonfinite_flag.data_ptr() if nonfinite_flag is not None else None, L.stream))
+    return (out, fg_out) if want_fg else out
+
+
 def coarse_depths(rays, t_vals, t_rand=None, lindisp=False) -> torch.Tensor:
     lib = _lib.load()
     _shape(rays, "rays", None, RAY_FLOATS)

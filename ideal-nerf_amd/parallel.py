@@ -1,5 +1,7 @@
 """Multi-GPU tiling of the per-ray path: one process per GPU, weights replicated, the
-frame split into contiguous row bands, one all-gather of the rendered tiles per frame.
+frame split into contiguous row bands, one all-gather of the rendered tiles per frame -- or,
+for a whole clip, whole frames dealt round-robin to the ranks (``frames_of``) and assembled in
+order on rank 0 (``ClipAssembler``): no collective until a frame is finished bytes.
 
 This replaces the reference's single-process ``nn.DataParallel`` ray scatter / output
 gather (NeRFs/HeadNeRF/train/distribute_nerf.py:457-466, test/test_distribute_nerf.py:
@@ -7,7 +9,7 @@ gather (NeRFs/HeadNeRF/train/distribute_nerf.py:457-466, test/test_distribute_ne
 -- no input scatter -- and only the outputs are exchanged (393 KB per rank for a 512^2
 frame at 8 ranks; one RCCL all_gather over xGMI, latency-bound).
 """
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -71,3 +73,94 @@ def average_gradients(params, group=None) -> None:
         else:
             p.grad.copy_(g)
         off += n
+
+
+def frames_of(rank: int, world: int, n_frames: int) -> range:
+    """Frame-parallel clip rendering: rank r renders frames r, r + N, r + 2N, ...  Shares are
+    disjoint, increasing, cover the clip and differ by at most one frame."""
+    if not 0 <= rank < world:
+        raise ValueError(f"rank {rank} outside a world of {world}")
+    return range(rank, max(int(n_frames), 0), world)
+
+
+class ClipAssembler:
+    """Puts the frames of ``frames_of`` shares back in clip order in front of one writer.
+
+    Every rank calls ``push(u8_frame, nonfinite)`` once per round, in its ``frames_of`` order; a rank whose share
+    is one frame short calls ``push(None)`` in the last round.  Round k carries the frames k*N .. k*N+N-1 to
+    rank 0 in one ``dist.gather`` of equal uint8 payloads (the frame's bytes and one flag byte: host tensors
+    under gloo, device tensors under RCCL); rank 0 hands them to ``sink.submit_u8`` in frame order and drops the
+    placeholders.  Each rank has converted its own frame, so only bytes travel.  ``sink`` is anything with
+    ``submit_u8(frame, nonfinite)`` and ``release()`` (``frame_io.FrameSink``); ranks other than 0 pass None.
+    Without an initialised process group, or with one rank, push() is sink.submit_u8()."""
+
+    def __init__(self, sink, n_frames: int, group=None):
+        self.sink, self.n_frames, self.group = sink, int(n_frames), group
+        self.on = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+        self.world = dist.get_world_size(group) if self.on else 1
+        self.rank = dist.get_rank(group) if self.on else 0
+        self.root = dist.get_global_rank(group, 0) if self.on and group is not None else 0
+        self.device_payloads = self.on and dist.get_backend(group) == "nccl"
+        self.rounds = -(-self.n_frames // self.world)
+        self.round = 0
+        self.shape: Optional[Tuple[int, ...]] = None
+        self._flagged: List[int] = []     # frames whose flag reached this object as a host bool
+        if self.rank == 0 and sink is None:
+            raise ValueError("rank 0 assembles the clip: it needs a sink")
+
+    def _agree_on_shape(self, frame) -> None:
+        """Round 0: rank 0 (which holds frame 0) tells the frame shape to ranks that may never hold one."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.device_payloads else torch.device("cpu")
+        hw = torch.tensor(list(frame.shape) if self.rank == 0 else [0, 0, 0], dtype=torch.int64, device=dev)
+        dist.broadcast(hw, src=self.root, group=self.group)
+        self.shape = tuple(int(v) for v in hw.tolist())
+        self.payload_device = dev
+
+    def push(self, frame, nonfinite=False) -> None:
+        """frame: uint8 [H, W, 3] (device or host tensor, or ndarray), or None for the placeholder of an uneven last
+        round; nonfinite: bool, or the int32 device flag the frame's conversion set."""
+        if self.round >= self.rounds:
+            raise RuntimeError(f"push() number {self.round + 1} for a clip of {self.rounds} round(s)")
+        index = self.round * self.world + self.rank
+        if (frame is None) != (index >= self.n_frames):
+            raise ValueError(f"round {self.round}: rank {self.rank} " + ("has no frame left" if frame is not None else f"owes frame {index}"))
+        if not self.on:
+            if not isinstance(nonfinite, torch.Tensor) and nonfinite:
+                self._flagged.append(index)
+            self.sink.submit_u8(frame, nonfinite)
+            self.round += 1
+            return
+        if frame is not None and not isinstance(frame, torch.Tensor):
+            frame = torch.as_tensor(frame)
+        if self.shape is None:
+            self._agree_on_shape(frame)
+        n = self.shape[0] * self.shape[1] * self.shape[2]
+        payload = torch.zeros(n + 1, dtype=torch.uint8, device=self.payload_device)
+        if frame is not None:
+            if frame.dtype != torch.uint8 or tuple(frame.shape) != self.shape:
+                raise ValueError(f"expected uint8 {list(self.shape)}, got {frame.dtype} {list(frame.shape)}")
+            flag = (nonfinite.reshape(-1)[:1] != 0) if isinstance(nonfinite, torch.Tensor) else torch.tensor([bool(nonfinite)])
+            payload[:n] = frame.reshape(-1).to(self.payload_device)
+            payload[n:] = flag.to(device=self.payload_device, dtype=torch.uint8)
+        parts = [torch.empty_like(payload) for _ in range(self.world)] if self.rank == 0 else None
+        dist.gather(payload, parts, dst=self.root, group=self.group)
+        if self.rank == 0:
+            for r, part in enumerate(parts):
+                if self.round * self.world + r >= self.n_frames:
+                    break       # placeholders of the uneven last round
+                flag = part[n:].to(torch.int32) if part.is_cuda else bool(part[n])
+                if flag is True:
+                    self._flagged.append(self.round * self.world + r)
+                self.sink.submit_u8(part[:n].view(self.shape), flag)
+        self.round += 1
+
+    def close(self):
+        """After the last round: rank 0 releases the sink and returns dict(n_frames, nonfinite_frames); others None."""
+        if self.round != self.rounds:
+            raise RuntimeError(f"close() after {self.round} of {self.rounds} round(s)")
+        if self.rank != 0:
+            return None
+        self.sink.release()
+        # a device flag is read by the sink together with the frame's bytes: the sink knows those frames
+        flagged = set(self._flagged) | {int(i) for i in getattr(self.sink, "nonfinite_frames", ())}
+        return dict(n_frames=self.n_frames, nonfinite_frames=sorted(flagged))

@@ -432,6 +432,17 @@ int idealnerf_audio_net_bwd(const idn_audio_net_params* p, const idn_audio_net_g
  */
 int idealnerf_to8b(const float* rgb, int64_t n_pixels, int swap_rb, uint8_t* out, int* nonfinite_flag, void* stream);
 
+/* Tail of the head + torso clip loop (NeRFs/TorsoNeRF/test_torso.py:523-525, train_torso.py:269-270) as one kernel:
+ *   out = to8b(rgb_head * last_weight[:, None] + rgb_fg)
+ * rgb_head [n,3], last_weight [n], rgb_fg [n,3] fp32 -> out [n,3] u8; swap_rb and nonfinite_flag as idealnerf_to8b.
+ * The product and the sum round once each (no contraction), so for a finite composite out equals idealnerf_to8b of the
+ * eager expression bit for bit.  A NaN/Inf in any input makes the composite NaN/Inf: that value is written as 0 and
+ * flagged (idealnerf_to8b writes 255 for +Inf, numpy's clip; both flag it).
+ * fg_out (may be NULL): [n,3] u8 = idealnerf_to8b(rgb_fg), the every-10th-frame "_torso.jpg" still (test_torso.py:529-530).
+ * Pointers that are 16-byte (inputs) / 4-byte (outputs) aligned take the four-pixels-per-thread path; any others are legal. */
+int idealnerf_compose_to8b(const float* rgb_head, const float* last_weight, const float* rgb_fg, int64_t n_pixels,
+                           int swap_rb, uint8_t* out, uint8_t* fg_out, int* nonfinite_flag, void* stream);
+
 /*
  * Measurement aid (no reference counterpart): between begin and end, every launch of
  * the fused PE+MLP kernel is bracketed by HIP events on its own stream.  end()

@@ -1,0 +1,240 @@
+#!/usr/bin/env python3
+"""Render a whole clip to an AVI and print one JSON line: the command line over idealnerf_amd.clip.
+
+    python tools/render_clip.py --flow torso --frames 25 --out clip.avi             # head + torso, synthetic scene
+    python tools/render_clip.py --flow torso --frames 64 --gpus 8 --out clip.avi    # frame-parallel, one rank per GPU
+    python tools/render_clip.py --flow head --datadir dataset/May --aud-file aud.npy --ckpt run/head.tar --out clip.avi
+    python tools/render_clip.py --tail-timing                                        # the fused tail against the eager ops
+
+--flow torso is `clip.render_torso_clip` on the scene bench.py's torso measurement builds (synthetic.frame, xavier seeds
+2..5 with density gains 300 / 4, plain bf16, perturb 0, 512 x 512, 64 + 128 samples) with a seeded pose and audio track of
+--frames entries.  --flow head is `clip.render_head_clip` on a dataset directory in the reference's format, weights from a
+reference checkpoint (--ckpt) or xavier.  --gpus N starts N ranks as fresh child processes (`python -m
+torch.distributed.run`, rendezvous on 127.0.0.1); this parent never opens the GPU.  IDN_DIST_BACKEND=gloo
+IDN_FORCE_DEVICE=0 rehearses N > 1 on one GPU (the ranks share it: that proves the path, it is not a scaling number).
+
+The line: {"metric": "frames/s (...)", "value", "n_frames", "nonfinite_frames", "seconds", "frames_per_s", "world", ...}.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def parse():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--flow", choices=("torso", "head"), default="torso")
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--frames", type=int, default=25, help="clip length (torso: at least the smoothing window, 8)")
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--perturb", type=float, default=0.0)
+    ap.add_argument("--seed", type=int, default=None, help="per-frame draws seeded with seed + frame (perturb > 0)")
+    ap.add_argument("--warmup", type=int, default=1, help="frames rendered and thrown away before the clip is timed")
+    ap.add_argument("--out", default="clip.avi")
+    ap.add_argument("--codec", choices=("MJPG", "raw"), default="MJPG")
+    ap.add_argument("--swap-rb", action="store_true")
+    ap.add_argument("--still-every", type=int, default=0)
+    ap.add_argument("--still-path", default=None, help="torso: a directory; head: a template such as out/frame_{i}.jpg")
+    ap.add_argument("--datadir", default=None)
+    ap.add_argument("--aud-file", default="aud.npy")
+    ap.add_argument("--ckpt", default=None)
+    ap.add_argument("--global-step", type=int, default=None, help="head: default is the checkpoint's, else nosmo_iters")
+    ap.add_argument("--tail-timing", action="store_true", help="HIP-event time of ops.compose_to8b against multiply + add + to8b")
+    return ap.parse_args()
+
+
+def launch(n, argv):
+    """N ranks as children of this process, which has not touched the GPU; rank 0's JSON line is relayed."""
+    import signal
+    import socket
+    import subprocess
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    env.setdefault("OMP_NUM_THREADS", "4")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
+    child = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, start_new_session=True)
+    try:
+        out, _ = child.communicate(timeout=float(os.environ.get("IDN_LAUNCH_TIMEOUT_S", "1500")))
+    except subprocess.TimeoutExpired:
+        for sig in (signal.SIGTERM, signal.SIGKILL):     # the whole group, by its id
+            try:
+                os.killpg(child.pid, sig)
+                child.wait(timeout=15)
+                break
+            except ProcessLookupError:
+                break
+            except subprocess.TimeoutExpired:
+                continue
+        sys.stderr.write(f"render_clip.py: the {n}-rank run did not finish in time\n")
+        return 124
+    line = None
+    for ln in out.splitlines():
+        try:
+            obj = json.loads(ln)
+        except ValueError:
+            obj = None
+        if isinstance(obj, dict) and "metric" in obj:
+            line = ln
+        else:
+            sys.stderr.write(ln + "\n")
+    if child.returncode != 0 or line is None:
+        sys.stderr.write(f"render_clip.py: the ranks failed (exit code {child.returncode}) or printed no result line\n")
+        return child.returncode or 1
+    print(line, flush=True)
+    return 0
+
+
+def init_ranks():
+    import datetime
+    import torch
+    import torch.distributed as dist
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("IDN_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    backend = os.environ.get("IDN_DIST_BACKEND", "nccl") if world > 1 else None
+    have = torch.cuda.device_count()
+    if "IDN_FORCE_DEVICE" not in os.environ and (local >= have or (backend == "nccl" and world > have)):
+        sys.exit(f"render_clip.py: rank {rank} of {world} needs GPU {local}, but this node exposes {have}: use --gpus <= {have}, "
+                 "or rehearse with IDN_DIST_BACKEND=gloo IDN_FORCE_DEVICE=0")
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    if backend is not None:
+        limit = datetime.timedelta(seconds=int(os.environ.get("IDN_DIST_TIMEOUT_S", "300")))
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev, timeout=limit)
+        else:
+            dist.init_process_group(backend, timeout=limit)
+    return world, rank, dev, backend
+
+
+def torso_scene(args, dev):
+    import numpy as np
+    import torch
+    import idealnerf_amd
+    from idealnerf_amd import synthetic
+    from idealnerf_amd.helper import RenderConfig
+    from idealnerf_amd.train_torso import Network
+    H = W = args.size
+    syn = synthetic.frame(H, W, seed=0)
+    cfg = RenderConfig(perturb=args.perturb, chunk=32768, near=syn["near"], far=syn["far"], dim_expr=76)
+    torch.manual_seed(0)   # the audio nets: every rank builds the same network
+    net = Network(H, W, syn["focal"], syn["near"], syn["far"], 32768, 64, 128, args=cfg, dim_expr_head=76).to(dev).eval()
+    for i, m in enumerate((net.face_nerf_coarse, net.face_nerf_fine, net.torso_coarse_nerf, net.torso_fine_nerf)):
+        synthetic.xavier_state_dict(m, 2 + i, 300.0 if i < 2 else 4.0, 0.3 if i < 2 else -0.2)
+    idealnerf_amd.set_render_precision(net, args.precision)
+    bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]])
+    poses = torch.stack([torch.cat([synthetic.frame(H, W, seed=j)["c2w"], bottom], 0) for j in range(args.frames)])
+    auds = torch.from_numpy(np.random.RandomState(11).standard_normal((args.frames, 16, 29)).astype(np.float32))
+    return net, dict(poses=poses, auds=auds, bc_img=syn["bc"]), dict(expr=syn["expr"], latent_code=syn["latent"], torso_pose=poses[0])
+
+
+def run_torso(args, dev):
+    from idealnerf_amd import clip
+    net, track, cond = torso_scene(args, dev)
+    common = dict(cond, seed=args.seed, swap_rb=args.swap_rb)
+    if args.warmup:   # first-launch costs (code objects, weight packing, pinned buffers) stay out of the clip's time
+        clip.render_torso_clip(net, track["poses"], track["auds"], track["bc_img"], None, frames=range(args.warmup), codec="raw", **common)
+    if args.still_every and args.still_path:
+        os.makedirs(args.still_path, exist_ok=True)
+    return clip.render_torso_clip(net, track["poses"], track["auds"], track["bc_img"], args.out, codec=args.codec,
+                                  still_every=args.still_every, still_path=args.still_path, **common)
+
+
+def run_head(args, dev):
+    import torch
+    import idealnerf_amd
+    from types import SimpleNamespace
+    from idealnerf_amd import checkpoint, clip, dataset, synthetic
+    from idealnerf_amd.audio_exp_nerf import Network
+    from idealnerf_amd.helper import RenderConfig
+    if not args.datadir:
+        sys.exit("render_clip.py: --flow head needs --datadir (a dataset directory in the reference's format)")
+    flags = SimpleNamespace(gt_dirs="head_imgs", testskip=1, N_rand=64, sample_rate=0.95, mouth_rays=8, torso_rays=4)
+    ds = dataset.GetData(args.datadir, args.aud_file, "val", flags, skip=1, device=dev)
+    cfg = RenderConfig(perturb=args.perturb)
+    net = Network(ds.H, ds.W, ds.focal, cfg.near, cfg.far, cfg.chunk, None, cfg.N_samples, cfg.N_importance, args=cfg)
+    step, latent = cfg.nosmo_iters, torch.zeros(32)
+    if args.ckpt:
+        step, codes = checkpoint.load_checkpoint(args.ckpt, net, map_location="cpu")
+        latent = codes[0]
+    else:
+        synthetic.xavier_state_dict(net.face_nerf_coarse, 2, 300.0, 0.3)
+        synthetic.xavier_state_dict(net.face_nerf_fine, 3, 300.0, 0.3)
+    net = net.to(dev).eval()
+    idealnerf_amd.set_render_precision(net, args.precision)
+    frames = range(min(args.frames, ds.data_size))
+    return clip.render_head_clip(net, ds, args.out, step if args.global_step is None else args.global_step, latent_code=latent,
+                                 frames=frames, seed=args.seed, codec=args.codec, swap_rb=args.swap_rb,
+                                 still_every=args.still_every, still_path=args.still_path)
+
+
+def tail_timing(dev, sizes=(450, 512), reps=200):
+    """HIP-event time per call of the fused tail and of the three eager launches it replaces."""
+    import torch
+    from idealnerf_amd import ops
+    out = {}
+    for size in sizes:
+        g = torch.Generator(device=dev).manual_seed(size)
+        rgb = torch.rand((size, size, 3), device=dev, generator=g)
+        lw = torch.rand((size, size), device=dev, generator=g)
+        fg = torch.rand((size, size, 3), device=dev, generator=g) * 0.5
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        ways = {"compose_to8b_us": lambda: ops.compose_to8b(rgb, lw, fg, False, flag),
+                "compose_to8b_with_fg_us": lambda: ops.compose_to8b(rgb, lw, fg, False, flag, want_fg=True),
+                "eager_mul_add_to8b_us": lambda: ops.to8b(rgb * lw[..., None] + fg, False, flag)}
+        assert torch.equal(ways["compose_to8b_us"](), ways["eager_mul_add_to8b_us"]())
+        res = {}
+        for name, fn in ways.items():
+            for _ in range(20):
+                fn()
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            start.record()
+            for _ in range(reps):
+                fn()
+            stop.record()
+            stop.synchronize()
+            res[name] = start.elapsed_time(stop) * 1e3 / reps
+        res["note"] = f"back-to-back calls, {reps} per figure, each including its output allocation; host launch cost bounds the small sizes"
+        out[f"{size}x{size}"] = res
+    return out
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "RANK" not in os.environ:
+        return launch(args.gpus, sys.argv[1:])
+    import torch
+    import torch.distributed as dist
+    world, rank, dev, backend = init_ranks()
+    try:
+        if args.tail_timing:
+            print(json.dumps({"metric": "fused clip tail, microseconds per call", "device": torch.cuda.get_device_name(dev),
+                              "tail": tail_timing(dev)}), flush=True)
+            return 0
+        res = (run_torso if args.flow == "torso" else run_head)(args, dev)
+        if res is not None:
+            what = "head + torso composite" if args.flow == "torso" else "head only"
+            print(json.dumps(dict(res, metric=f"frames/s ({what} clip, render + convert + copy + file, whole job)",
+                                  value=res["frames_per_s"], unit="frames/s", higher_is_better=True, n_gpus=world, backend=backend,
+                                  shared_device="IDN_FORCE_DEVICE" in os.environ and world > 1, flow=args.flow, size=args.size,
+                                  dtype=args.precision, perturb=args.perturb, codec=args.codec, warmup=args.warmup,
+                                  device=torch.cuda.get_device_name(dev))), flush=True)
+    finally:
+        if dist.is_available() and dist.is_initialized():
+            dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
