@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("IDN_LIB") or os.path.join(HERE, "libidealnerf.so")
 
 IDN_PREC_F32, IDN_PREC_BF16X3, IDN_PREC_BF16, IDN_PREC_FP16X3, IDN_PREC_BF16X6 = 0, 1, 2, 3, 4
 RAY_FLOATS = 11
+SAMPLE_MAX_REGION = 4096   # IDN_SAMPLE_MAX_REGION
 PROF_KINDS = ("mlp_fwd", "mlp_fwd_save", "delta_chain", "dw_gemm", "dw_gemm_x6", "mlp_fwd_save_x6", "delta_chain_x6")   # IDN_PROF_* of include/idealnerf.h
 
 fp = C.c_void_p  # device pointers travel as integers
@@ -78,6 +79,11 @@ PROTOTYPES = {
     "idealnerf_to8b": (C.c_int, [fp, C.c_int64, C.c_int, fp, fp, fp]),
     "idealnerf_compose_to8b": (C.c_int, [fp, fp, fp, C.c_int64, C.c_int, fp, fp, fp, fp]),
     "idealnerf_philox_uniform": (C.c_int, [C.c_uint64, C.c_int, C.c_int64, C.c_int64, C.c_int, fp, fp]),
+    "idealnerf_sample_pixels_workspace_bytes": (C.c_size_t, []),
+    "idealnerf_sample_pixels": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
+                                          fp, C.c_size_t, fp, fp]),
+    "idealnerf_gather_rays": (C.c_int, [fp, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                        fp, fp, fp, fp, fp, fp, fp, fp]),
     "idealnerf_coarse_depths": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, fp, fp]),
     "idealnerf_composite_fwd": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int64, C.c_int, C.POINTER(CompositeOut), fp]),
     "idealnerf_sample_pdf_fwd": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp]),

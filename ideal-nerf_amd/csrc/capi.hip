@@ -165,6 +165,40 @@ int idealnerf_philox_uniform(uint64_t seed, int which, int64_t row0, int64_t n_r
     return launch_philox_uniform((unsigned long long)seed, which, row0, n_rows, n_cols, out, (hipStream_t)stream);
 }
 
+size_t idealnerf_sample_pixels_workspace_bytes(void) { return 4 * sizeof(int); }
+
+int idealnerf_sample_pixels(const uint8_t* region_map, int H, int W, int n_rect, int n_outside, int n_mouth, int n_torso,
+                            uint64_t seed, uint64_t draw, void* workspace, size_t workspace_bytes, int64_t* sel, void* stream) {
+    const int counts[4] = {n_rect, n_outside, n_mouth, n_torso};
+    static const char* const names[4] = {"rect", "outside", "mouth", "torso"};
+    if (H <= 0 || W <= 0 || (int64_t)H * W > (1LL << 30)) return fail(IDN_EINVAL, "bad frame %d x %d", H, W);
+    int64_t total = 0;
+    for (int g = 0; g < 4; ++g) {
+        if (counts[g] < 0) return fail(IDN_EINVAL, "negative %s count %d", names[g], counts[g]);
+        if (counts[g] > IDN_SAMPLE_MAX_REGION)
+            return fail(IDN_EUNSUPPORTED, "%s count %d exceeds IDN_SAMPLE_MAX_REGION = %d picks per region", names[g], counts[g],
+                        IDN_SAMPLE_MAX_REGION);
+        total += counts[g];
+    }
+    if (!region_map || !workspace || (total > 0 && !sel)) return fail(IDN_EINVAL, "NULL pointer");
+    if (workspace_bytes < idealnerf_sample_pixels_workspace_bytes() || ((uintptr_t)workspace & 3u))
+        return fail(IDN_EWORKSPACE, "workspace of %zu bytes (need %zu, int32-aligned)", workspace_bytes, idealnerf_sample_pixels_workspace_bytes());
+    return launch_sample_pixels(region_map, H, W, counts, (unsigned long long)seed, (unsigned long long)draw, (int*)workspace,
+                                (long long*)sel, (hipStream_t)stream);
+}
+
+int idealnerf_gather_rays(const int64_t* sel, int64_t n, const float* c2w, int H, int W, float focal, float cx, float cy,
+                          const uint8_t* image, const uint8_t* background, const float* target_table, const float* background_table,
+                          float* batch_rays, float* target_s, float* bc_rgb, void* stream) {
+    if (H <= 0 || W <= 0 || (int64_t)H * W > (1LL << 30)) return fail(IDN_EINVAL, "bad frame %d x %d", H, W);
+    if (n < 0 || n > 0x7fffffffLL / 8) return fail(IDN_EINVAL, "bad n %lld", (long long)n);
+    if (n == 0) return IDN_OK;
+    if (!sel || !c2w || !image || !background || !target_table || !background_table || !batch_rays || !target_s || !bc_rgb)
+        return fail(IDN_EINVAL, "NULL pointer");
+    return launch_gather_rays((const long long*)sel, n, c2w, H, W, focal, cx, cy, image, background, target_table, background_table,
+                              batch_rays, target_s, bc_rgb, (hipStream_t)stream);
+}
+
 int idealnerf_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int lindisp, int64_t n_rays,
                             int n_samples, float* z, void* stream) {
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes");

@@ -227,6 +227,12 @@ struct Draws {
     int on;
 };
 int launch_philox_uniform(unsigned long long seed, int which, int64_t row0, int64_t n_rows, int n_cols, float* out, hipStream_t s);
+// sampler.hip: the training loader's region-weighted pixel draw and the gather of the drawn pixels' rays / colours
+int launch_sample_pixels(const unsigned char* map, int H, int W, const int counts[4], unsigned long long seed, unsigned long long draw,
+                         int* population, long long* sel, hipStream_t s);
+int launch_gather_rays(const long long* sel, int64_t n, const float* c2w_host, int H, int W, float focal, float cx, float cy,
+                       const unsigned char* image, const unsigned char* background, const float* target_table,
+                       const float* background_table, float* batch_rays, float* target_s, float* bc_rgb, hipStream_t s);
 int launch_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays, int S,
                          int lindisp, float* z, hipStream_t s, Draws draws = Draws{0, 0, 0});
 int launch_composite(const float* raw, const float* z, const float* rays, const float* bc, int64_t n_rays, int S,

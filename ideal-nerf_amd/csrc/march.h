@@ -7,11 +7,9 @@ namespace idn {
 
 constexpr int kMaxSpl = 4;  // samples per lane: S <= 256
 
-// Column `col` of row `row` of the draw table (include/idealnerf.h: idealnerf_philox_uniform): Philox4x32-10 with
-// key = seed, counter = (col / 4, 0, row); word col % 4 as a 24-bit uniform on [0, 1).
-__device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigned long long row, unsigned col) {
-    unsigned c0 = col >> 2, c1 = 0u, c2 = (unsigned)row, c3 = (unsigned)(row >> 32);
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds on the counter (c0..c3) under the key (k0, k1).  The one round function of
+// the library: the draw table below and the ray sampler's sort keys (sampler.hip) both come from it.
+__device__ __forceinline__ void philox4x32_10(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0, unsigned k1) {
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
         const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
@@ -23,6 +21,13 @@ __device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigne
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }
+}
+
+// Column `col` of row `row` of the draw table (include/idealnerf.h: idealnerf_philox_uniform): Philox4x32-10 with
+// key = seed, counter = (col / 4, 0, row); word col % 4 as a 24-bit uniform on [0, 1).
+__device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigned long long row, unsigned col) {
+    unsigned c0 = col >> 2, c1 = 0u, c2 = (unsigned)row, c3 = (unsigned)(row >> 32);
+    philox4x32_10(c0, c1, c2, c3, (unsigned)seed, (unsigned)(seed >> 32));
     const unsigned w = col & 3u;
     const unsigned x = w == 0 ? c0 : w == 1 ? c1 : w == 2 ? c2 : c3;
     return (float)(x >> 8) * 0x1p-24f;

@@ -31,9 +31,11 @@ def _imread(path):
     return np.asarray(Image.open(path))
 
 
-def select_pixels(H, W, face_rect, landmark, parse_img, n_rand, mouth_rays, torso_rays, sample_rate):
-    """-> int64 [n_rand, 2] (row, col) in the reference's order: face rect, outside rect, mouth,
-    torso (audio_exp_nerf.py:143-187).  Draws from the global numpy RNG exactly like upstream."""
+def region_masks(H, W, face_rect, landmark, parse_img):
+    """The pixel regions the sampler draws from (audio_exp_nerf.py:143-175) -> (coords [H W, 2] float32 (row, col), mouth [H W],
+    rect [H W], torso [H, W]) as boolean masks.  Upstream's row/column convention is kept: pixel ROWS are compared against the
+    landmark / rect *x* bounds (:150-155).  The one definition of the regions: `select_pixels` draws from these masks and
+    `region_byte_map` packs them for the device-side sampler."""
     mouth = landmark[48:]
     max_x, min_x = np.max(mouth[:, 0]) + 20, np.min(mouth[:, 0]) - 20
     max_y, min_y = np.max(mouth[:, 1]) + 20, np.min(mouth[:, 1]) - 20
@@ -43,8 +45,26 @@ def select_pixels(H, W, face_rect, landmark, parse_img, n_rand, mouth_rays, tors
     rect_w = ((coords[:, 0] >= face_rect[0]) & (coords[:, 0] <= face_rect[0] + face_rect[2]) &
               (coords[:, 1] >= face_rect[1]) & (coords[:, 1] <= face_rect[1] + face_rect[3]))
     torso = (parse_img[:, :, 0] == 255) & (parse_img[:, :, 1] == 0) & (parse_img[:, :, 2] == 0)
+    return coords, mouth_w, rect_w, torso
+
+
+REGION_NAMES = ("rect", "outside", "mouth", "torso")   # bit g of the byte map, row block g of a batch
+
+
+def region_byte_map(H, W, face_rect, landmark, parse_img):
+    """uint8 [H, W]: bit 0 = face rect minus mouth box, bit 1 = outside the face rect, bit 2 = mouth box, bit 3 = torso
+    (parsing == (255, 0, 0)) -- the four populations `select_pixels` draws from, for ops.sample_pixels."""
+    _, mouth_w, rect_w, torso = region_masks(H, W, face_rect, landmark, parse_img)
+    m = ((rect_w & ~mouth_w).astype(np.uint8) | ((~rect_w).astype(np.uint8) << 1) | (mouth_w.astype(np.uint8) << 2)).reshape(H, W)
+    return m | (torso.astype(np.uint8) << 3)
+
+
+def select_pixels(H, W, face_rect, landmark, parse_img, n_rand, mouth_rays, torso_rays, sample_rate):
+    """-> int64 [n_rand, 2] (row, col) in the reference's order: face rect, outside rect, mouth,
+    torso (audio_exp_nerf.py:143-187).  Draws from the global numpy RNG exactly like upstream."""
+    coords, mouth_w, rect_w, torso = region_masks(H, W, face_rect, landmark, parse_img)
     c_mouth, c_rect, c_norect = coords[mouth_w], coords[rect_w & ~mouth_w], coords[~rect_w]
-    c_torso = np.stack([rows, cols], -1)[torso].reshape(-1, 2)
+    c_torso = coords.reshape(H, W, 2)[torso].reshape(-1, 2)
     sample_num = n_rand - mouth_rays - torso_rays
     rect_num = int(sample_num * sample_rate)
     norect_num = sample_num - rect_num
@@ -114,3 +134,98 @@ class GetData(torch.utils.data.Dataset):
         bc_rgb = bc_rgb if self.mode == "train" else self.background_img
         exp = torch.tensor(self.all_exprs[index], dtype=torch.float32)
         return batch_rays, target_s, bc_rgb, self.auds, raw_img, pose, exp, index
+
+
+class ResidentFrames:
+    """The training clip resident on the device, drawn from by the device-side sampler: the opt-in second data path beside
+    ``GetData`` (which stays the reference's host-side loader, numpy draw sequence included).
+
+    Same constructor arguments as ``GetData(mode="train")``.  The directory is read ONCE: per frame the ground-truth image
+    (uint8 [H, W, 3], BGR as ``GetData.__getitem__`` produces it) and the region byte map (``region_byte_map``) go to the device
+    -- 4 bytes per pixel and frame, 4.9 GB for 6 000 frames at 450 x 450 -- with the background (uint8), the clip's audio
+    windows, the expressions and the poses; the poses also stay on the host (they travel as kernel arguments, like
+    ``ops.frame_rays``'), as do the four region populations of every frame.
+
+    ``batch(index, draw)`` returns the reference's 8-tuple for frame ``index`` with the pixels of draw number ``draw``
+    (``ops.sample_pixels``: a function of (frame, seed, draw) alone): two kernel launches, no host synchronisation, no
+    device-to-host copy, no allocation beyond the three output tensors; no [H W, 11] ray tensor exists.
+
+    Raises ``ValueError`` at construction -- from the host-side populations, before anything is uploaded -- if the clip needs
+    more than ``max_bytes`` of device memory or if a region of a frame holds fewer pixels than its share of ``N_rand`` (the step
+    at which upstream's ``np.random.choice`` raises)."""
+
+    def __init__(self, data_dir, aud_file, mode, args, skip=1, device="cuda", max_bytes=8 << 30, seed=0):
+        self.data_dir, self.aud_file, self.mode, self.args, self.device, self.seed = data_dir, aud_file, mode, args, device, int(seed)
+        with open(os.path.join(data_dir, f"transforms_exp_{mode}.json")) as fp:
+            self.meta = json.load(fp)
+        frames = self.meta["frames"][::skip]
+        self.focal, self.cx, self.cy = float(self.meta["focal_len"]), float(self.meta["cx"]), float(self.meta["cy"])
+        self.H, self.W = int(self.cy * 2), int(self.cx * 2)
+        self.data_size = n = len(frames)
+        need = (n + 1) * self.H * self.W * 4
+        if max_bytes is not None and need > max_bytes:
+            raise ValueError(f"{n} frames of {self.H} x {self.W} need {need} bytes of device memory (4 per pixel and frame), more "
+                             f"than max_bytes = {max_bytes}: raise max_bytes, take fewer frames (skip=), or use GetData")
+        self.counts = ops.sample_counts(args.N_rand, args.mouth_rays, args.torso_rays, args.sample_rate)
+        if min(self.counts) < 0:
+            raise ValueError(f"N_rand {args.N_rand} is smaller than mouth_rays + torso_rays")
+        from ._lib import SAMPLE_MAX_REGION
+        if max(self.counts) > SAMPLE_MAX_REGION:
+            raise ValueError(f"the split {dict(zip(REGION_NAMES, self.counts))} asks a region for more than the sampler's "
+                             f"{SAMPLE_MAX_REGION} picks")
+        aud_features = np.load(os.path.join(data_dir, aud_file))
+        img_paths, maps, poses, exprs, auds = [], [], [], [], []
+        self.populations = np.zeros((n, 4), np.int64)
+        for i, frame in enumerate(frames):
+            fid = str(frame["img_id"])
+            img_paths.append(os.path.join(data_dir, args.gt_dirs, fid + ".jpg"))
+            parse = _imread(os.path.join(data_dir, "parsing", fid + ".png"))
+            if parse.shape[:2] != (self.H, self.W):
+                raise ValueError(f"frame {fid}: parsing image is {parse.shape[:2]}, the clip's cx / cy say {(self.H, self.W)}")
+            landmark = np.loadtxt(os.path.join(data_dir, "ori_imgs", fid + ".lms"))
+            m = region_byte_map(self.H, self.W, np.array(frame["face_rect"], dtype=np.int32), landmark, parse)
+            self.populations[i] = [int(((m >> g) & 1).sum()) for g in range(4)]
+            for g in range(4):
+                if self.populations[i, g] < self.counts[g]:
+                    raise ValueError(f"frame {fid} (index {i}): region '{REGION_NAMES[g]}' holds {self.populations[i, g]} pixels, "
+                                     f"fewer than the {self.counts[g]} the batch draws from it without replacement")
+            maps.append(m)
+            poses.append(np.array(frame["transform_matrix"])[:3, :4])
+            auds.append(aud_features[min(frame["aud_id"], aud_features.shape[0] - 1)])
+            exprs.append(frame["exp"])
+        self.all_poses = poses                                   # float64 [3, 4] each, as GetData keeps them
+        self._cams = [ops.camera_floats(p) for p in poses]       # the same matrices as the 12 floats the kernels take
+        # ---- upload
+        self.maps = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=device)
+        self.imgs = torch.empty((n, self.H, self.W, 3), dtype=torch.uint8, device=device)
+        for i in range(n):
+            self.maps[i].copy_(torch.from_numpy(maps[i]))
+            raw = _imread(img_paths[i])[..., ::-1].copy()        # upstream reads with cv2: BGR
+            if raw.shape != (self.H, self.W, 3):
+                raise ValueError(f"{img_paths[i]} is {raw.shape}, the clip's cx / cy say {(self.H, self.W, 3)}")
+            self.imgs[i].copy_(torch.from_numpy(raw))
+        del maps
+        self.background = torch.from_numpy(np.array(_imread(os.path.join(data_dir, "bc.jpg")))).to(device)
+        self.auds = torch.tensor(np.asarray(auds), dtype=torch.float).to(device)
+        self.poses = torch.tensor(np.asarray(poses), dtype=torch.float32).to(device)
+        self.exprs = torch.tensor(np.asarray(exprs), dtype=torch.float32).to(device)
+        self._sel = torch.empty(sum(self.counts), dtype=torch.int64, device=device)
+        self._ws = torch.zeros(4, dtype=torch.int32, device=device)
+        if torch.device(device).type == "cuda":
+            ops.byte_tables(device)                              # built here, so that batch() allocates nothing but its outputs
+
+    def __len__(self):
+        return self.data_size
+
+    def select(self, index, draw):
+        """The flat pixel indices of draw `draw` on frame `index` (int64 [N_rand]; the loader's own buffer, overwritten by
+        the next call in stream order)."""
+        return ops.sample_pixels(self.maps[index], self.counts, self.seed, draw, out=self._sel, workspace=self._ws)
+
+    def batch(self, index, draw):
+        """-> (batch_rays [2, n, 3], target_s [n, 3], bc_rgb [n, 3], auds, raw_img, pose, expr, index), every tensor on the device."""
+        index = int(index)
+        sel = self.select(index, draw)
+        batch_rays, target_s, bc_rgb = ops.gather_rays(sel, self._cams[index], self.H, self.W, self.focal, self.imgs[index],
+                                                       self.background, self.cx, self.cy)
+        return batch_rays, target_s, bc_rgb, self.auds, self.imgs[index], self.poses[index], self.exprs[index], index

@@ -543,6 +543,96 @@ def philox_uniform(seed, which, row0, n_rows, n_cols, device) -> torch.Tensor:
     return out
 
 
+def sample_counts(n_rand, mouth_rays, torso_rays, sample_rate):
+    """(rect, outside, mouth, torso) picks of one batch, computed as upstream does (audio_exp_nerf.py:176-178)."""
+    sample_num = int(n_rand) - int(mouth_rays) - int(torso_rays)
+    rect_num = int(sample_num * sample_rate)
+    return rect_num, sample_num - rect_num, int(mouth_rays), int(torso_rays)
+
+
+def camera_floats(c2w):
+    """[3, 4] / [4, 4] camera matrix (tensor, array or nested list) -> the 12 host floats the ray kernels take as arguments."""
+    if isinstance(c2w, C.Array):
+        return c2w
+    m = torch.as_tensor(c2w, dtype=torch.float32).detach().cpu()
+    if m.dim() != 2 or tuple(m.shape) not in ((3, 4), (4, 4)):
+        raise IdealNerfError(f"c2w must be [3, 4] or [4, 4], got {list(m.shape)}")
+    return (C.c_float * 12)(*[float(v) for v in m[:3, :4].reshape(-1).tolist()])
+
+
+def sample_pixels(region_map, counts, seed, draw, out=None, workspace=None) -> torch.Tensor:
+    """The region-weighted pixel draw of the training loader on the device (idealnerf_sample_pixels): region_map uint8 [H, W]
+    (bit 0 rect minus mouth, 1 outside rect, 2 mouth, 3 torso), counts = (rect, outside, mouth, torso) -> int64 [sum(counts)] flat
+    pixel indices in that order; a function of (region_map, counts, seed, draw) alone.  `out` / `workspace` (int32 [>= 4], receives
+    the region populations): the caller's buffers, for a call that allocates nothing."""
+    lib = _lib.load()
+    if region_map.dim() != 2:
+        raise IdealNerfError(f"region_map must be [H, W], got {list(region_map.shape)}")
+    counts = [int(c) for c in counts]
+    if len(counts) != 4 or min(counts) < 0:
+        raise IdealNerfError(f"counts must be four non-negative numbers (rect, outside, mouth, torso), got {counts}")
+    if max(counts) > _lib.SAMPLE_MAX_REGION:
+        raise IdealNerfError(f"a region count of {max(counts)} exceeds the sampler's {_lib.SAMPLE_MAX_REGION} picks per region")
+    H, W = region_map.shape
+    n = sum(counts)
+    _shape(out, "out", n)
+    with _Launch(region_map, out, workspace) as L:
+        mp = _ptr(region_map, "region_map", torch.uint8)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=region_map.device)
+        if workspace is None:
+            workspace = torch.empty(4, dtype=torch.int32, device=region_map.device)
+        if workspace.numel() < 4:
+            raise IdealNerfError("workspace must hold four int32")
+        check(lib.idealnerf_sample_pixels(mp, H, W, *counts, int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1),
+                                          _ptr(workspace, "workspace", torch.int32), workspace.numel() * 4,
+                                          _ptr(out, "out", torch.int64), L.stream))
+    return out
+
+
+_byte_tables: Dict[str, tuple] = {}
+
+
+def byte_tables(device):
+    """(target_table, background_table), fp32 [256] on `device`: what a byte becomes in GetData -- the target as
+    `uint8 tensor -> device -> float() / 255.0`, evaluated by that very expression on that device; the background as numpy's
+    `uint8 / 255.0` in float64, rounded to fp32 (the cast Network.forward applies)."""
+    import numpy as np
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = str(device)
+    t = _byte_tables.get(key)
+    if t is None:
+        target = torch.arange(256, dtype=torch.int32).to(torch.uint8).to(device).float() / 255.0
+        background = torch.tensor(np.arange(256, dtype=np.uint8) / 255.0).to(device).to(torch.float32)
+        t = _byte_tables[key] = (target.contiguous(), background.contiguous())
+    return t
+
+
+def gather_rays(sel, c2w, H, W, focal, image, background, cx=None, cy=None):
+    """Rays and colours of the pixels `sel` (int64 [n], flat row-major) of one training frame (idealnerf_gather_rays) ->
+    (batch_rays [2, n, 3], target_s [n, 3], bc_rgb [n, 3]) fp32.  image / background: uint8 [H, W, 3] on the device; c2w: the
+    camera on the HOST (it travels as kernel arguments), or `camera_floats` of it.  No [H W, 11] ray tensor exists."""
+    lib = _lib.load()
+    _shape(sel, "sel", None)
+    _shape(image, "image", H, W, 3)
+    _shape(background, "background", H, W, 3)
+    n = sel.shape[0]
+    m = camera_floats(c2w)
+    with _Launch(sel, image, background) as L:
+        tt, tb = byte_tables(L.device)
+        batch_rays = torch.empty((2, n, 3), dtype=torch.float32, device=sel.device)
+        target_s = torch.empty((n, 3), dtype=torch.float32, device=sel.device)
+        bc_rgb = torch.empty((n, 3), dtype=torch.float32, device=sel.device)
+        check(lib.idealnerf_gather_rays(_ptr(sel, "sel", torch.int64), n, m, int(H), int(W), float(focal),
+                                        -1.0 if cx is None else float(cx), -1.0 if cy is None else float(cy),
+                                        _ptr(image, "image", torch.uint8), _ptr(background, "background", torch.uint8),
+                                        _ptr(tt, "target table"), _ptr(tb, "background table"),
+                                        batch_rays.data_ptr(), target_s.data_ptr(), bc_rgb.data_ptr(), L.stream))
+    return batch_rays, target_s, bc_rgb
+
+
 def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals, u, n_importance,
                     t_rand=None, with_fg=False, taps=False, precision=IDN_PREC_F32, precision_fine=None, lindisp=False,
                     white_bkgd=False, noise_coarse=None, noise_fine=None, fused=None, frame=None, draws=None) -> Dict[str, torch.Tensor]:

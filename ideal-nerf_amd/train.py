@@ -1,7 +1,12 @@
 """The reference's training-loop body (NeRFs/HeadNeRF/train/audio_exp_nerf.py:529-558) as
-a function: render the sampled rays with gradients, MSE(fine) + MSE(coarse) +
-10 * lc_weight * ||latent||, Adam step, exponential learning-rate decay, PSNR.
+a function (``train_step``): render the sampled rays with gradients, MSE(fine) + MSE(coarse) +
+10 * lc_weight * ||latent||, Adam step, exponential learning-rate decay, PSNR -- and the loop around it
+(``train``, audio_exp_nerf.py:451-593): datasets, Xavier init, per-frame latent codes, resume, epochs, the validation
+frame, ``head.tar``.
 """
+import logging
+import os
+
 import torch
 
 from .helper import img2mse, mse2psnr
@@ -45,3 +50,165 @@ def train_step(network, optimizer, data, latent_codes, global_step, dataset_size
     for group in optimizer.param_groups:
         group['lr'] = new_lrate
     return dict(loss=loss.detach(), psnr=psnr, latent_code_loss=latent_code_loss.detach(), lr=new_lrate)
+
+
+logger = logging.getLogger("adnerf")
+
+
+def draw_index(global_step, rank=0, world=1):
+    """The sampler draw a replica uses at a step: rank r of N takes draw `global_step * N + r`, so the replicas of one step
+    sample different rays and no draw is used twice.  A function of the step alone: a resumed run continues the sequence."""
+    if not (0 <= rank < world) or global_step < 0:
+        raise ValueError(f"rank {rank} of {world}, step {global_step}")
+    return int(global_step) * int(world) + int(rank)
+
+
+def _as_loader_item(item):
+    """What the reference's DataLoader makes of a GetData item, as far as Network.forward reads it: the pose as a tensor."""
+    batch_rays, target_s, bc_rgb, auds, raw_img, pose, expr, index = item
+    return batch_rays, target_s, bc_rgb, auds, raw_img, torch.as_tensor(pose, dtype=torch.float32), expr, index
+
+
+def _summary_writer(logdir):
+    try:   # a TensorBoard writer if and only if it imports
+        from torch.utils.tensorboard import SummaryWriter
+    except Exception:
+        return None
+    return SummaryWriter(logdir)
+
+
+def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30):
+    """The reference's ``train()`` (audio_exp_nerf.py:451-593) on the flags ``args`` (``helper.config_parser().parse_args()``):
+    write_config, the train and validation datasets, ``Network`` + ``init_weights``, ``latent_codes = ones[n_frames, 32]``, Adam,
+    warm start from ``ft_path`` or resume from the newest ``*.tar`` of ``basedir/expname``, then epochs over the frames in
+    order (one frame per step, as upstream's forward takes them) with a log line every ``i_print`` steps, one validation frame
+    every ``100 * i_print`` and ``head.tar`` every ``i_weights``.
+
+    loader = "resident": ``dataset.ResidentFrames`` -- the clip on the device, pixels drawn there, draw number
+             ``draw_index(global_step, rank, world)``;
+    loader = "reference": ``dataset.GetData`` -- upstream's host-side loader and its numpy draw sequence.
+
+    Two departures from upstream, both so that a run resumed from ``head.tar`` continues exactly as the uninterrupted run
+    would (with perturb = 0 and the resident loader: bit for bit): ``head.tar`` is written at upstream's moments but records
+    the number of COMPLETED steps (upstream records the index of the step just done and so repeats that step after a resume),
+    and a resumed run enters its first epoch at frame ``global_step % n_frames`` (upstream restarts the epoch at frame 0 while
+    keeping ``global_step``).  ``steps``: stop after that many steps of THIS call (None: run ``N_iters + 1`` epochs).
+
+    ``on_log(kind, global_step, payload)`` receives ("train", step, {loss, psnr, learning_rate, latent_code_loss}) and
+    ("val", step, image [3, 2 H, W] RGB: prediction over ground truth); ``on_step(global_step, info)`` runs after every step.
+    Inside a process group every rank trains (``train_step`` all-reduces the gradients); rank 0 alone logs and saves.
+    -> dict(network, optimizer, latent_codes, global_step, data_size)."""
+    import numpy as np
+    from . import checkpoint, dataset
+    from .audio_exp_nerf import Network, init_weights
+    from .config import to_render_config
+    from .helper import write_config
+
+    if loader not in ("resident", "reference"):
+        raise ValueError(f"loader must be 'resident' or 'reference', got {loader!r}")
+    dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
+    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if dist_on else (0, 1)
+    basedir, expname = args.basedir, args.expname
+    run_dir = os.path.join(basedir, expname)
+    N_iters = args.N_iters + 1
+
+    if loader == "resident":
+        dataset_train = dataset.ResidentFrames(args.datadir, args.aud_file, "train", args, device=device, max_bytes=max_bytes,
+                                               seed=sample_seed)
+    else:
+        dataset_train = dataset.GetData(args.datadir, args.aud_file, mode="train", args=args, device=device)
+    dataset_val = dataset.GetData(args.datadir, args.aud_file, mode="val", args=args, skip=args.testskip, device=device)
+    logger.info(f'dataset_val length: {dataset_val.data_size}')
+    data_size = dataset_train.data_size
+    H, W, focal = dataset_val.H, dataset_val.W, dataset_val.focal
+    intrinsic = np.array([[focal, 0., W / 2], [0, focal, H / 2], [0, 0, 1.]])
+    if rank == 0:
+        write_config(args)
+
+    network = Network(H, W, focal, near=args.near, far=args.far, chunk=args.chunk, intrinsic=intrinsic,
+                      N_samlpes=args.N_samples, N_importance=args.N_importance, args=to_render_config(args)).to(device)
+    latent_codes = torch.ones(data_size, 32, dtype=torch.float32, device=device)
+    network.apply(init_weights)
+    latent_codes.requires_grad = True
+    optimizer = make_optimizer(network, latent_codes, args.lrate)
+
+    global_step = 0
+    if args.ft_path is not None and args.ft_path != 'None':
+        logger.info(f'Found ckpts:{[args.ft_path]}')
+        checkpoint.load_adnerf_finetune(args.ft_path, network, map_location=device)
+    else:
+        ckpt_path = checkpoint.latest_checkpoint(run_dir)
+        if ckpt_path is not None:
+            logger.info(f'Found ckpts:{ckpt_path}')
+            global_step, saved_codes = checkpoint.load_checkpoint(ckpt_path, network, optimizer, map_location=device)
+            latent_codes.data = saved_codes.to(device)
+
+    writer = _summary_writer(run_dir) if rank == 0 else None
+    start = int(global_step / data_size)
+    logger.info(f"start: {start}, global_step:{global_step}")
+    network.train()
+    done = 0
+    try:
+        for epoch in range(start, N_iters):
+            for it in range(global_step % data_size if epoch == start else 0, data_size):
+                if steps is not None and done >= steps:
+                    break
+                if loader == "resident":
+                    data = dataset_train.batch(it, draw_index(global_step, rank, world))
+                else:
+                    data = _as_loader_item(dataset_train[it])
+                info = train_step(network, optimizer, data, latent_codes, global_step, data_size, lrate=args.lrate,
+                                  lrate_decay=args.lrate_decay)
+
+                if global_step % args.i_print == 0 and rank == 0:
+                    scalars = dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"],
+                                   latent_code_loss=info["latent_code_loss"].item())
+                    logger.info(f"[TRAIN] epoch: {epoch} Iter: {it} LatentLoss: {scalars['latent_code_loss']}  "
+                                f"PSNR: {scalars['psnr']} LR: {info['lr']}")
+                    for k, v in scalars.items():
+                        if writer is not None:
+                            writer.add_scalar('train/' + k, v, global_step=global_step)
+                    if on_log is not None:
+                        on_log("train", global_step, scalars)
+
+                if global_step % (100 * args.i_print) == 0 and rank == 0:
+                    image = validation_frame(network, dataset_val, latent_codes, global_step, sample_seed)
+                    if writer is not None:
+                        writer.add_image("val/rgb_fine", image, global_step=global_step)
+                    if on_log is not None:
+                        on_log("val", global_step, image)
+                    logger.info('Saved test set and turn back to trainning mode')
+
+                if global_step % args.i_weights == 0 and rank == 0:
+                    path = os.path.join(run_dir, 'head.tar')
+                    checkpoint.save_checkpoint(path, network, optimizer, latent_codes, global_step + 1)
+                    logger.info(f'Saved checkpoints at {path} and start to test with network')
+                global_step += 1
+                done += 1
+                if on_step is not None:
+                    on_step(global_step, info)
+            if steps is not None and done >= steps:
+                break
+    finally:
+        if writer is not None:
+            writer.close()
+    return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
+
+
+def validation_frame(network, dataset_val, latent_codes, global_step, sample_seed=0):
+    """audio_exp_nerf.py:568-581: one randomly chosen validation frame rendered in eval mode under no_grad with
+    ``latent_codes[0]``, stacked over its ground truth, channels flipped to RGB -> [3, 2 H, W] on the host; the network
+    goes back to train mode.  The frame is chosen by a generator of its own seeded from (sample_seed, global_step) --
+    upstream shuffles its validation loader -- so a validation neither depends on nor disturbs the training draws."""
+    gen = torch.Generator().manual_seed((int(sample_seed) * 1000003 + int(global_step)) & (2 ** 63 - 1))
+    val_i = int(torch.randint(len(dataset_val), (1,), generator=gen))
+    network.eval()
+    try:
+        batch_rays, target_s, bg_img, auds, raw_img, pose, expr, index = _as_loader_item(dataset_val[val_i])
+        data = batch_rays, target_s, bg_img, auds, raw_img, pose, expr, latent_codes[0], index
+        with torch.no_grad():
+            rgb, _, _, _, _ = network([data, global_step, dataset_val.data_size])
+    finally:
+        network.train()
+    pred_with_label = torch.cat((rgb.cpu().permute(2, 0, 1), raw_img.cpu().permute(2, 0, 1) / 255.0), dim=1)
+    return pred_with_label[[2, 1, 0], :, :]

@@ -278,6 +278,44 @@ typedef struct idn_render_args {
  * counter = (c / 4, 0, low, high of 2 * (row0 + r) + which).  which: 0 = stratified offsets (t_rand), 1 = importance draws (u). */
 int idealnerf_philox_uniform(uint64_t seed, int which, int64_t row0, int64_t n_rows, int n_cols, float* out, void* stream);
 
+/*
+ * The training loader's ray sampler on the device: GetData.sample_rays (NeRFs/HeadNeRF/train/audio_exp_nerf.py:134-195) as two
+ * launches, with no host round trip and no full-frame ray tensor.  Additive entries: the ABI version is unchanged.
+ *
+ * idealnerf_sample_pixels: region_map is uint8 [H, W]; bit 0 = face rect minus mouth box, bit 1 = outside the face rect,
+ * bit 2 = mouth box, bit 3 = torso (a pixel may carry bit 3 beside another).  sel receives n_rect + n_outside + n_mouth + n_torso
+ * flat row-major pixel indices in the reference's order: rect, outside, mouth, torso (:143-187).
+ *
+ * Sampling without replacement is DEFINED, so that it can be checked exactly.  For region g in {0 rect, 1 outside, 2 mouth,
+ * 3 torso} and flat pixel p, key(p, g) = word 0 of Philox4x32-10 (the generator of idealnerf_philox_uniform) with
+ * key = (seed low, seed high) and counter = (p, g, draw low, draw high).  Region g contributes its c_g pixels with the smallest
+ * (key, p) pairs, in ascending (key, p) order: keys are independent and uniform, so this is a uniform c_g-subset in uniform random
+ * order -- the distribution of np.random.choice(replace=False).  Regions are drawn independently, as upstream.
+ * The result is a function of (region_map, counts, seed, draw) alone: launch geometry and scheduling do not enter.
+ *
+ * A per-region count above IDN_SAMPLE_MAX_REGION returns IDN_EUNSUPPORTED (nothing is truncated).  A count above the region's
+ * population cannot be seen from the host without a device read: the caller knows its populations (dataset.ResidentFrames checks
+ * them at load time); if it happens all the same, that region's rows of sel are -1, which idealnerf_gather_rays turns into zero
+ * rows.  workspace: idealnerf_sample_pixels_workspace_bytes() bytes, int32-aligned; on return (in stream order) its first four
+ * int32 hold each region's population as the kernel counted it (-1 for a region whose count is 0: not counted).
+ */
+#define IDN_SAMPLE_MAX_REGION 4096 /* largest per-region count; the reference's default split needs 2675 (N_rand 3072, mouth 256, rate 0.95) */
+size_t idealnerf_sample_pixels_workspace_bytes(void);
+int idealnerf_sample_pixels(const uint8_t* region_map, int H, int W, int n_rect, int n_outside, int n_mouth, int n_torso,
+                            uint64_t seed, uint64_t draw, void* workspace, size_t workspace_bytes, int64_t* sel, void* stream);
+
+/*
+ * idealnerf_gather_rays: for the n pixels of sel, batch_rays [2, n, 3] (origins, then UNNORMALISED directions: columns 0:3 and
+ * 3:6 of the rows idealnerf_frame_rays writes for those pixels, bit for bit -- same operations, same order), target_s [n, 3] =
+ * target_table[image[p]] and bc_rgb [n, 3] = background_table[background[p]].  c2w [host]: 12 floats, the [3, 4] camera matrix;
+ * cx / cy < 0: the frame centre, as in idealnerf_frame_rays.  image / background: uint8 [H, W, 3].  The two tables are fp32 [256]
+ * on the device: what a byte becomes (the loader's `uint8 -> float32 / 255` for the target, `float64 / 255` rounded to fp32 for
+ * the background), built once by the caller so that the values are the loader's own.  Rows of sel outside [0, H W) give zeros.
+ */
+int idealnerf_gather_rays(const int64_t* sel, int64_t n, const float* c2w, int H, int W, float focal, float cx, float cy,
+                          const uint8_t* image, const uint8_t* background, const float* target_table, const float* background_table,
+                          float* batch_rays, float* target_s, float* bc_rgb, void* stream);
+
 size_t idealnerf_render_workspace_bytes(int64_t n_rays, int n_samples, int n_importance);
 int idealnerf_render_rays_fwd(const idn_render_args* a, void* stream);
 
