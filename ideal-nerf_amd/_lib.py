@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("IDN_LIB") or os.path.join(HERE, "libidealnerf.so")
 IDN_PREC_F32, IDN_PREC_BF16X3, IDN_PREC_BF16, IDN_PREC_FP16X3, IDN_PREC_BF16X6 = 0, 1, 2, 3, 4
 RAY_FLOATS = 11
 SAMPLE_MAX_REGION = 4096   # IDN_SAMPLE_MAX_REGION
+SCORE_TILE = 32            # IDN_SCORE_TILE
 PROF_KINDS = ("mlp_fwd", "mlp_fwd_save", "delta_chain", "dw_gemm", "dw_gemm_x6", "mlp_fwd_save_x6", "delta_chain_x6")   # IDN_PROF_* of include/idealnerf.h
 
 fp = C.c_void_p  # device pointers travel as integers
@@ -84,6 +85,8 @@ PROTOTYPES = {
                                           fp, C.c_size_t, fp, fp]),
     "idealnerf_gather_rays": (C.c_int, [fp, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                         fp, fp, fp, fp, fp, fp, fp, fp]),
+    "idealnerf_frame_scores_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "idealnerf_frame_scores": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
     "idealnerf_coarse_depths": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, fp, fp]),
     "idealnerf_composite_fwd": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int64, C.c_int, C.POINTER(CompositeOut), fp]),
     "idealnerf_sample_pdf_fwd": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp]),

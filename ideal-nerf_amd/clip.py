@@ -11,6 +11,10 @@ Both are frame-parallel: inside an initialised process group rank r renders the 
 ``parallel.ClipAssembler``; rank 0 owns the ``frame_io.FrameSink`` and writes the clip in order.  There is no
 collective until a frame is finished.  Without a process group the same code renders every frame and the
 assembler is a pass-through, so a clip is the same file for any world size.
+
+``score_head_clip`` / ``score_torso_clip`` are the same two loops with ground truth beside them: every rendered frame is
+scored on the device where it was rendered (``ops.frame_scores``: squared error and SSIM, whole frame and per sampling
+region) into this rank's rows of a table, and one gather at the end of the clip puts the rows in frame order on rank 0.
 """
 import contextlib
 import math
@@ -23,7 +27,7 @@ import torch.distributed as dist
 from . import ops
 from .frame_io import FrameSink, encode_jpeg
 from .models.audio_net import clip_audio_features
-from .parallel import ClipAssembler, frames_of
+from .parallel import ClipAssembler, frames_of, gather_frame_rows
 
 
 def _ranks(group):
@@ -48,8 +52,10 @@ def _frame_rng(seed, frame, device):
         yield
 
 
-def _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, still_every, still_path, still_ids):
-    """The loop both flows share.  render_one(position, frame) -> (u8 [H, W, 3], int32 flag), both on the device."""
+def _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, still_every, still_path, still_ids, write=True):
+    """The loop every flow shares.  render_one(position, frame) -> (u8 [H, W, 3], int32 flag), both on the device; it is the
+    per-frame hook: what else a flow does with a frame (scoring it) happens in there.  write=False: the frames are rendered
+    and handed to nobody -- no sink, no assembler, no collective; render_one's return value is not looked at."""
     rank, world = _ranks(group)
     n = len(frames)
     if still_every and not still_path:
@@ -66,6 +72,8 @@ def _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, st
                 if pos < n:
                     with _frame_rng(seed, frames[pos], device):
                         u8, flag = render_one(pos, frames[pos])
+                if not write:
+                    continue
                 if assembler is None:   # rank 0 holds frame 0: its size is the clip's
                     sink = None
                     if rank == 0:
@@ -73,7 +81,7 @@ def _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, st
                                          still_every=still_every, still_path=still_path, still_ids=still_ids)
                     assembler = ClipAssembler(sink, n, group)
                 assembler.push(u8, flag if u8 is not None else False)
-        done = assembler.close() if assembler is not None else (dict(n_frames=0, nonfinite_frames=[]) if rank == 0 else None)
+        done = assembler.close() if assembler is not None else (dict(n_frames=0 if write else n, nonfinite_frames=[]) if rank == 0 else None)
     finally:
         network.train(was_training)
     if done is None:
@@ -108,6 +116,32 @@ def render_head_clip(network, dataset, path, global_step, *, latent_code, frames
     return _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, still_every, still_path, None)
 
 
+def _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose):
+    """The per-frame body of the head + torso clip loop: once per clip the smoothed audio features, then
+    pairs(j) -> (rgb of the head pair at poses[j], last_weight and rgb_fg of the torso pair at torso_pose), on the device."""
+    device = next(network.parameters()).device
+    f32 = lambda t: torch.as_tensor(t).to(device=device, dtype=torch.float32)
+    poses_host = torch.as_tensor(poses).detach().to(device="cpu", dtype=torch.float32)   # the camera travels as kernel arguments
+    poses_dev, torso_host = f32(poses), torch.as_tensor(torso_pose).detach().to(device="cpu", dtype=torch.float32)
+    bc_img, expr, latent_code = f32(bc_img), f32(expr), f32(latent_code)
+    H, W = int(bc_img.shape[0]), int(bc_img.shape[1])
+    with torch.no_grad():
+        aud_smo = clip_audio_features(network.aud_net, network.aud_att_net, f32(auds), network.args.smo_size)
+    kw = dict(H=H, W=W, focal=network.focal, chunk=network.args.chunk, near=network.near, far=network.far, bc_rgb=bc_img)
+    head = {"coarse": network.face_nerf_coarse, "fine": network.face_nerf_fine}
+    torso = {"coarse": network.torso_coarse_nerf, "fine": network.torso_fine_nerf}
+
+    def pairs(j):
+        signal = network.torso_signal(aud_smo[j], poses_dev[j])
+        rgb, _, _, _, _, _ = network.render_pair(expr=expr, latent_code=latent_code, aud_para=aud_smo[j],
+                                                 render_poses=poses_host[j][:3, :4], network_nerf=head, **kw)
+        _, _, _, last_w, rgb_fg, _ = network.render_pair(expr=None, latent_code=None, aud_para=signal,
+                                                         render_poses=torso_host[:3, :4], network_nerf=torso, **kw)
+        return rgb, last_w, rgb_fg
+
+    return pairs
+
+
 def render_torso_clip(network, poses, auds, bc_img, path, *, expr, latent_code, torso_pose, aud_ids=None, frames=None,
                       seed=None, fps=25, codec="MJPG", swap_rb=False, still_every=0, still_path=None, group=None):
     """The head + torso clip loop for a ``train_torso.Network``.  poses [F, >=3, 4], auds [F, 16, 29] (the clip's
@@ -127,23 +161,10 @@ def render_torso_clip(network, poses, auds, bc_img, path, *, expr, latent_code, 
     n_clip = int(poses.shape[0])
     frames = list(range(n_clip) if frames is None else frames)
     aud_ids = list(range(n_clip) if aud_ids is None else aud_ids)
-    f32 = lambda t: torch.as_tensor(t).to(device=device, dtype=torch.float32)
-    poses_host = torch.as_tensor(poses).detach().to(device="cpu", dtype=torch.float32)   # the camera travels as kernel arguments
-    poses_dev, torso_host = f32(poses), torch.as_tensor(torso_pose).detach().to(device="cpu", dtype=torch.float32)
-    bc_img, expr, latent_code = f32(bc_img), f32(expr), f32(latent_code)
-    H, W = int(bc_img.shape[0]), int(bc_img.shape[1])
-    with torch.no_grad():
-        aud_smo = clip_audio_features(network.aud_net, network.aud_att_net, f32(auds), network.args.smo_size)
-    kw = dict(H=H, W=W, focal=network.focal, chunk=network.args.chunk, near=network.near, far=network.far, bc_rgb=bc_img)
-    head = {"coarse": network.face_nerf_coarse, "fine": network.face_nerf_fine}
-    torso = {"coarse": network.torso_coarse_nerf, "fine": network.torso_fine_nerf}
+    pairs = _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose)
 
     def render_one(pos, j):
-        signal = network.torso_signal(aud_smo[j], poses_dev[j])
-        rgb, _, _, _, _, _ = network.render_pair(expr=expr, latent_code=latent_code, aud_para=aud_smo[j],
-                                                 render_poses=poses_host[j][:3, :4], network_nerf=head, **kw)
-        _, _, _, last_w, rgb_fg, _ = network.render_pair(expr=None, latent_code=None, aud_para=signal,
-                                                         render_poses=torso_host[:3, :4], network_nerf=torso, **kw)
+        rgb, last_w, rgb_fg = pairs(j)
         flag = torch.zeros(1, dtype=torch.int32, device=device)
         still = bool(still_every) and pos % still_every == 0
         out = ops.compose_to8b(rgb, last_w, rgb_fg, swap_rb, flag, want_fg=still)
@@ -156,3 +177,101 @@ def render_torso_clip(network, poses, auds, bc_img, path, *, expr, latent_code, 
     names = os.path.join(still_path, "{i}.jpg") if still_every and still_path else None
     return _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, still_every, names,
                 [aud_ids[j] for j in frames])
+
+
+def summarise_clip(table):
+    """Score table [n, 5, 4] (``ops.frame_scores`` rows, one per frame) -> dict(per_frame, mean, pooled):
+    per_frame  ``ops.summarise_scores(table)``: mse / psnr / ssim, [n, 5] each (groups: ops.SCORE_GROUPS);
+    mean       per group the mean over frames of psnr and of ssim, taken over the frames where the value is finite, with
+               ``n_excluded`` = how many frames that leaves out (a group absent from a frame, a perfect or a non-finite frame):
+               reported, never silently dropped;
+    pooled     mse / psnr / ssim of the table summed over frames (every pixel and window of the clip weighs the same)."""
+    import numpy as np
+    t = np.asarray(table.detach().cpu() if isinstance(table, torch.Tensor) else table, dtype=np.float64).reshape(-1, 5, 4)
+    per_frame = ops.summarise_scores(t)
+    mean = dict(n_excluded={})
+    for key in ("psnr", "ssim"):
+        ok = np.isfinite(per_frame[key])
+        kept = ok.sum(0)
+        with np.errstate(invalid="ignore"):
+            mean[key] = np.where(kept > 0, np.where(ok, per_frame[key], 0.0).sum(0) / np.maximum(kept, 1), np.nan)
+        mean["n_excluded"][key] = (t.shape[0] - kept).astype(np.int64)
+    return dict(per_frame=per_frame, mean=mean, pooled=ops.summarise_scores(t.sum(0)))
+
+
+def _score(frames, score_one, network, path, group, seed, fps, codec, swap_rb, device):
+    """What both scoring flows share around ``_run``: this rank's rows of the device table, the loop, the one gather, the
+    result.  score_one(frame, out_row, want_bytes) renders frame `frame`, scores it into out_row (float64 [5, 4], device) and
+    returns (u8 or None, flag or None)."""
+    rank, world = _ranks(group)
+    n = len(frames)
+    table = torch.zeros((len(frames_of(rank, world, n)), 5, 4), dtype=torch.float64, device=device)
+    write = path is not None
+    t0 = time.perf_counter()
+    done = _run(frames, lambda pos, frame: score_one(frame, table[pos // world], write), network, path, group, seed, fps, codec,
+                swap_rb, 0, None, None, write=write)
+    rows = gather_frame_rows(table, n, group)
+    if rows is None:
+        return None
+    rows = rows.cpu()             # the one device-to-host copy: 160 bytes per frame
+    seconds = time.perf_counter() - t0
+    bad = sorted(set(done["nonfinite_frames"]) | {int(i) for i in torch.nonzero(~torch.isfinite(rows[:, 0, 1])).reshape(-1)})
+    return dict(summarise_clip(rows), frames=list(frames), table=rows, n_frames=n, nonfinite_frames=bad, seconds=seconds,
+                frames_per_s=n / seconds if n else 0.0, world=world)
+
+
+def score_head_clip(network, frames, global_step, *, latent_code, frame_ids=None, path=None, seed=None, group=None, fps=25,
+                    codec="MJPG", swap_rb=False):
+    """``render_head_clip`` with the ground truth beside it.  ``frames`` is a val-mode ``dataset.ResidentFrames``: frame j of
+    ``frame_ids`` (default: all of them) comes from ``frames.frame(j)`` -- no file read, no host meshgrid -- goes through
+    ``network([data, global_step, frames.data_size])`` in eval mode under no_grad (the caller's mode is restored), and the float
+    render is scored on the device against ``frames.imgs[j]`` per region of ``frames.maps[j]`` (``ops.frame_scores``).  No
+    float frame leaves the device.  Frame-parallel like the render loops (``parallel.frames_of``; ``seed`` as there), with one
+    collective at the end of the clip (``parallel.gather_frame_rows``).
+
+    ``path=None``: nothing is converted to bytes and nothing is written.  With ``path`` the clip is also written, through the
+    same conversion, assembler and sink as ``render_head_clip``: the same file.
+
+    Returns on rank 0 (None on the other ranks) ``dict(frames, table, per_frame, mean, pooled, n_frames, nonfinite_frames,
+    seconds, frames_per_s, world)``: ``table`` float64 [n, 5, 4] on the host (rows ops.SCORE_GROUPS, columns
+    ops.SCORE_COLUMNS), per_frame / mean / pooled as ``summarise_clip``; nonfinite_frames: POSITIONS in the clip whose render
+    holds a NaN/Inf (their sums are not finite, so ``mean`` counts them in n_excluded); seconds: first render to the table
+    on the host."""
+    device = next(network.parameters()).device
+    ids = list(range(frames.data_size) if frame_ids is None else frame_ids)
+    ws = torch.empty(ops.frame_scores_workspace_doubles(frames.H, frames.W), dtype=torch.float64, device=device)
+
+    def score_one(j, row, want_bytes):
+        data = frames.frame(j)
+        rgb = network([(*data[:7], latent_code, data[7]), global_step, frames.data_size])[0]
+        ops.frame_scores(rgb, frames.imgs[j], frames.maps[j], out=row, workspace=ws)
+        if not want_bytes:
+            return None, None
+        flag = torch.zeros(1, dtype=torch.int32, device=device)
+        return ops.to8b(rgb, swap_rb, flag), flag
+
+    return _score(ids, score_one, network, path, group, seed, fps, codec, swap_rb, device)
+
+
+def score_torso_clip(network, poses, auds, bc_img, truth, *, regions=None, expr, latent_code, torso_pose, frames=None,
+                     path=None, seed=None, group=None, fps=25, codec="MJPG", swap_rb=False):
+    """``render_torso_clip`` with the ground truth beside it: truth uint8 [F, H, W, 3] and (optionally) regions uint8 [F, H, W]
+    (``dataset.region_byte_map``) on the device, indexed like poses.  Per frame the same two render pairs; what is scored is
+    the FLOAT composite ``rgb * last_weight[..., None] + rgb_fg`` -- a torch expression with one frame-sized temporary, since
+    the fused tail (``ops.compose_to8b``) keeps the composite in registers and hands out bytes only; with ``path`` the clip's
+    bytes still come from that fused tail, so the file is ``render_torso_clip``'s.  Everything else, and the return value, as
+    ``score_head_clip``."""
+    device = next(network.parameters()).device
+    ids = list(range(int(poses.shape[0])) if frames is None else frames)
+    pairs = _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose)
+    ws = torch.empty(ops.frame_scores_workspace_doubles(truth.shape[1], truth.shape[2]), dtype=torch.float64, device=device)
+
+    def score_one(j, row, want_bytes):
+        rgb, last_w, rgb_fg = pairs(j)
+        ops.frame_scores(rgb * last_w[..., None] + rgb_fg, truth[j], None if regions is None else regions[j], out=row, workspace=ws)
+        if not want_bytes:
+            return None, None
+        flag = torch.zeros(1, dtype=torch.int32, device=device)
+        return ops.compose_to8b(rgb, last_w, rgb_fg, swap_rb, flag), flag
+
+    return _score(ids, score_one, network, path, group, seed, fps, codec, swap_rb, device)

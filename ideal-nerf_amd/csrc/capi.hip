@@ -199,6 +199,18 @@ int idealnerf_gather_rays(const int64_t* sel, int64_t n, const float* c2w, int H
                               batch_rays, target_s, bc_rgb, (hipStream_t)stream);
 }
 
+size_t idealnerf_frame_scores_workspace_bytes(int H, int W) { return frame_scores_workspace_bytes(H, W); }
+
+int idealnerf_frame_scores(const float* pred, const uint8_t* truth, const uint8_t* regions, int H, int W, double* out,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (H <= 0 || W <= 0 || (int64_t)H * W > (1LL << 30)) return fail(IDN_EINVAL, "bad frame %d x %d", H, W);
+    if (!pred || !truth || !out) return fail(IDN_EINVAL, "NULL pointer (pred, truth or out)");
+    const size_t need = frame_scores_workspace_bytes(H, W);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7u))
+        return fail(IDN_EINVAL, "workspace of %zu bytes (need %zu, 8-byte aligned)", workspace_bytes, need);
+    return launch_frame_scores(pred, truth, regions, H, W, out, (double*)workspace, (hipStream_t)stream);
+}
+
 int idealnerf_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int lindisp, int64_t n_rays,
                             int n_samples, float* z, void* stream) {
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes");

@@ -233,6 +233,10 @@ int launch_sample_pixels(const unsigned char* map, int H, int W, const int count
 int launch_gather_rays(const long long* sel, int64_t n, const float* c2w_host, int H, int W, float focal, float cx, float cy,
                        const unsigned char* image, const unsigned char* background, const float* target_table,
                        const float* background_table, float* batch_rays, float* target_s, float* bc_rgb, hipStream_t s);
+// metrics.hip: squared error and SSIM of a frame against its uint8 ground truth, whole frame and per region -> out [5, 4] fp64
+size_t frame_scores_workspace_bytes(int H, int W);
+int launch_frame_scores(const float* pred, const unsigned char* truth, const unsigned char* regions, int H, int W, double* out,
+                        double* partial, hipStream_t s);
 int launch_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays, int S,
                          int lindisp, float* z, hipStream_t s, Draws draws = Draws{0, 0, 0});
 int launch_composite(const float* raw, const float* z, const float* rays, const float* bc, int64_t n_rays, int S,

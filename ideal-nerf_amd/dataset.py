@@ -150,6 +150,9 @@ class ResidentFrames:
     (``ops.sample_pixels``: a function of (frame, seed, draw) alone): two kernel launches, no host synchronisation, no
     device-to-host copy, no allocation beyond the three output tensors; no [H W, 11] ray tensor exists.
 
+    ``frame(index)`` is the validation side of the same object (``mode="val"``, ``skip=args.testskip``): the whole frame as the
+    8-tuple the eval forward takes, for ``clip.score_head_clip`` and ``train.train(val="resident")``.
+
     Raises ``ValueError`` at construction -- from the host-side populations, before anything is uploaded -- if the clip needs
     more than ``max_bytes`` of device memory or if a region of a frame holds fewer pixels than its share of ``N_rand`` (the step
     at which upstream's ``np.random.choice`` raises)."""
@@ -205,7 +208,11 @@ class ResidentFrames:
                 raise ValueError(f"{img_paths[i]} is {raw.shape}, the clip's cx / cy say {(self.H, self.W, 3)}")
             self.imgs[i].copy_(torch.from_numpy(raw))
         del maps
-        self.background = torch.from_numpy(np.array(_imread(os.path.join(data_dir, "bc.jpg")))).to(device)
+        background = np.array(_imread(os.path.join(data_dir, "bc.jpg")))
+        self.background = torch.from_numpy(background).to(device)
+        self.background_unit = torch.tensor(background / 255.0).to(device)   # float64, GetData's background_img: what frame() hands over
+        self._poses_host = [torch.from_numpy(np.ascontiguousarray(p)) for p in poses]   # float64 [3, 4] each, on the host
+        self._no_rays = torch.empty(0, dtype=torch.float32, device=device)
         self.auds = torch.tensor(np.asarray(auds), dtype=torch.float).to(device)
         self.poses = torch.tensor(np.asarray(poses), dtype=torch.float32).to(device)
         self.exprs = torch.tensor(np.asarray(exprs), dtype=torch.float32).to(device)
@@ -216,6 +223,18 @@ class ResidentFrames:
 
     def __len__(self):
         return self.data_size
+
+    def frame(self, index):
+        """The resident validation loader: frame ``index`` as the 8-tuple ``Network.forward`` takes in eval mode -- (batch_rays,
+        target_s, bg_img, auds, raw_img, pose, expr, index) with GetData(val)'s values in the fields the full-frame render reads:
+        the whole background as GetData keeps it (float64 ``uint8 / 255.0``, uploaded once), the clip's audio windows, the
+        ground-truth image (uint8, BGR), the expression and the index on the device, and the pose on the HOST (float64 [3, 4]:
+        the camera travels as kernel arguments, so the forward must not have to fetch it from the device).  batch_rays and
+        target_s, which the eval forward never reads, are empty.  No file is read, no host meshgrid is built, nothing is copied
+        from the device, nothing is allocated."""
+        index = int(index)
+        return (self._no_rays, self._no_rays, self.background_unit, self.auds, self.imgs[index], self._poses_host[index],
+                self.exprs[index], index)
 
     def select(self, index, draw):
         """The flat pixel indices of draw `draw` on frame `index` (int64 [N_rand]; the loader's own buffer, overwritten by

@@ -484,6 +484,58 @@ def audio_net_bwd(params, windows, saved, d_out, dim_aud):
     return grads
 
 
+SCORE_GROUPS = ("frame", "rect", "outside", "mouth", "torso")    # rows of a score table: the whole frame, then dataset.REGION_NAMES
+SCORE_COLUMNS = ("n_pixels", "sse", "n_windows", "ssim_sum")
+SCORE_TILE = _lib.SCORE_TILE                                      # edge of the pixel tile one workgroup scores
+
+
+def frame_scores_workspace_doubles(H, W) -> int:
+    return _lib.load().idealnerf_frame_scores_workspace_bytes(int(H), int(W)) // 8
+
+
+def frame_scores(pred, truth_u8, regions=None, out=None, workspace=None) -> torch.Tensor:
+    """Squared error and SSIM of a rendered frame against its ground truth (idealnerf_frame_scores): pred [H, W, 3] fp32,
+    truth_u8 [H, W, 3] uint8, regions [H, W] uint8 (``dataset.region_byte_map``) or None -> float64 [5, 4] on the device: rows
+    SCORE_GROUPS, columns SCORE_COLUMNS (``summarise_scores`` turns them into mse / psnr / ssim).  fp64 sums, no atomics: the
+    same inputs give the same 160 bytes.  `out` (float64 [5, 4], e.g. a row of a caller's table) and `workspace` (float64
+    [>= frame_scores_workspace_doubles(H, W)]): the caller's buffers, for a call that allocates nothing; nothing is read back."""
+    lib = _lib.load()
+    if pred.dim() != 3 or pred.shape[-1] != 3:
+        raise IdealNerfError(f"pred must be [H, W, 3], got {list(pred.shape)}")
+    H, W = int(pred.shape[0]), int(pred.shape[1])
+    _shape(truth_u8, "truth_u8", H, W, 3)
+    _shape(regions, "regions", H, W)
+    _shape(out, "out", 5, 4)
+    with _Launch(pred, truth_u8, regions, out, workspace) as L:
+        ptrs = (_ptr(pred, "pred"), _ptr(truth_u8, "truth_u8", torch.uint8), _ptr(regions, "regions", torch.uint8))
+        need = lib.idealnerf_frame_scores_workspace_bytes(H, W)
+        if out is None:
+            out = torch.empty((5, 4), dtype=torch.float64, device=pred.device)
+        if workspace is None:
+            workspace = torch.empty(need // 8, dtype=torch.float64, device=pred.device)
+        if workspace.numel() * 8 < need:
+            raise IdealNerfError(f"workspace must hold {need // 8} float64 for a {H} x {W} frame, got {workspace.numel()}")
+        check(lib.idealnerf_frame_scores(*ptrs, H, W, _ptr(out, "out", torch.float64), _ptr(workspace, "workspace", torch.float64),
+                                         workspace.numel() * 8, L.stream))
+    return out
+
+
+def summarise_scores(table):
+    """Score table(s) [..., 5, 4] (tensor or array; a device tensor is copied to the host here) -> dict of float64 arrays [..., 5]:
+    ``mse = sse / (3 n_pixels)``, ``psnr = -10 log10(mse)`` (helper.mse2psnr), ``ssim = ssim_sum / (3 n_windows)``.  A group
+    without pixels (windows) has mse and psnr (ssim) nan; mse == 0 gives psnr = inf."""
+    import numpy as np
+    t = np.asarray(table.detach().cpu() if isinstance(table, torch.Tensor) else table, dtype=np.float64)
+    if t.ndim < 2 or t.shape[-2:] != (5, 4):
+        raise ValueError(f"a score table is [..., 5, 4], got {list(t.shape)}")
+    n_pix, sse, n_win, ssim_sum = (t[..., c] for c in range(4))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse = np.where(n_pix > 0, sse / (3.0 * n_pix), np.nan)
+        psnr = -10.0 * np.log10(mse)
+        ssim = np.where(n_win > 0, ssim_sum / (3.0 * n_win), np.nan)
+    return dict(mse=mse, psnr=psnr, ssim=ssim)
+
+
 _workspaces: Dict[tuple, torch.Tensor] = {}
 
 

@@ -164,3 +164,29 @@ class ClipAssembler:
         # a device flag is read by the sink together with the frame's bytes: the sink knows those frames
         flagged = set(self._flagged) | {int(i) for i in getattr(self.sink, "nonfinite_frames", ())}
         return dict(n_frames=self.n_frames, nonfinite_frames=sorted(flagged))
+
+
+def gather_frame_rows(rows: torch.Tensor, n_frames: int, group=None) -> Optional[torch.Tensor]:
+    """The per-frame result rows of a frame-parallel loop back in frame order: every rank passes its
+    ``[len(frames_of(rank, world, n_frames)), ...]`` tensor (row k belongs to frame ``k * world + rank``) and rank 0 receives
+    ``[n_frames, ...]``, the other ranks None.  ONE ``dist.gather`` of equal payloads (a rank whose share is a frame short pads
+    a zero row, dropped again on rank 0): host tensors under gloo (a device tensor is copied to the host first -- these are
+    score rows, not frames), device tensors under RCCL.  Without an initialised process group, or with one rank, ``rows`` is
+    returned as it is."""
+    n_frames = int(n_frames)
+    on = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    mine = len(frames_of(rank, world, n_frames))
+    if rows.shape[0] != mine:
+        raise ValueError(f"rank {rank} of {world} holds {mine} of {n_frames} frames, got {rows.shape[0]} rows")
+    if not on:
+        return rows
+    device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    rounds = -(-n_frames // world)
+    payload = torch.zeros((rounds,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=device)
+    payload[:mine] = rows.to(device)
+    parts = [torch.empty_like(payload) for _ in range(world)] if rank == 0 else None
+    dist.gather(payload, parts, dst=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    if rank != 0:
+        return None
+    return torch.stack(parts, 1).reshape((rounds * world,) + tuple(rows.shape[1:]))[:n_frames]

@@ -77,7 +77,8 @@ def _summary_writer(logdir):
     return SummaryWriter(logdir)
 
 
-def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30):
+def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30,
+          val="reference"):
     """The reference's ``train()`` (audio_exp_nerf.py:451-593) on the flags ``args`` (``helper.config_parser().parse_args()``):
     write_config, the train and validation datasets, ``Network`` + ``init_weights``, ``latent_codes = ones[n_frames, 32]``, Adam,
     warm start from ``ft_path`` or resume from the newest ``*.tar`` of ``basedir/expname``, then epochs over the frames in
@@ -88,6 +89,12 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
              ``draw_index(global_step, rank, world)``;
     loader = "reference": ``dataset.GetData`` -- upstream's host-side loader and its numpy draw sequence.
 
+    val = "reference": the validation frame comes from ``dataset.GetData(val)`` (``validation_frame``);
+    val = "resident":  the validation clip is resident too (``dataset.ResidentFrames(mode="val")``): the same frame index from
+             the same generator, rendered from ``ResidentFrames.frame`` without a file read, and scored on the device
+             (``ops.frame_scores``) -- ``val/psnr`` and ``val/ssim`` are logged and ``on_log("val_scores", ...)`` is called beside
+             the image.  The scores are read at the validation moment only: one host sync every ``100 * i_print`` steps.
+
     Two departures from upstream, both so that a run resumed from ``head.tar`` continues exactly as the uninterrupted run
     would (with perturb = 0 and the resident loader: bit for bit): ``head.tar`` is written at upstream's moments but records
     the number of COMPLETED steps (upstream records the index of the step just done and so repeats that step after a resume),
@@ -95,7 +102,8 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     keeping ``global_step``).  ``steps``: stop after that many steps of THIS call (None: run ``N_iters + 1`` epochs).
 
     ``on_log(kind, global_step, payload)`` receives ("train", step, {loss, psnr, learning_rate, latent_code_loss}) and
-    ("val", step, image [3, 2 H, W] RGB: prediction over ground truth); ``on_step(global_step, info)`` runs after every step.
+    ("val", step, image [3, 2 H, W] RGB: prediction over ground truth) and, with val = "resident", ("val_scores", step,
+    {frame, groups, mse, psnr, ssim: one value per ops.SCORE_GROUPS}); ``on_step(global_step, info)`` runs after every step.
     Inside a process group every rank trains (``train_step`` all-reduces the gradients); rank 0 alone logs and saves.
     -> dict(network, optimizer, latent_codes, global_step, data_size)."""
     import numpy as np
@@ -106,6 +114,8 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
 
     if loader not in ("resident", "reference"):
         raise ValueError(f"loader must be 'resident' or 'reference', got {loader!r}")
+    if val not in ("reference", "resident"):
+        raise ValueError(f"val must be 'reference' or 'resident', got {val!r}")
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
     rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if dist_on else (0, 1)
     basedir, expname = args.basedir, args.expname
@@ -119,6 +129,10 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
         dataset_train = dataset.GetData(args.datadir, args.aud_file, mode="train", args=args, device=device)
     dataset_val = dataset.GetData(args.datadir, args.aud_file, mode="val", args=args, skip=args.testskip, device=device)
     logger.info(f'dataset_val length: {dataset_val.data_size}')
+    frames_val = None
+    if val == "resident" and rank == 0:
+        frames_val = dataset.ResidentFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device,
+                                            max_bytes=max_bytes, seed=sample_seed)
     data_size = dataset_train.data_size
     H, W, focal = dataset_val.H, dataset_val.W, dataset_val.focal
     intrinsic = np.array([[focal, 0., W / 2], [0, focal, H / 2], [0, 0, 1.]])
@@ -172,11 +186,19 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
                         on_log("train", global_step, scalars)
 
                 if global_step % (100 * args.i_print) == 0 and rank == 0:
-                    image = validation_frame(network, dataset_val, latent_codes, global_step, sample_seed)
+                    if frames_val is None:
+                        image, scores = validation_frame(network, dataset_val, latent_codes, global_step, sample_seed), None
+                    else:
+                        image, scores = resident_validation_frame(network, frames_val, latent_codes, global_step, sample_seed)
                     if writer is not None:
                         writer.add_image("val/rgb_fine", image, global_step=global_step)
+                        if scores is not None:
+                            writer.add_scalar("val/psnr", scores["psnr"][0], global_step=global_step)
+                            writer.add_scalar("val/ssim", scores["ssim"][0], global_step=global_step)
                     if on_log is not None:
                         on_log("val", global_step, image)
+                        if scores is not None:
+                            on_log("val_scores", global_step, scores)
                     logger.info('Saved test set and turn back to trainning mode')
 
                 if global_step % args.i_weights == 0 and rank == 0:
@@ -195,13 +217,17 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
 
 
+def _validation_index(n, global_step, sample_seed):
+    gen = torch.Generator().manual_seed((int(sample_seed) * 1000003 + int(global_step)) & (2 ** 63 - 1))
+    return int(torch.randint(n, (1,), generator=gen))
+
+
 def validation_frame(network, dataset_val, latent_codes, global_step, sample_seed=0):
     """audio_exp_nerf.py:568-581: one randomly chosen validation frame rendered in eval mode under no_grad with
     ``latent_codes[0]``, stacked over its ground truth, channels flipped to RGB -> [3, 2 H, W] on the host; the network
     goes back to train mode.  The frame is chosen by a generator of its own seeded from (sample_seed, global_step) --
     upstream shuffles its validation loader -- so a validation neither depends on nor disturbs the training draws."""
-    gen = torch.Generator().manual_seed((int(sample_seed) * 1000003 + int(global_step)) & (2 ** 63 - 1))
-    val_i = int(torch.randint(len(dataset_val), (1,), generator=gen))
+    val_i = _validation_index(len(dataset_val), global_step, sample_seed)
     network.eval()
     try:
         batch_rays, target_s, bg_img, auds, raw_img, pose, expr, index = _as_loader_item(dataset_val[val_i])
@@ -212,3 +238,25 @@ def validation_frame(network, dataset_val, latent_codes, global_step, sample_see
         network.train()
     pred_with_label = torch.cat((rgb.cpu().permute(2, 0, 1), raw_img.cpu().permute(2, 0, 1) / 255.0), dim=1)
     return pred_with_label[[2, 1, 0], :, :]
+
+
+def resident_validation_frame(network, frames_val, latent_codes, global_step, sample_seed=0):
+    """``validation_frame`` from a resident validation clip (``dataset.ResidentFrames(mode="val")``): the same frame index from
+    the same generator, the frame's inputs from ``frames_val.frame`` (no file read, no host meshgrid), and the render scored on
+    the device against the frame's ground truth, whole frame and per sampling region (``ops.frame_scores``) -> (image as
+    ``validation_frame``, dict(frame, groups, mse, psnr, ssim) with one float per ``ops.SCORE_GROUPS``; nan where a group has no
+    pixel or window).  The scores are read back here, together with the image: the validation moment's one host sync."""
+    from . import ops
+    val_i = _validation_index(len(frames_val), global_step, sample_seed)
+    network.eval()
+    try:
+        data = frames_val.frame(val_i)
+        with torch.no_grad():
+            rgb, _, _, _, _ = network([(*data[:7], latent_codes[0], data[7]), global_step, frames_val.data_size])
+            table = ops.frame_scores(rgb, frames_val.imgs[val_i], frames_val.maps[val_i])
+    finally:
+        network.train()
+    raw_img = data[4]
+    pred_with_label = torch.cat((rgb.cpu().permute(2, 0, 1), raw_img.cpu().permute(2, 0, 1) / 255.0), dim=1)
+    scores = {k: [float(x) for x in v] for k, v in ops.summarise_scores(table).items()}
+    return pred_with_label[[2, 1, 0], :, :], dict(scores, frame=val_i, groups=list(ops.SCORE_GROUPS))

@@ -316,6 +316,33 @@ int idealnerf_gather_rays(const int64_t* sel, int64_t n, const float* c2w, int H
                           const uint8_t* image, const uint8_t* background, const float* target_table, const float* background_table,
                           float* batch_rays, float* target_s, float* bc_rgb, void* stream);
 
+/*
+ * Frame scores: how far a rendered frame is from its ground truth, on the device.  Additive entries: the ABI version is unchanged.
+ *
+ * pred [H, W, 3] fp32, truth [H, W, 3] uint8, regions [H, W] uint8 (the region byte map idealnerf_sample_pixels draws from: bit 0
+ * rect, 1 outside, 2 mouth, 3 torso) or NULL -> out [5, 4] float64.  Row 0 is the whole frame, rows 1..4 the pixels carrying bit
+ * 0..3 of the region byte (zero rows with regions == NULL).  Columns:
+ *   0 n_pixels   pixels of the group
+ *   1 sse        sum over those pixels and the 3 channels of (pred - t)^2 with t = float(truth) / 255.0f: the reference's
+ *                img2mse(rgb, target) times its element count (NeRFs/HeadNeRF/helper.py:150; target = uint8 / 255,
+ *                train/audio_exp_nerf.py:126), so that PSNR = mse2psnr(sse / (3 n_pixels)) = -10 log10(mse) (helper.py:151).
+ *                Difference and square in fp32, as the reference's; accumulation in fp64.
+ *   2 n_windows  SSIM windows whose CENTRE pixel is in the group
+ *   3 ssim_sum   sum over those windows and the 3 channels of the SSIM index (Wang et al. 2004): 11 x 11 Gaussian window, sigma
+ *                1.5, separable, its 11 weights normalised in fp64 and rounded to fp32; "valid" windows only, (H - 10) x (W - 10)
+ *                centres; data range 1, C1 = 1e-4, C2 = 9e-4; weighted biased variances E[x^2] - mu^2.  The window sums and the
+ *                index are evaluated in fp64 (E[x^2] - mu^2 cancels against C2: fp32 sums move a window by 3e-4).
+ *                H < 11 or W < 11: columns 2 and 3 are zero.
+ * Deterministic: per-workgroup partial sums in the workspace, added in index order by a final pass, no floating-point atomics --
+ * the same inputs give the same 160 bytes.  Nothing is read back to the host.  workspace:
+ * idealnerf_frame_scores_workspace_bytes(H, W) bytes (20 doubles per IDN_SCORE_TILE^2 tile of the frame), 8-byte aligned.
+ * H <= 0, W <= 0, a NULL pred / truth / out or a short workspace return IDN_EINVAL before any launch.
+ */
+#define IDN_SCORE_TILE 32 /* edge of the pixel tile one workgroup scores */
+size_t idealnerf_frame_scores_workspace_bytes(int H, int W);
+int idealnerf_frame_scores(const float* pred, const uint8_t* truth, const uint8_t* regions, int H, int W, double* out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 size_t idealnerf_render_workspace_bytes(int64_t n_rays, int n_samples, int n_importance);
 int idealnerf_render_rays_fwd(const idn_render_args* a, void* stream);
 

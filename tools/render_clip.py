@@ -48,8 +48,11 @@ def parse():
     return ap.parse_args()
 
 
-def launch(n, argv):
-    """N ranks as children of this process, which has not touched the GPU; rank 0's JSON line is relayed."""
+def launch(n, argv, script=None):
+    """N ranks as children of this process, which has not touched the GPU; rank 0's JSON line is relayed.
+    script: the file the ranks run (default: this one; tools/score_clip.py starts its ranks through here)."""
+    script = os.path.abspath(script or __file__)
+    name = os.path.basename(script)
     import signal
     import socket
     import subprocess
@@ -62,7 +65,7 @@ def launch(n, argv):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
+           "--master-port", str(port), script] + list(argv)
     child = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, start_new_session=True)
     try:
         out, _ = child.communicate(timeout=float(os.environ.get("IDN_LAUNCH_TIMEOUT_S", "1500")))
@@ -76,7 +79,7 @@ def launch(n, argv):
                 break
             except subprocess.TimeoutExpired:
                 continue
-        sys.stderr.write(f"render_clip.py: the {n}-rank run did not finish in time\n")
+        sys.stderr.write(f"{name}: the {n}-rank run did not finish in time\n")
         return 124
     line = None
     for ln in out.splitlines():
@@ -89,7 +92,7 @@ def launch(n, argv):
         else:
             sys.stderr.write(ln + "\n")
     if child.returncode != 0 or line is None:
-        sys.stderr.write(f"render_clip.py: the ranks failed (exit code {child.returncode}) or printed no result line\n")
+        sys.stderr.write(f"{name}: the ranks failed (exit code {child.returncode}) or printed no result line\n")
         return child.returncode or 1
     print(line, flush=True)
     return 0
