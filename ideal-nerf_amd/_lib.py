@@ -62,6 +62,10 @@ class Frame(C.Structure):
                 ("near_", C.c_float), ("far_", C.c_float), ("row0", C.c_int), ("nrows", C.c_int), ("rays_out", fp)]
 
 
+class RenderOpts(C.Structure):
+    _fields_ = [("colour_gate", C.c_int), ("gate_counters", fp)]
+
+
 ABI_VERSION = 4   # idealnerf_version(): 4 since idn_render_args carries `rng_mode / rng_seed / rng_ray0` (3: `fused_march`)
 
 # name -> (restype, argtypes); mirrors include/idealnerf.h one to one
@@ -98,6 +102,9 @@ PROTOTYPES = {
     "idealnerf_render_rays_fwd": (C.c_int, [C.POINTER(RenderArgs), fp]),
     "idealnerf_render_frame_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "idealnerf_render_frame_fwd": (C.c_int, [C.POINTER(RenderArgs), C.POINTER(Frame), fp]),
+    "idealnerf_render_rays_fwd_opts": (C.c_int, [C.POINTER(RenderArgs), C.POINTER(RenderOpts), fp]),
+    "idealnerf_render_frame_fwd_opts": (C.c_int, [C.POINTER(RenderArgs), C.POINTER(Frame), C.POINTER(RenderOpts), fp]),
+    "idealnerf_colour_gate_max_dist": (C.c_float, []),
     "idealnerf_audio_net_saved_floats": (C.c_size_t, [C.c_int]),
     "idealnerf_audio_net_fwd": (C.c_int, [C.POINTER(AudioNetParams), fp, C.c_int, fp, fp, fp]),
     "idealnerf_audio_net_bwd": (C.c_int, [C.POINTER(AudioNetParams), C.POINTER(AudioNetGrads), fp, fp, fp, C.c_int, fp]),

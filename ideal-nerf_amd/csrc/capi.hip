@@ -28,7 +28,7 @@ static int check_precision_train(int precision) {
 
 int launch_mlp(int precision, const float* packed, const float* folded, const float* x, const float* rays,
                const float* z, const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw,
-               hipStream_t s) {
+               hipStream_t s, int gate, int64_t* gate_counters) {
     if (n_points > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "n_points %lld exceeds 2^31-1 per launch", (long long)n_points);
     if ((rays || pts) && n_samples < 1) return fail(IDN_EINVAL, "n_samples < 1");
     if (precision == IDN_PREC_BF16X3)
@@ -39,7 +39,7 @@ int launch_mlp(int precision, const float* packed, const float* folded, const fl
         return launch_mlp_fp16x3(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s);
     if (precision == IDN_PREC_BF16X6)
         return launch_mlp_bf16x6(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s);
-    return launch_mlp_f32(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s);
+    return launch_mlp_f32(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, nullptr, 0, gate, gate_counters);
 }
 
 static int check_params(const idn_facenerf_params* p) {
@@ -465,8 +465,10 @@ size_t idealnerf_render_workspace_bytes(int64_t n_rays, int n_samples, int n_imp
     return carve(nullptr, n_rays, n_samples, n_importance).bytes;
 }
 
-static int render_impl(const idn_render_args* a, const idn_frame* frame, void* stream_);
-int idealnerf_render_rays_fwd(const idn_render_args* a, void* stream_) { return render_impl(a, nullptr, stream_); }
+static int render_impl(const idn_render_args* a, const idn_frame* frame, const idn_render_opts* opts, void* stream_);
+int idealnerf_render_rays_fwd(const idn_render_args* a, void* stream_) { return render_impl(a, nullptr, nullptr, stream_); }
+int idealnerf_render_rays_fwd_opts(const idn_render_args* a, const idn_render_opts* opts, void* stream_) { return render_impl(a, nullptr, opts, stream_); }
+float idealnerf_colour_gate_max_dist(void) { return kGateMaxDist; }
 
 static size_t frame_scratch_bytes(int64_t n_rays) {
     const int64_t c = n_rays < kRenderChunk ? n_rays : kRenderChunk;
@@ -476,16 +478,18 @@ size_t idealnerf_render_frame_workspace_bytes(int64_t n_rays, int n_samples, int
     const size_t base = idealnerf_render_workspace_bytes(n_rays, n_samples, n_importance);
     return base ? base + frame_scratch_bytes(n_rays) : 0;
 }
-int idealnerf_render_frame_fwd(const idn_render_args* a, const idn_frame* f, void* stream_) {
+int idealnerf_render_frame_fwd(const idn_render_args* a, const idn_frame* f, void* stream_) { return idealnerf_render_frame_fwd_opts(a, f, nullptr, stream_); }
+int idealnerf_render_frame_fwd_opts(const idn_render_args* a, const idn_frame* f, const idn_render_opts* opts, void* stream_) {
     if (!a || !f) return fail(IDN_EINVAL, "args / frame is NULL");
     if (a->rays) return fail(IDN_EINVAL, "frame mode derives the rays from the camera: args->rays must be NULL");
     if (f->H <= 0 || f->W <= 0 || f->row0 < 0 || f->nrows < 0 || f->row0 + f->nrows > f->H) return fail(IDN_EINVAL, "bad frame / rows");
     if (a->n_rays != (int64_t)f->nrows * f->W) return fail(IDN_EINVAL, "n_rays %lld != nrows * W = %lld", (long long)a->n_rays, (long long)f->nrows * f->W);
-    return render_impl(a, f, stream_);
+    return render_impl(a, f, opts, stream_);
 }
 
-static int render_impl(const idn_render_args* a, const idn_frame* frame, void* stream_) {
+static int render_impl(const idn_render_args* a, const idn_frame* frame, const idn_render_opts* opts, void* stream_) {
     if (!a) return fail(IDN_EINVAL, "args is NULL");
+    if (opts && opts->colour_gate != 0 && opts->colour_gate != 1) return fail(IDN_EINVAL, "colour_gate %d (1 = on, the default; 0 = off)", opts->colour_gate);
     if (int e = check_precision(a->precision)) return e;
     const int prec_fine = a->precision_fine_plus1 ? a->precision_fine_plus1 - 1 : a->precision;
     if (int e = check_precision(prec_fine)) return e;
@@ -511,6 +515,12 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, void* s
         if (S != 64 || Ni != 128) return fail(IDN_EUNSUPPORTED, "fused march: built for n_samples = 64, n_importance = 128 (got %d, %d)", S, Ni);
         if (a->noise_coarse || a->noise_fine) return fail(IDN_EUNSUPPORTED, "fused march: no density noise");
     }
+    // the colour gate (include/idealnerf.h: idn_render_opts), pass by pass: fp32 only, and neither where noise is added to sigma
+    // after the kernel nor where the raw colours themselves are asked for
+    const bool gate_on = !opts || opts->colour_gate;
+    const int gate_c = gate_on && a->precision == IDN_PREC_F32 && !a->noise_coarse && !a->tap_raw_coarse;
+    const int gate_f = gate_on && prec_fine == IDN_PREC_F32 && !a->noise_fine && !a->tap_raw_fine;
+    int64_t* const gate_counters = opts ? opts->gate_counters : nullptr;
     hipStream_t st = (hipStream_t)stream_;
     const RenderWs w = carve(reinterpret_cast<char*>(a->workspace), n, S, Ni);
 
@@ -536,7 +546,7 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, void* s
         const Draws draws{(unsigned long long)a->rng_seed, (long)(a->rng_ray0 + r0), a->rng_mode};   // this pass's rows of the draw table
         if (int e = launch_coarse_depths(rays, a->t_vals, off(a->t_rand, r0 * S), c, S, a->lindisp, w.z_c, st, draws)) return e;
         if (!a->fused_march)
-            if (int e = launch_mlp(a->precision, a->packed_coarse, a->folded_coarse, nullptr, rays, w.z_c, nullptr, nullptr, c * S, S, w.raw_c, st)) return e;
+            if (int e = launch_mlp(a->precision, a->packed_coarse, a->folded_coarse, nullptr, rays, w.z_c, nullptr, nullptr, c * S, S, w.raw_c, st, gate_c, gate_counters)) return e;
         idn_composite_out co = {};
         const bool fine = Ni > 0;
         co.rgb_map = off(fine ? a->rgb0 : a->rgb_map, r0 * 3);
@@ -579,7 +589,8 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, void* s
                                  off(a->tap_z_samples, r0 * Ni), off(a->tap_inds, r0 * Ni), off(a->tap_cdf, r0 * (S - 1)),
                                  w.z_f, off(a->z_std, r0), st, draws))
             return e;
-        if (int e = launch_mlp(prec_fine, a->packed_fine, a->folded_fine, nullptr, rays, w.z_f, nullptr, nullptr, c * Sf, Sf, w.raw_f, st)) return e;
+        if (int e = launch_mlp(prec_fine, a->packed_fine, a->folded_fine, nullptr, rays, w.z_f, nullptr, nullptr, c * Sf, Sf, w.raw_f, st, gate_f,
+                                 gate_counters ? gate_counters + 2 : nullptr)) return e;
         idn_composite_out fo = {};
         fo.rgb_map = off(a->rgb_map, r0 * 3);
         fo.disp_map = off(a->disp_map, r0);

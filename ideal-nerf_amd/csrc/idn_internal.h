@@ -104,6 +104,10 @@ static_assert(kBiasFloats == 3136, "bias table changed");
 // pass over the trunk output instead of a separate N=1 layer.
 constexpr int kSigmaChannel = 128;
 
+// Colour gate (mlp_common.h): the longest sample spacing dist = (z[s+1] - z[s]) * |rays_d| across which a sample with
+// sigma <= 0 is taken to have the weight exactly 0 (idealnerf_colour_gate_max_dist).
+constexpr float kGateMaxDist = 0.0125f;
+
 // ---------------------------------------------------------------------------
 // Training-mode activation slab: layer-major row-major matrices of p_pad rows each
 // (p_pad = n_points rounded up to 128; rows beyond n_points stay zero).
@@ -198,16 +202,18 @@ int launch_mlp_bf16x3(const float* packed, const float* folded, const float* x, 
 int launch_mlp_fp16x3(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                       const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s);
 // precision dispatch for the inference forward
+// gate (fp32 rays mode only; ignored by the other arithmetics): the colour-gated kernel; gate_counters: device int64 [2]
+// (tiles, skipped) it adds to, or null
 int launch_mlp(int precision, const float* packed, const float* folded, const float* x, const float* rays,
                const float* z, const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw,
-               hipStream_t s);
+               hipStream_t s, int gate = 0, int64_t* gate_counters = nullptr);
 int launch_fold(const idn_facenerf_params& p, const float* aud, const float* expr, const float* latent,
                 float* folded, hipStream_t s);
 // x != nullptr: pre-embedded rows [n_points, 90]; pts != nullptr: raw points [n_points,3] +
 // dirs[n_points/S, 3]; else rays[n_rays,11] + z[n_rays,S]
 int launch_mlp_f32(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                   float* acts = nullptr, int64_t p_pad = 0);
+                   float* acts = nullptr, int64_t p_pad = 0, int gate = 0, int64_t* gate_counters = nullptr);
 
 int launch_frame_rays(const float* c2w, int H, int W, float focal, float cx, float cy, float near_, float far_,
                       int row0, int nrows, float* rays_out, hipStream_t s);

@@ -343,6 +343,10 @@ struct MlpArgs {
     float* acts;        // training only: activation slab (act_off() matrices of p_pad rows), else null
     long p_pad;
 };
+// the colour-gated fp32 rays kernel's arguments (the other kernels' stay as they are)
+struct MlpGateArgs : MlpArgs {
+    unsigned long long* gate_counters;   // (tiles, skipped) this launch adds to, or null
+};
 
 // Raw inputs of one lane's point.  They are loaded one pass ahead (right after a slice opens in
 // the middle of the previous pass and "touched" after the next one, where the slice barrier's
@@ -350,6 +354,8 @@ struct MlpArgs {
 // round trip queued behind the weight pieces issued at the end of the pass before.
 struct PointIn {
     float f[10];  // kModeRays: o(3) d(3) viewdir(3) z   kModePts: p(3) viewdir(3)   kModeX: unused
+    float zn;     // colour gate only (load_gate_point): depth of the ray's next sample, the point's own at a ray's last one
+    int last;     //   "         : the point is the last sample of its ray
 };
 struct NoHook {
     __device__ __forceinline__ void operator()() const {}
@@ -374,6 +380,31 @@ __device__ __forceinline__ void load_point(const MlpArgs& a, long tile, int wave
 __device__ __forceinline__ void touch_point(PointIn& in) {
 #pragma unroll
     for (int i = 0; i < 10; ++i) asm volatile("" : "+v"(in.f[i]));
+}
+
+// ---------------------------------------------------------------------------
+// Colour gate (fp32 rays-mode inference): a sample's colour is not needed where raw2outputs gives it
+// the weight +0 whatever the colour is -- sigma <= 0 across a spacing so short that expf(-1e-6 dist) == 1 (march.h:
+// composite_ray) -- or replaces it by the background pixel (a ray's last sample).  kGateMaxDist (idn_internal.h): a correctly rounded expf
+// returns 1 down to -2^-25, i.e. up to dist = 2^-25 / 1e-6 = 0.0298; the constant leaves a factor 2.4 for the device expf
+// (tests/test_colour_gate_gpu.py checks the built compositing kernel on a dense grid up to it).
+// ---------------------------------------------------------------------------
+// the gate's extra inputs of the lane's point, loaded with (right after) load_point's
+__device__ __forceinline__ void load_gate_point(const MlpArgs& a, long tile, int wave, int m, PointIn& in) {
+    long P = tile * 128 + wave * 32 + m;
+    if (P >= a.n_points) P = a.n_points - 1;   // as load_point: a valid address; such a point is dead anyway
+    const unsigned ray = (unsigned)P / (unsigned)a.S;
+    in.last = ((unsigned)P - ray * (unsigned)a.S == (unsigned)a.S - 1u) ? 1 : 0;
+    in.zn = a.z[in.last ? P : P + 1];          // never past a ray's (and so the array's) end
+}
+__device__ __forceinline__ void touch_gate_point(PointIn& in) { asm volatile("" : "+v"(in.zn), "+v"(in.last)); }
+// dist of composite_ray (march.h:86,105-106), same operations in the same order; false for a NaN sigma or dist.
+// |dist|: depths that run backwards by more than the threshold give expf > 1 and a non-zero weight.
+__device__ __forceinline__ bool gate_point_dead(const PointIn& in, float sigma) {
+    const float dn = sqrtf((in.f[3] * in.f[3] + in.f[4] * in.f[4]) + in.f[5] * in.f[5]);
+    float dist = in.zn - in.f[9];
+    dist = dist * dn;
+    return in.last != 0 || (sigma <= 0.0f && fabsf(dist) <= kGateMaxDist);
 }
 // point and view direction of the lane (pts = rays_o + rays_d * z with product and sum rounded
 // separately, audio_exp_nerf.py:332; this code is built with -ffp-contract=off)
@@ -431,6 +462,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(float* first_row, in
 }
 
 constexpr int kMlpLds = kRingFrags * kFragBytes + kBiasFloats * 4;
+constexpr int kMlpLdsGate = kMlpLds + 16;             // + the colour gate's two flag words
 constexpr int kStagePitch = 33;                       // 32x32 transpose tile, conflict-free
 constexpr int kStageFloats = 32 * kStagePitch;
 constexpr int kMlpLdsTrain = kMlpLds + 4 * kStageFloats * 4;

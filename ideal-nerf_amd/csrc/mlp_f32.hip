@@ -95,8 +95,10 @@ struct SaveSide {
     }
 };
 
-template <int MODE, bool SAVE>
-__global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
+// GATE: the colour gate of the render's own rays-mode launches (mlp_f32_layers.h)
+template <int MODE, bool SAVE, bool GATE = false>
+__global__ __launch_bounds__(256, 1) void mlp_f32_kernel(std::conditional_t<GATE, MlpGateArgs, MlpArgs> a) {
+    static_assert(!GATE || (MODE == kModeRays && !SAVE), "the colour gate is built for the rays-mode inference pass");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;
     float* bias_s = reinterpret_cast<float*>(smem + kRingFrags * kFragBytes);
@@ -110,6 +112,10 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
     const int m = lane & 31, h = lane >> 5;
 
     for (int i = tid; i < kBiasFloats; i += 256) bias_s[i] = a.bias[i];
+    GateWord* gate_words = (GateWord*)(__attribute__((address_space(3))) char*)(smem + kMlpLds);   // GATE only: [2], alternating tile by tile
+    if constexpr (GATE)
+        if (tid < 2) gate_words[tid] = 0u;
+    int gate_par = 0;
     __syncthreads();  // the bias block is read (by other waves) before the first slice barrier
 
     WStream ws;
@@ -125,6 +131,7 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
 
     PointIn cur, nxt;   // raw inputs of this lane's point, loaded one pass ahead (mlp_common.h)
     load_point<MODE>(a, blockIdx.x, wave, m, cur);
+    if constexpr (GATE) load_gate_point(a, blockIdx.x, wave, m, cur);
     nxt = cur;
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long P = tile * 128 + wave * 32 + m;
@@ -183,7 +190,19 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
         }
 
         float rgb[3], sigma;
-        if constexpr (!SAVE) {
+        if constexpr (GATE) {
+            // as below, with the gate's inputs beside the point's; a point beyond n_points is dead
+            const bool skipped = f32_inference_pass<true>(
+                pe, pd, bias_s, bias_h, ws, fr,
+                [&]() { load_point<MODE>(a, tile + gridDim.x, wave, m, nxt); load_gate_point(a, tile + gridDim.x, wave, m, nxt); },
+                [&]() { touch_point(nxt); touch_gate_point(nxt); }, rgb, sigma,
+                [&](float sg) { return !valid || gate_point_dead(cur, sg); }, gate_words + gate_par, gate_words + (gate_par ^ 1));
+            gate_par ^= 1;
+            if (a.gate_counters && tid == 0) {
+                atomicAdd(a.gate_counters + 0, 1ull);
+                if (skipped) atomicAdd(a.gate_counters + 1, 1ull);
+            }
+        } else if constexpr (!SAVE) {
             // the next tile's point inputs: loaded after pts_linears.5's first slice opens, touched one layer later
             f32_inference_pass(pe, pd, bias_s, bias_h, ws, fr,
                                [&]() { if constexpr (MODE != kModeX) load_point<MODE>(a, tile + gridDim.x, wave, m, nxt); },
@@ -348,13 +367,15 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(MlpArgs a) {
 
 int launch_mlp_f32(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                   float* acts, int64_t p_pad) {
+                   float* acts, int64_t p_pad, int gate, int64_t* gate_counters) {
     if (n_points <= 0) return IDN_OK;
     static LaunchSetup setup;
     int num_cu = 0;
     if (int e = setup.get([]() -> int {
             IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeRays, false>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
+            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeRays, false, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsGate));
             IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeX, false>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
             IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModePts, false>),
@@ -368,6 +389,7 @@ int launch_mlp_f32(const float* packed, const float* folded, const float* x, con
         return e;
     const int64_t ntiles = (n_points + 127) / 128;
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
+    if (gate && (acts || x || pts)) return fail(IDN_EUNSUPPORTED, "the colour gate is built for the rays-mode inference launch");
     MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad};
     ProfScope prof(s, n_points, acts ? IDN_PROF_MLP_FWD_SAVE : IDN_PROF_MLP_FWD);
     if (acts) {
@@ -380,6 +402,12 @@ int launch_mlp_f32(const float* packed, const float* folded, const float* x, con
         hipLaunchKernelGGL((mlp_f32_kernel<kModeX, false>), dim3(grid), dim3(256), kMlpLds, s, a);
     else if (pts)
         hipLaunchKernelGGL((mlp_f32_kernel<kModePts, false>), dim3(grid), dim3(256), kMlpLds, s, a);
+    else if (gate) {
+        MlpGateArgs ga;
+        static_cast<MlpArgs&>(ga) = a;
+        ga.gate_counters = reinterpret_cast<unsigned long long*>(gate_counters);
+        hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, false, true>), dim3(grid), dim3(256), kMlpLdsGate, s, ga);
+    }
     else
         hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, false>), dim3(grid), dim3(256), kMlpLds, s, a);
     IDN_HIP_CHECK(hipGetLastError());

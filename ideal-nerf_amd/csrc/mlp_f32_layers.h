@@ -21,13 +21,15 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // would retire that read, the compiler would treat its destination registers as dead and
 // reuse them (e.g. as a global address) while the LDS data is still on its way
 // (tools/audit_asm_loads.py checks the ISA for this).
-template <int F0, int NT, int KG, bool LAST = false, class BGet, class Side, class Hook = NoHook, class WS = WStream>
+// OPENED: the caller has opened the slice F0 starts (the colour gate decides at that barrier).
+template <int F0, int NT, int KG, bool LAST = false, bool OPENED = false, class BGet, class Side, class Hook = NoHook, class WS = WStream>
 __device__ __forceinline__ void run_layer(f32x16 (&out)[NT], BGet&& bget, WS& ws, FragReader& fr, Side&& side,
                                           Hook&& after_open = NoHook{}) {
     constexpr int STEPS = KG / 2, NP = NT * STEPS;
     static_assert(KG % 2 == 0 && F0 % 2 == 0, "fragments are consumed in pairs");
+    static_assert(!OPENED || F0 % kSliceFrags == 0, "only a layer that starts a slice can find it opened");
     if constexpr (F0 % kSliceFrags == 0) {
-        ws.open_slice();
+        if constexpr (!OPENED) ws.open_slice();
         after_open();   // global loads issued here have a whole slice to land before the next barrier's vmcnt(0)
         fr.pref0 = fr.template issue<F0>();
         fr.pref1 = fr.template issue<F0 + 1>();
@@ -101,10 +103,24 @@ struct LayerSide {
 // shadows (LayerSide), the last tile's ReLU owed to the next layer -- and read by the next.  after_open5 / after_open6 run
 // right after the first slice of pts_linears.5 / .6 opens (the next pass's point inputs are loaded there and touched one
 // layer later: a whole slice to land before the next barrier's vmcnt(0)).  -> raw rgb (3) and sigma of the lane's point.
-template <class WS, class Hook5, class Hook6>
-__device__ __forceinline__ void f32_inference_pass(const float (&pe)[8][4], const float (&pd)[4][4], const float* bias_s, const float* bias_h,
+//
+// GATE (colour gate): the trunk ends on a slice boundary, and the barrier that opens views_linears.0's
+// first slice is where the workgroup decides whether any of its 128 points needs a colour.  Before it: the ReLU owed to the
+// trunk's last tile, sigma (the same dot product, moved up), dead(sigma) per lane, and a wave with a live lane sets the LDS
+// word *gate_mine; thread 0 clears *gate_next, the word of the NEXT pass (the caller alternates two words: one is cleared a
+// whole pass after its last reader and a barrier before its next writer).  After it every wave reads the word.  Live: the
+// colour branch as ever.  All dead: rgb = 0 and the stream is re-armed for the next pass -- this wave's pieces of the opened
+// slice have landed (the open's vmcnt), a wave overwrites only its own quarter of slot 0, and the decision is workgroup-uniform,
+// so nobody reads slot 0 before the next pass opens it.  Both ways leave slice 0 in flight and next_slice == 1.  -> skipped?
+typedef volatile __attribute__((address_space(3))) uint32_t GateWord;   // an LDS word, addressed as one (ds_write / ds_read)
+struct NoGate {
+    __device__ __forceinline__ bool operator()(float) const { return false; }
+};
+template <bool GATE = false, class WS, class Hook5, class Hook6, class Dead = NoGate>
+__device__ __forceinline__ bool f32_inference_pass(const float (&pe)[8][4], const float (&pd)[4][4], const float* bias_s, const float* bias_h,
                                                    WS& ws, FragReader& fr, Hook5&& after_open5, Hook6&& after_open6, float (&rgb)[3],
-                                                   float& sigma) {
+                                                   float& sigma, Dead&& dead = NoGate{}, GateWord* gate_mine = nullptr,
+                                                   GateWord* gate_next = nullptr) {
     f32x16 A[8], B[8], V[5];
     auto pe_get = [&](auto G, auto J) { return pe[decltype(G)::value][decltype(J)::value]; };
     auto tiles_get = [](f32x16* arr) {
@@ -125,7 +141,7 @@ __device__ __forceinline__ void f32_inference_pass(const float (&pe)[8][4], cons
             if constexpr (F0 == layer_f0(6)) after_open6();
         };
         bias_tile(out[0], bias_l);
-        run_layer<F0, NT, KG, LAST>(out, bget, ws, fr, LayerSide<NT, KG / 2, DEFER>{&out[0], deferred, bias_l}, hook);
+        run_layer<F0, NT, KG, LAST, GATE && F0 == layer_f0(8)>(out, bget, ws, fr, LayerSide<NT, KG / 2, DEFER>{&out[0], deferred, bias_l}, hook);
     };
     // ---- pts_linears.0 : PE(64) -> 256
     layer(ic<layer_f0(0)>{}, ic<8>{}, ic<8>{}, ic<0>{}, A, nullptr, pe_get, bias_h + bias_off(0));
@@ -150,7 +166,40 @@ __device__ __forceinline__ void f32_inference_pass(const float (&pe)[8][4], cons
     //      (the bf16 kernels use it); here its 36 fragments are walked without being read, and sigma is a
     //      256-term dot product on the vector unit: 128 FMAs per lane against 144 MFMAs (one row of 32 used).
     f32x16(&V4a)[4] = reinterpret_cast<f32x16(&)[4]>(V);
-    layer(ic<layer_f0(8)>{}, ic<4>{}, ic<36>{}, ic<1>{}, V4a, &B[7],
+    if constexpr (GATE) {
+        static_assert(layer_f0(8) % kSliceFrags == 0 && (layer_f0(8) / kSliceFrags) % kRingSlots == 0 && kNumSlices % kRingSlots == 0,
+                      "the gate decides where slot 0 opens: a skipped pass refills that slot with slice 0");
+        relu_regs<0, 16>(B[7]);   // owed by pts_linears.7: views_linears.0 runs without a deferred tile
+        {   // sigma, moved up: the same dot product on the same values (below), so its bits do not move
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            static_for<8>([&](auto T) {
+                constexpr int t = decltype(T)::value;
+                static_for<4>([&](auto Q) {
+                    constexpr int q = decltype(Q)::value;
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(bias_h + kAlphaOff + 32 * t + 8 * q);
+                    s0 = fmaf(w.x, B[t][4 * q + 0], s0);
+                    s1 = fmaf(w.y, B[t][4 * q + 1], s1);
+                    s2 = fmaf(w.z, B[t][4 * q + 2], s2);
+                    s3 = fmaf(w.w, B[t][4 * q + 3], s3);
+                });
+            });
+            const float part = (s0 + s1) + (s2 + s3);
+            sigma = bias_s[bias_off(8) + kSigmaChannel] + (part + __shfl_xor(part, 32, 64));
+        }
+        const bool any_live = __builtin_amdgcn_ballot_w64(!dead(sigma)) != 0;
+        if (any_live && (threadIdx.x & 63) == 0) *gate_mine = 1u;
+        if (threadIdx.x == 0) *gate_next = 0u;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // open_slice waits for vector memory only
+        ws.open_slice();
+        if (__builtin_amdgcn_readfirstlane(*gate_mine) == 0u) {
+            rgb[0] = rgb[1] = rgb[2] = 0.0f;
+            ws.next_slice = 0;
+            ws.soff = 0;
+            ws.template issue_rest<0, 0>();
+            return true;
+        }
+    }
+    layer(ic<layer_f0(8)>{}, ic<4>{}, ic<36>{}, ic<GATE ? 0 : 1>{}, V4a, GATE ? nullptr : &B[7],
           [&](auto G, auto J) {
               constexpr int g = decltype(G)::value, j = decltype(J)::value;
               if constexpr (g < 32) return B[g >> 2][(g & 3) * 4 + j];
@@ -165,6 +214,7 @@ __device__ __forceinline__ void f32_inference_pass(const float (&pe)[8][4], cons
         fr.pref0 = fr.template issue<f_to>();
         fr.pref1 = fr.template issue<f_to + 1>();
     }
+    if constexpr (!GATE)
     {
         // B holds h7 (post-ReLU; its last tile was finished inside the layer above): this lane has the
         // channels 32t + 8q + 4h + i, the weights sit in LDS in the same order as a bias row
@@ -220,6 +270,7 @@ __device__ __forceinline__ void f32_inference_pass(const float (&pe)[8][4], cons
             rgb[c] += part[c] + __shfl_xor(part[c], 32, 64);
         });
     }
+    return false;
 }
 
 }  // namespace idn

@@ -569,6 +569,10 @@ def _fused_code(fused, where) -> int:
 FUSED_MARCH_DEFAULT = _fused_code(os.environ.get("IDN_FUSED_MARCH", "0") or "0", "IDN_FUSED_MARCH")
 
 
+# read once: whether the fp32 kernel sequence launches its colour-gated network kernels where `colour_gate` is not given
+COLOUR_GATE_DEFAULT = (os.environ.get("IDN_COLOUR_GATE", "1") or "1").strip() != "0"
+
+
 def make_frame(c2w, H, W, focal, near, far, row0=0, nrows=None, cx=None, cy=None):
     """The camera of a full-frame render (idn_frame): rays of rows [row0, row0 + nrows) are derived on the device."""
     nrows = H - row0 if nrows is None else nrows
@@ -687,7 +691,8 @@ def gather_rays(sel, c2w, H, W, focal, image, background, cx=None, cy=None):
 
 def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals, u, n_importance,
                     t_rand=None, with_fg=False, taps=False, precision=IDN_PREC_F32, precision_fine=None, lindisp=False,
-                    white_bkgd=False, noise_coarse=None, noise_fine=None, fused=None, frame=None, draws=None) -> Dict[str, torch.Tensor]:
+                    white_bkgd=False, noise_coarse=None, noise_fine=None, fused=None, frame=None, draws=None,
+                    colour_gate=None, gate_counters=None) -> Dict[str, torch.Tensor]:
     """Network.render_rays forward (audio_exp_nerf.py:297-371) as one C call.  `precision_fine` (default: the
     same as `precision`) selects the fine network's arithmetic; packed_f must be packed for it.
     `fused`: the arrangement of the kernels (same results bit for bit).  False / 0: the kernel sequence
@@ -700,8 +705,14 @@ def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals
     `frame` (ops.make_frame) with `rays=None`: full-frame mode (idealnerf_render_frame_fwd) -- the ray records of the frame's
     row band are derived on the device pass by pass; with `taps` they come back as `tap_rays`.
     `draws=(seed, ray0)` with `u=None, t_rand=None`: the perturb > 0 draws are made inside the kernels (rng_mode 1 of
-    idn_render_args), ray r using row ray0 + r of the table `philox_uniform` writes out -- no [n, S] / [n, Ni] random tensors."""
+    idn_render_args), ray r using row ray0 + r of the table `philox_uniform` writes out -- no [n, S] / [n, Ni] random tensors.
+    `colour_gate` (idn_render_opts): the fp32 kernel sequence skips the colour branch of every 128-point tile whose colours
+    cannot reach a pixel (same results bit for bit; off wherever noise or a raw tap is given).  None: IDN_COLOUR_GATE (1 / 0,
+    read once, default 1).  `gate_counters`: int64 [2, 2] on the device, (coarse, fine) x (tiles, skipped); the gated launches
+    add to it."""
     lib = _lib.load()
+    if gate_counters is not None:
+        _shape(gate_counters, "gate_counters", 2, 2)
     if draws is not None and (u is not None or t_rand is not None):
         raise IdealNerfError("draws=(seed, ray0) replaces BOTH t_rand and u: pass them as None")
     _shape(t_vals, "t_vals", None)
@@ -725,8 +736,11 @@ def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals
             _u_shape(u, n, Ni)
         _net_buffers(lib, packed_f, folded_f, precision if precision_fine is None else precision_fine, "_fine")
     dev = bc_rgb.device
-    with _Launch(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals, u, t_rand, noise_coarse, noise_fine) as L:
+    with _Launch(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals, u, t_rand, noise_coarse, noise_fine, gate_counters) as L:
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        opts = _lib.RenderOpts()
+        opts.colour_gate = int(COLOUR_GATE_DEFAULT if colour_gate is None else bool(colour_gate))
+        opts.gate_counters = _ptr(gate_counters, "gate_counters", torch.int64)
         out = dict(rgb_map=new(n, 3), disp_map=new(n), acc_map=new(n))
         if Ni > 0:
             out.update(rgb0=new(n, 3), disp0=new(n), acc0=new(n), z_std=new(n), last_weight=new(n))
@@ -764,14 +778,14 @@ def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals
             nbytes = lib.idealnerf_render_workspace_bytes(n, S, Ni)
             ws = _workspace(nbytes, dev, L.stream or 0)
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            check(lib.idealnerf_render_rays_fwd(C.byref(a), L.stream))
+            check(lib.idealnerf_render_rays_fwd_opts(C.byref(a), C.byref(opts), L.stream))
         else:
             tap_rays = new(n, RAY_FLOATS) if taps else None
             frame.rays_out = None if tap_rays is None else tap_rays.data_ptr()
             nbytes = lib.idealnerf_render_frame_workspace_bytes(n, S, Ni)
             ws = _workspace(nbytes, dev, L.stream or 0)
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            check(lib.idealnerf_render_frame_fwd(C.byref(a), C.byref(frame), L.stream))
+            check(lib.idealnerf_render_frame_fwd_opts(C.byref(a), C.byref(frame), C.byref(opts), L.stream))
             frame.rays_out = None
             if tap_rays is not None:
                 out["tap_rays"] = tap_rays

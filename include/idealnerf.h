@@ -367,6 +367,31 @@ typedef struct idn_frame {
 size_t idealnerf_render_frame_workspace_bytes(int64_t n_rays, int n_samples, int n_importance);
 int idealnerf_render_frame_fwd(const idn_render_args* a, const idn_frame* frame, void* stream);
 
+/*
+ * The two render entries with options.  Additive entries: idn_render_args and the ABI version are unchanged, and the
+ * entries above are these with opts == NULL (the defaults).
+ *
+ * colour_gate (default 1): the fp32 kernel sequence (fused_march == 0) launches its coarse and fine network kernels in a
+ * form that skips the colour branch (views_linears.*, rgb_linear: 12.4 % of a pass) for every 128-point tile in which NO
+ * point's colour can reach a pixel, and writes the raw colour 0.0f for it.  A point's colour cannot when the point is the
+ * last sample of its ray (raw2outputs replaces its colour by the background pixel), or when its sigma <= 0 and its
+ * spacing |z[s+1] - z[s]| * |rays_d| <= idealnerf_colour_gate_max_dist(): then alpha = 1 - expf(-1e-6 * dist) is exactly 0,
+ * so is the weight, and weight * colour is +0 whatever the colour.  Sigma is computed as ever.  Every output of the render
+ * is bit-identical to the ungated run; the one exception is a zero-weight sample whose colour branch ALONE overflows to
+ * NaN / inf while its sigma is finite and <= 0 -- ungated that NaN reaches the pixel as 0 * NaN, gated it does not.
+ * The gate is off (the ungated kernel is launched) for a pass whose density noise (noise_coarse / noise_fine) or raw tap
+ * (tap_raw_coarse / tap_raw_fine) is given, for every arithmetic but IDN_PREC_F32, and in the fused arrangements.
+ * gate_counters (may be NULL): device int64 [2][2] = (coarse, fine) x (tiles, skipped); the gated launches ADD their tile
+ * counts to it (the caller zeroes it); a pass that ran ungated adds nothing.
+ */
+typedef struct idn_render_opts {
+    int colour_gate;        /* 1 default, 0 off */
+    int64_t* gate_counters; /* device, [2][2], or NULL */
+} idn_render_opts;
+int idealnerf_render_rays_fwd_opts(const idn_render_args* a, const idn_render_opts* opts, void* stream);
+int idealnerf_render_frame_fwd_opts(const idn_render_args* a, const idn_frame* frame, const idn_render_opts* opts, void* stream);
+float idealnerf_colour_gate_max_dist(void);
+
 /* ------------------------------------------------------------------------------------------
  * Training step (NeRFs/HeadNeRF/train/audio_exp_nerf.py:534-552).  The forward of a pass is
  * idealnerf_coarse_depths / _query_rays_train_fwd / _composite_fwd / _sample_pdf_fwd; the
