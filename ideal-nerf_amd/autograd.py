@@ -11,22 +11,17 @@ exactly as upstream (:345); ``expr`` is data.
 ``FaceNeRFFn`` is the same machinery for ``FaceNeRF.forward`` on pre-embedded rows (models/face_nerf.py:40-80): the
 activation-saving forward in the rows' mode, and a backward seeded by dL/d out that also returns d x and d expr.
 """
-import ctypes as C
 import os
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
-from ._lib import IDN_PREC_F32, check
 from .helper import linspace01
 
 PARAM_KEYS = ([f"pts_linears.{i}.{k}" for i in range(8) for k in ("weight", "bias")] +
               [f"views_linears.{i}.{k}" for i in range(3) for k in ("weight", "bias")] +
               ["alpha_linear.weight", "alpha_linear.bias", "rgb_linear.weight", "rgb_linear.bias"])
-
-_grads_struct = ops.grads_struct
-
 
 # Arithmetic of the training forward: "bf16x6" (six bf16 piece products per fp32 product, weights and activations as
 # three bf16 pieces: fp32-grade, 1.6x the fp32 pipe) or "f32" (fp32 MFMA).  The backward's pipes are a property of the
@@ -34,47 +29,22 @@ _grads_struct = ops.grads_struct
 TRAIN_PRECISION = os.environ.get("IDN_TRAIN_PRECISION", "bf16x6")
 
 
-def _train_query(net, folded, rays, z):
-    lib = _lib.load()
-    ops._shape(z, "z", None, None)
-    n, S = z.shape
-    ops._shape(rays, "rays", n, ops.RAY_FLOATS)
+def _train_code():
     if TRAIN_PRECISION not in ("f32", "bf16x6"):
         raise _lib.IdealNerfError(f"IDN_TRAIN_PRECISION must be f32 or bf16x6 (got {TRAIN_PRECISION!r})")
-    packed = net.packed_weights(TRAIN_PRECISION)
-    code = _lib.IDN_PREC_F32 if TRAIN_PRECISION == "f32" else _lib.IDN_PREC_BF16X6
-    with ops._Launch(packed, folded, rays, z) as L:
-        raw = torch.empty((n, S, 4), dtype=torch.float32, device=z.device)
-        acts = torch.empty(lib.idealnerf_train_acts_floats(n * S), dtype=torch.float32, device=z.device)
-        check(lib.idealnerf_query_rays_train_fwd(ops._ptr(packed, "packed"), ops._ptr(folded, "folded"), code,
-                                                 ops._ptr(rays, "rays"), ops._ptr(z, "z"), n, S, raw.data_ptr(),
-                                                 acts.data_ptr(), L.stream))
-    return raw, acts
+    return TRAIN_PRECISION, (_lib.IDN_PREC_F32 if TRAIN_PRECISION == "f32" else _lib.IDN_PREC_BF16X6)
+
+
+def _train_query(net, folded, rays, z):
+    prec_name, code = _train_code()
+    return ops.query_rays_train_fwd(net.packed_weights(prec_name), folded, rays, z, code)
 
 
 def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
-    lib = _lib.load()
-    n, S = z.shape
     sd = dict(net.named_parameters())
+    # (no column stays uninitialised: the fold kernel writes all conditioning columns, the GEMM reductions all others)
     grads = {k: torch.empty_like(sd[k]) for k in PARAM_KEYS}
-    # columns the kernels never address (none today) would stay uninitialised: the fold
-    # kernel writes all conditioning columns, the GEMM reductions all others.
-    ps = net.kernel_params()
-    gs = _grads_struct(grads)
-    nbytes = lib.idealnerf_pass_bwd_workspace_bytes(n, S)
-    for t, name, shape in ((raw, "raw", (n, S, 4)), (rays, "rays", (n, ops.RAY_FLOATS)), (bc, "bc_rgb", (n, 3)),
-                           (g_rgb, "g_rgb_map", (n, 3)), (g_fg, "g_rgb_fg", (n, 3)), (g_lw, "g_last_weight", (n,)),
-                           (g_acc, "g_acc", (n,))):
-        ops._shape(t, name, *shape)
-    ptr = ops._ptr
-    with ops._Launch(aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent,
-                     *grads.values()) as L:
-        ws = ops._workspace(nbytes, z.device, L.stream)   # scratch of this (device, stream): two streams training on one GPU do not share it
-        check(lib.idealnerf_pass_bwd(C.byref(ps), C.byref(gs), ptr(aud), ptr(expr), ptr(latent), ptr(acts),
-                                     ptr(raw), ptr(z), ptr(rays), ptr(bc), n, S, ptr(g_rgb),
-                                     ptr(g_fg), ptr(g_lw), ptr(g_acc), ptr(d_aud), ptr(d_latent), ws.data_ptr(),
-                                     ws.numel(), L.stream))
-    return grads
+    return ops.pass_bwd(net.kernel_params(), grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
 
 
 class RenderRaysFn(torch.autograd.Function):
@@ -169,12 +139,6 @@ def render_rays_apply(network, coarse, fine, rays, bc_rgb, aud_para, latent_code
     elif with_fg:
         ret['rgb_map_fg'] = outs[3]
     return ret
-
-
-def _train_code():
-    if TRAIN_PRECISION not in ("f32", "bf16x6"):
-        raise _lib.IdealNerfError(f"IDN_TRAIN_PRECISION must be f32 or bf16x6 (got {TRAIN_PRECISION!r})")
-    return TRAIN_PRECISION, (_lib.IDN_PREC_F32 if TRAIN_PRECISION == "f32" else _lib.IDN_PREC_BF16X6)
 
 
 class FaceNeRFFn(torch.autograd.Function):

@@ -322,18 +322,23 @@ size_t idealnerf_pass_bwd_workspace_bytes(int64_t n_rays, int n_samples) {
     return bwd_workspace_bytes(n_rays * n_samples);
 }
 
-int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
-                       const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
-                       const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
-                       const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
-                       float* d_latent, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int e = check_params(p)) return e;
+static int check_grads(const idn_facenerf_grads* grads) {
     if (!grads) return fail(IDN_EINVAL, "grads is NULL");
     for (int i = 0; i < 8; ++i)
         if (!grads->pts_w[i] || !grads->pts_b[i]) return fail(IDN_EINVAL, "grad pts_linears.%d is NULL", i);
     for (int i = 0; i < 3; ++i)
         if (!grads->views_w[i] || !grads->views_b[i]) return fail(IDN_EINVAL, "grad views_linears.%d is NULL", i);
     if (!grads->alpha_w || !grads->alpha_b || !grads->rgb_w || !grads->rgb_b) return fail(IDN_EINVAL, "grad head is NULL");
+    return IDN_OK;
+}
+
+int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
+                       const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
+                       const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
+                       const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
+                       float* d_latent, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_grads(grads)) return e;
     if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
         (p->dim_latent > 0) != (latent != nullptr))
         return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
@@ -343,16 +348,6 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
     return launch_pass_bwd(*p, *grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
                            g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
                            (hipStream_t)stream);
-}
-
-static int check_grads(const idn_facenerf_grads* grads) {
-    if (!grads) return fail(IDN_EINVAL, "grads is NULL");
-    for (int i = 0; i < 8; ++i)
-        if (!grads->pts_w[i] || !grads->pts_b[i]) return fail(IDN_EINVAL, "grad pts_linears.%d is NULL", i);
-    for (int i = 0; i < 3; ++i)
-        if (!grads->views_w[i] || !grads->views_b[i]) return fail(IDN_EINVAL, "grad views_linears.%d is NULL", i);
-    if (!grads->alpha_w || !grads->alpha_b || !grads->rgb_w || !grads->rgb_b) return fail(IDN_EINVAL, "grad head is NULL");
-    return IDN_OK;
 }
 
 int idealnerf_facenerf_train_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,

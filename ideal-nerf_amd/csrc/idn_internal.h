@@ -263,7 +263,6 @@ int launch_sample_pdf(const float* z, const float* weights, const float* cdf_in,
                       const float* u, int u_per_ray, int64_t n_rays, int S, int Ni, float* z_samples,
                       int64_t* inds, float* cdf_out, float* z_fine, float* z_std, hipStream_t s);
 
-// train.hip: backward of one render pass
 // ---------------------------------------------------------------------------
 // Backward delta chain (mlp_f32_bwd.hip): the transposed weights as a second fragment stream.
 // Stage s computes D_in^T = W_s^T . D_out^T for 32 points per wave, masks it with the saved
@@ -299,10 +298,14 @@ size_t bwd_stream_floats_x6();
 int launch_pack_bf16x6_bwd(const idn_facenerf_params& p, float* packed_bwd, hipStream_t s);
 int launch_delta_chain_x6(const float* packed_bwd, const float* acts, int64_t p_pad, const float* d_rgb, float* dv0,
                           float* dv2, float* dv1, float* const da[8], hipStream_t s);
-size_t bwd_workspace_bytes(int64_t n_points);
+
+// dw_gemm.hip: one 256 x 256 weight-gradient product in isolation (idealnerf_dw_gemm); pipe: IDN_DW_PIPE_*
 size_t dw_gemm_workspace_bytes();
 int launch_dw_gemm(const float* delta, int ld_delta, const float* acts, int ld_acts, int64_t rows, float* dW, float* db, int pipe,
                    void* ws, size_t ws_bytes, hipStream_t s);
+
+// train.hip: backward of one render pass
+size_t bwd_workspace_bytes(int64_t n_points);
 int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,

@@ -6,7 +6,7 @@
 //      a.b ~ a1 b1 + a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1        (dropped: <= 2^-23 |a b|),
 // accumulated in fp32 by v_mfma_f32_32x32x16_bf16: the rounding of an fp32 fma chain at 16 / 6 of the fp32 MFMA
 // rate.  (bf16x3 keeps two pieces per operand and three products: 1e-5; the third piece is what makes this one
-// fp32-grade.  The training step's 256 x 256 weight-gradient GEMMs use the same arithmetic, train.hip.)
+// fp32-grade.  The training step's 256 x 256 weight-gradient GEMMs use the same arithmetic, dw_gemm.hip.)
 //
 // K-MAJOR layers (round 3).  A layer walks its 16-channel k-steps in order and, inside a k-step, its n-tiles: step
 // (s, t) = six piece products of k-step s into accumulator tile t.  The B operand of a k-step -- the three pieces of 16

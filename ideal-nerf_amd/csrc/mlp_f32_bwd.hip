@@ -6,7 +6,7 @@
 // (mlp_f32.hip): a wave owns 32 points, the TRANSPOSED weights are the streamed A operand, the
 // delta of one layer is the accumulator tile set that becomes the B operand of the next, and the
 // only HBM traffic per layer is the mask (the saved post-ReLU activation, read in accumulator
-// layout) and the delta itself, written row-major for the weight-gradient GEMMs (train.hip).
+// layout) and the delta itself, written row-major for the weight-gradient GEMMs (dw_gemm.hip).
 // The separate GEMMs moved three P x 256 matrices per layer and sat on the HBM/MFMA ridge.
 #include "mlp_x6.h"
 
@@ -333,7 +333,7 @@ int launch_delta_chain(const float* packed_bwd, const float* acts, int64_t p_pad
 
 // ===========================================================================================
 // The same chain on the bf16 matrix pipe, fp32-grade: six bf16 piece products per fp32 product (mlp_x6.h; the
-// forward in mlp_bf16x6.hip, the weight-gradient GEMMs in train.hip).  A stage's input delta is held as pieces
+// forward in mlp_bf16x6.hip, the weight-gradient GEMMs in dw_gemm.hip).  A stage's input delta is held as pieces
 // (192 registers for 256 channels x 32 points), its output as the fp32 accumulator tiles; at the end of a stage
 // the accumulators are masked, written to the delta matrix (this lane's row: a quad of registers is 16 contiguous
 // bytes of it) and split into the piece registers, which the finished stage no longer needs.

@@ -202,6 +202,38 @@ def facenerf_bwd(p, grads, aud, expr, latent, acts, g_out, d_x=None, d_aud=None,
     return grads
 
 
+def query_rays_train_fwd(packed, folded, rays, z, precision=_lib.IDN_PREC_BF16X6):
+    """query_rays_fwd that also records the backward's activation slab (idealnerf_query_rays_train_fwd):
+    -> (raw [n, S, 4], acts [idealnerf_train_acts_floats(n * S)])."""
+    lib = _lib.load()
+    _shape(z, "z", None, None)
+    n, S = z.shape
+    _shape(rays, "rays", n, RAY_FLOATS)
+    with _Launch(packed, folded, rays, z) as L:
+        raw = torch.empty((n, S, 4), dtype=torch.float32, device=z.device)
+        acts = torch.empty(lib.idealnerf_train_acts_floats(n * S), dtype=torch.float32, device=z.device)
+        check(lib.idealnerf_query_rays_train_fwd(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(rays, "rays"),
+                                                 _ptr(z, "z"), n, S, raw.data_ptr(), acts.data_ptr(), L.stream))
+    return raw, acts
+
+
+def pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
+    """Backward of one render pass (idealnerf_pass_bwd) from the slab of query_rays_train_fwd.  grads: as facenerf_bwd,
+    OVERWRITTEN; g_* = dL/d (rgb_map, rgb_fg, last_weight, acc_map), each may be None; d_aud / d_latent: accumulated."""
+    lib = _lib.load()
+    n, S = z.shape
+    for t, name, shape in ((raw, "raw", (n, S, 4)), (rays, "rays", (n, RAY_FLOATS)), (bc, "bc_rgb", (n, 3)),
+                           (g_rgb, "g_rgb_map", (n, 3)), (g_fg, "g_rgb_fg", (n, 3)), (g_lw, "g_last_weight", (n,)),
+                           (g_acc, "g_acc", (n,))):
+        _shape(t, name, *shape)
+    tensors = (aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+    with _Launch(*tensors, *grads.values()) as L:
+        ws = _workspace(lib.idealnerf_pass_bwd_workspace_bytes(n, S), z.device, L.stream)   # scratch of this (device, stream): two streams training on one GPU do not share it
+        ptrs = [_ptr(t) for t in tensors]
+        check(lib.idealnerf_pass_bwd(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
+    return grads
+
+
 def query_rays_fwd(packed, folded, rays, z, precision=IDN_PREC_F32) -> torch.Tensor:
     lib = _lib.load()
     _shape(z, "z", None, None)
@@ -545,7 +577,7 @@ def _workspace(nbytes: int, device, stream) -> torch.Tensor:
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
         # zeros, once per allocation: the backward multiplies whole 256-column delta matrices of which it writes 129 columns
-        # (csrc/train.hip: views_linears.0 + alpha_linear); what the other columns hold is never read back, but it must be
+        # (csrc/train.hip, bwd_tail: views_linears.0 + alpha_linear, a product of csrc/dw_gemm.hip); what the other columns hold is never read back, but it must be
         # DEFINED data (zeros now, values our own kernels wrote later), not whatever the allocator hands out
         ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         _workspaces[key] = ws
