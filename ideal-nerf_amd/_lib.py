@@ -89,6 +89,8 @@ PROTOTYPES = {
                                           fp, C.c_size_t, fp, fp]),
     "idealnerf_gather_rays": (C.c_int, [fp, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                         fp, fp, fp, fp, fp, fp, fp, fp]),
+    "idealnerf_gather_ray_pairs": (C.c_int, [fp, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float,
+                                             C.c_float, C.c_float, fp, fp, fp, fp, fp, fp, fp, fp, fp]),
     "idealnerf_frame_scores_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "idealnerf_frame_scores": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
     "idealnerf_coarse_depths": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, fp, fp]),
@@ -113,6 +115,8 @@ PROTOTYPES = {
     "idealnerf_pass_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "idealnerf_pass_bwd": (C.c_int, [C.POINTER(FaceNerfParams), C.POINTER(FaceNerfGrads), fp, fp, fp, fp, fp, fp, fp,
                                      fp, C.c_int64, C.c_int, fp, fp, fp, fp, fp, fp, fp, C.c_size_t, fp]),
+    "idealnerf_pass_bwd_cond": (C.c_int, [C.POINTER(FaceNerfParams), fp, fp, fp, fp, fp, fp, fp, fp, C.c_int64, C.c_int, fp, fp, fp,
+                                          fp, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_facenerf_train_fwd": (C.c_int, [fp, fp, C.c_int, fp, C.c_int64, fp, fp, fp]),
     "idealnerf_facenerf_bwd_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "idealnerf_facenerf_bwd": (C.c_int, [C.POINTER(FaceNerfParams), C.POINTER(FaceNerfGrads), fp, fp, fp, fp, C.c_int64, fp,

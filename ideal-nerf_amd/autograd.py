@@ -40,7 +40,15 @@ def _train_query(net, folded, rays, z):
     return ops.query_rays_train_fwd(net.packed_weights(prec_name), folded, rays, z, code)
 
 
-def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
+def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, frozen=False):
+    """One pass's backward -> its 24 parameter gradients by PARAM_KEYS.  frozen = (need_aud, need_latent) for a network none of
+    whose parameters needs a gradient: the conditioning-only plan -- d_aud / d_latent alone, each only if needed (neither: no
+    launch at all), and None for every parameter."""
+    if frozen:
+        d_aud, d_latent = (d if want else None for d, want in zip((d_aud, d_latent), frozen))
+        if d_aud is not None or d_latent is not None:
+            ops.pass_bwd_cond(net.kernel_params(), aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+        return dict.fromkeys(PARAM_KEYS)
     sd = dict(net.named_parameters())
     # (no column stays uninitialised: the fold kernel writes all conditioning columns, the GEMM reductions all others)
     grads = {k: torch.empty_like(sd[k]) for k in PARAM_KEYS}
@@ -96,22 +104,27 @@ class RenderRaysFn(torch.autograd.Function):
         coarse, fine = ctx.nets
         Ni, with_fg = ctx.Ni, ctx.with_fg
         aud, expr, lat = ctx.cond
-        d_aud = torch.zeros_like(aud) if aud is not None else None
-        d_lat = torch.zeros_like(lat) if lat is not None else None
+        need_aud, need_lat = ctx.needs
+        # the plan of each network, from what autograd asks for: a network none of whose 24 parameters needs a gradient runs the
+        # conditioning-only backward (and nothing at all if neither aud nor latent needs one either)
+        need_p = ctx.needs_input_grad[RenderRaysFn.N_FIXED:]
+        frozen_c, frozen_f = not any(need_p[:len(PARAM_KEYS)]), not any(need_p[len(PARAM_KEYS):])
+        both_frozen = frozen_c and (frozen_f or Ni == 0)
+        d_aud = torch.zeros_like(aud) if aud is not None and (need_aud or not both_frozen) else None
+        d_lat = torch.zeros_like(lat) if lat is not None and (need_lat or not both_frozen) else None
         c = lambda t: None if t is None else t.contiguous()
         if Ni == 0:
             rays, bc, raw_c, z_c, acts_c = ctx.saved
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[0]), c(g[3]) if with_fg else None,
-                           None, c(g[2]), d_aud, d_lat)
+                           None, c(g[2]), d_aud, d_lat, frozen=frozen_c and ctx.needs)
             gf = {k: None for k in PARAM_KEYS}
         else:
             rays, bc, raw_c, z_c, acts_c, raw_f, z_f, acts_f = ctx.saved
             gf = _pass_bwd(fine, aud, expr, lat, acts_f, raw_f, z_f, rays, bc, c(g[0]), c(g[8]) if with_fg else None,
-                           c(g[7]), c(g[2]), d_aud, d_lat)
+                           c(g[7]), c(g[2]), d_aud, d_lat, frozen=frozen_f and ctx.needs)
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[3]), c(g[9]) if with_fg else None,
-                           c(g[10]) if with_fg else None, c(g[5]), d_aud, d_lat)
+                           c(g[10]) if with_fg else None, c(g[5]), d_aud, d_lat, frozen=frozen_c and ctx.needs)
         ctx.saved = None
-        need_aud, need_lat = ctx.needs
         param_grads = [gc[k] for k in PARAM_KEYS] + [gf[k] for k in PARAM_KEYS]
         fixed = [None] * RenderRaysFn.N_FIXED
         fixed[10] = d_aud if need_aud else None

@@ -14,11 +14,12 @@ def natural_key(s: str):
     return [int(t) if t.isdigit() else t.lower() for t in re.split(r"(\d+)", s)]
 
 
-def latest_checkpoint(run_dir: str):
-    """natsorted(listdir)[-1] among names containing '.tar' (audio_exp_nerf.py:516-518), or None."""
+def latest_checkpoint(run_dir: str, contains: str = ".tar"):
+    """natsorted(listdir)[-1] among names containing '.tar' (audio_exp_nerf.py:516-518), or None.  contains: the substring
+    looked for instead -- the torso stage takes 'head.tar', then 'torso.tar' (train_torso.py:489-499)."""
     if not os.path.isdir(run_dir):
         return None
-    names = sorted((f for f in os.listdir(run_dir) if ".tar" in f), key=natural_key)
+    names = sorted((f for f in os.listdir(run_dir) if contains in f), key=natural_key)
     return os.path.join(run_dir, names[-1]) if names else None
 
 
@@ -30,10 +31,11 @@ def save_checkpoint(path: str, network, optimizer, latent_codes, global_step: in
                 "latent_codes": latent_codes.data}, path)
 
 
-def load_checkpoint(path: str, network, optimizer=None, map_location=None):
-    """-> (global_step, latent_codes).  Keys and strictness as upstream (:520-524)."""
+def load_checkpoint(path: str, network, optimizer=None, map_location=None, strict=True):
+    """-> (global_step, latent_codes).  Keys and strictness as upstream (:520-524); strict=False: how the torso stage takes the
+    head stage's weights (train_torso.py:495)."""
     ckpt = torch.load(path, map_location=map_location, weights_only=False)
-    network.load_state_dict(ckpt["model_state_dict"])
+    network.load_state_dict(ckpt["model_state_dict"], strict=strict)
     if optimizer is not None and ckpt.get("optimizer") is not None:
         optimizer.load_state_dict(ckpt["optimizer"])
     return ckpt["global_step"], ckpt["latent_codes"]

@@ -195,8 +195,22 @@ int idealnerf_gather_rays(const int64_t* sel, int64_t n, const float* c2w, int H
     if (n == 0) return IDN_OK;
     if (!sel || !c2w || !image || !background || !target_table || !background_table || !batch_rays || !target_s || !bc_rgb)
         return fail(IDN_EINVAL, "NULL pointer");
-    return launch_gather_rays((const long long*)sel, n, c2w, H, W, focal, cx, cy, image, background, target_table, background_table,
-                              batch_rays, target_s, bc_rgb, (hipStream_t)stream);
+    return launch_gather_rays((const long long*)sel, n, c2w, nullptr, H, W, focal, cx, cy, image, background, target_table,
+                              background_table, batch_rays, nullptr, target_s, bc_rgb, (hipStream_t)stream);
+}
+
+int idealnerf_gather_ray_pairs(const int64_t* sel, int64_t n, const float* c2w, const float* c2w_torso, int H, int W, float focal,
+                               float cx, float cy, const uint8_t* image, const uint8_t* background, const float* target_table,
+                               const float* background_table, float* batch_rays, float* batch_rays_torso, float* target_s,
+                               float* bc_rgb, void* stream) {
+    if (H <= 0 || W <= 0 || (int64_t)H * W > (1LL << 30)) return fail(IDN_EINVAL, "bad frame %d x %d", H, W);
+    if (n < 0 || n > 0x7fffffffLL / 8) return fail(IDN_EINVAL, "bad n %lld", (long long)n);
+    if (n == 0) return IDN_OK;
+    if (!sel || !c2w || !c2w_torso || !image || !background || !target_table || !background_table || !batch_rays ||
+        !batch_rays_torso || !target_s || !bc_rgb)
+        return fail(IDN_EINVAL, "NULL pointer");
+    return launch_gather_rays((const long long*)sel, n, c2w, c2w_torso, H, W, focal, cx, cy, image, background, target_table,
+                              background_table, batch_rays, batch_rays_torso, target_s, bc_rgb, (hipStream_t)stream);
 }
 
 size_t idealnerf_frame_scores_workspace_bytes(int H, int W) { return frame_scores_workspace_bytes(H, W); }
@@ -345,7 +359,24 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
     if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
     if (n_rays == 0) return IDN_OK;
     if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_pass_bwd(*p, *grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
+    return launch_pass_bwd(*p, grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
+                           g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
+                           (hipStream_t)stream);
+}
+
+int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, const float* expr, const float* latent,
+                            const float* acts, const float* raw, const float* z, const float* rays, const float* bc_rgb,
+                            int64_t n_rays, int n_samples, const float* g_rgb_map, const float* g_rgb_fg,
+                            const float* g_last_weight, const float* g_acc, float* d_aud, float* d_latent, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (int e = check_params(p)) return e;
+    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
+        (p->dim_latent > 0) != (latent != nullptr))
+        return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
+    if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
+    if (n_rays == 0 || (!d_aud && !d_latent)) return IDN_OK;   // nothing to deliver
+    if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_pass_bwd(*p, nullptr, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
                            g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
                            (hipStream_t)stream);
 }

@@ -236,9 +236,11 @@ int launch_philox_uniform(unsigned long long seed, int which, int64_t row0, int6
 // sampler.hip: the training loader's region-weighted pixel draw and the gather of the drawn pixels' rays / colours
 int launch_sample_pixels(const unsigned char* map, int H, int W, const int counts[4], unsigned long long seed, unsigned long long draw,
                          int* population, long long* sel, hipStream_t s);
-int launch_gather_rays(const long long* sel, int64_t n, const float* c2w_host, int H, int W, float focal, float cx, float cy,
-                       const unsigned char* image, const unsigned char* background, const float* target_table,
-                       const float* background_table, float* batch_rays, float* target_s, float* bc_rgb, hipStream_t s);
+// (c2w2_host / batch_rays2: the optional second camera and its rays for the same pixels; nullptr = one camera)
+int launch_gather_rays(const long long* sel, int64_t n, const float* c2w_host, const float* c2w2_host, int H, int W, float focal,
+                       float cx, float cy, const unsigned char* image, const unsigned char* background, const float* target_table,
+                       const float* background_table, float* batch_rays, float* batch_rays2, float* target_s, float* bc_rgb,
+                       hipStream_t s);
 // metrics.hip: squared error and SSIM of a frame against its uint8 ground truth, whole frame and per region -> out [5, 4] fp64
 size_t frame_scores_workspace_bytes(int H, int W);
 int launch_frame_scores(const float* pred, const unsigned char* truth, const unsigned char* regions, int H, int W, double* out,
@@ -306,7 +308,8 @@ int launch_dw_gemm(const float* delta, int ld_delta, const float* acts, int ld_a
 
 // train.hip: backward of one render pass
 size_t bwd_workspace_bytes(int64_t n_points);
-int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
+// gr == nullptr: the conditioning-only backward of a frozen network (d_aud / d_latent alone; no gradient tensor is written)
+int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
                     const float* g_acc, float* d_aud, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s);

@@ -188,9 +188,12 @@ int launch_sample_pixels(const unsigned char* map, int H, int W, const int count
 struct GatherCam {
     float m[12];
 };
-__global__ void gather_rays_kernel(const long long* sel, int n, GatherCam c, int W, long npix, float focal, float cx, float cy,
-                                   const unsigned char* image, const unsigned char* background, const float* target_table,
-                                   const float* background_table, float* batch_rays, float* target_s, float* bc_rgb) {
+// (c2 / batch_rays2: the optional second camera -- the torso stage's frame-0 pose -- for the same pixels; batch_rays2 == nullptr
+//  is the one-camera case)
+__global__ void gather_rays_kernel(const long long* sel, int n, GatherCam c, GatherCam c2, int W, long npix, float focal, float cx,
+                                   float cy, const unsigned char* image, const unsigned char* background, const float* target_table,
+                                   const float* background_table, float* batch_rays, float* batch_rays2, float* target_s,
+                                   float* bc_rgb) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     const long long pix = sel[idx];
@@ -202,27 +205,37 @@ __global__ void gather_rays_kernel(const long long* sel, int n, GatherCam c, int
     const float d0 = (i - cx) / focal;
     const float d1 = -(j - cy) / focal;
     const float d2 = -1.0f;
-    float d[3];
+    auto rays_of = [&](const GatherCam& cam, float* out) {
+        float d[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) d[r] = (d0 * c.m[4 * r + 0] + d1 * c.m[4 * r + 1]) + d2 * c.m[4 * r + 2];
+        for (int r = 0; r < 3; ++r) d[r] = (d0 * cam.m[4 * r + 0] + d1 * cam.m[4 * r + 1]) + d2 * cam.m[4 * r + 2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            out[(long)idx * 3 + r] = ok ? cam.m[4 * r + 3] : 0.0f;
+            out[((long)n + idx) * 3 + r] = ok ? d[r] : 0.0f;
+        }
+    };
+    rays_of(c, batch_rays);
+    if (batch_rays2) rays_of(c2, batch_rays2);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        batch_rays[(long)idx * 3 + r] = ok ? c.m[4 * r + 3] : 0.0f;
-        batch_rays[((long)n + idx) * 3 + r] = ok ? d[r] : 0.0f;
         target_s[(long)idx * 3 + r] = ok ? target_table[image[q * 3 + r]] : 0.0f;
         bc_rgb[(long)idx * 3 + r] = ok ? background_table[background[q * 3 + r]] : 0.0f;
     }
 }
 
-int launch_gather_rays(const long long* sel, int64_t n, const float* c2w_host, int H, int W, float focal, float cx, float cy,
-                       const unsigned char* image, const unsigned char* background, const float* target_table,
-                       const float* background_table, float* batch_rays, float* target_s, float* bc_rgb, hipStream_t s) {
-    GatherCam c;
+int launch_gather_rays(const long long* sel, int64_t n, const float* c2w_host, const float* c2w2_host, int H, int W, float focal,
+                       float cx, float cy, const unsigned char* image, const unsigned char* background, const float* target_table,
+                       const float* background_table, float* batch_rays, float* batch_rays2, float* target_s, float* bc_rgb,
+                       hipStream_t s) {
+    GatherCam c, c2;
     for (int i = 0; i < 12; ++i) c.m[i] = c2w_host[i];
+    for (int i = 0; i < 12; ++i) c2.m[i] = c2w2_host ? c2w2_host[i] : 0.0f;
     if (cx < 0) cx = W * 0.5f;
     if (cy < 0) cy = H * 0.5f;
-    hipLaunchKernelGGL(gather_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sel, (int)n, c, W, (long)H * W, focal,
-                       cx, cy, image, background, target_table, background_table, batch_rays, target_s, bc_rgb);
+    hipLaunchKernelGGL(gather_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sel, (int)n, c, c2, W, (long)H * W,
+                       focal, cx, cy, image, background, target_table, background_table, batch_rays, c2w2_host ? batch_rays2 : nullptr,
+                       target_s, bc_rgb);
     IDN_HIP_CHECK(hipGetLastError());
     return IDN_OK;
 }

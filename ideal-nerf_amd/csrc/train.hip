@@ -6,6 +6,8 @@
 //   delta chain       all delta_l = (delta_{l+1} . W_{l+1}) (.) [a_l > 0] in one fused kernel (mlp_f32_bwd.hip)
 //   dW products       dW_l = delta_l^T . a_{l-1} and db_l = sum_p delta_l: dw_gemm.hip, scheduled by DwPass (dw_gemm.h)
 //   fold_bwd          conditioning columns of W0 / W5 / Wv0 and d aud, d latent
+//   frozen network    (no gradient tensors: idealnerf_pass_bwd_cond) instead of the dW products, colsum_rows / colsum_finish on
+//                     dA[0] and dA[5], and the d cond range of fold_bwd alone
 //
 // Activations come from the training variant of the MLP kernel as row-major matrices
 // (idn_internal.h, "activation slab").  Everything is deterministic: no float atomics.
@@ -168,17 +170,20 @@ __device__ __forceinline__ float cond_val(const FoldBwdArgs& d, int c) {
     c -= d.p.dim_expr;
     return d.latent[c];
 }
+// kCondOnly: the launch covers the d cond index range alone (a frozen network: bwd_tail without gradient tensors) -- gW0 / gW5 /
+// gWv0 and dbv are never touched
+template <bool kCondOnly>
 __global__ void fold_bwd_kernel(FoldBwdArgs d) {
     const int C = d.p.dim_aud + d.p.dim_expr + d.p.dim_latent;
     const int ld0 = IDN_PTS_CH + C, ld5 = IDN_PTS_CH + C + IDN_W, ldv = IDN_W + IDN_VIEWS_CH + d.p.dim_expr;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x + (kCondOnly ? IDN_W * C + (IDN_W / 2) * d.p.dim_expr : 0);
     const int n_outer = IDN_W * C;
-    if (idx < n_outer) {
+    if (!kCondOnly && idx < n_outer) {
         const int n = idx / C, c = idx % C;
         const float cv = cond_val(d, c);
         d.gW0[(long)n * ld0 + IDN_PTS_CH + c] = d.db0[n] * cv;
         d.gW5[(long)n * ld5 + IDN_PTS_CH + c] = d.db5[n] * cv;
-    } else if (idx < n_outer + (IDN_W / 2) * d.p.dim_expr) {
+    } else if (!kCondOnly && idx < n_outer + (IDN_W / 2) * d.p.dim_expr) {
         const int k = idx - n_outer, n = k / d.p.dim_expr, e = k % d.p.dim_expr;
         d.gWv0[(long)n * ldv + IDN_W + IDN_VIEWS_CH + e] = d.dbv[n] * (d.expr[e] * 1.0f / 3.0f);
     } else {
@@ -213,6 +218,37 @@ __global__ void fold_bwd_kernel(FoldBwdArgs d) {
         }
     }
 }
+
+// ---------------------------------------------------------------------------
+// Column sums of two [rows, 256] fp32 matrices (row pitch 256): the bias gradients db0' / db5' the conditioning fold reads, for
+// a pass whose weight gradients nobody wants.  Deterministic, no float atomics: workgroup (b, m) sums rows
+// [b rows_per_block, (b + 1) rows_per_block) of matrix m in row order, one thread per column (a row is one coalesced 1 KB
+// line), in fp64; colsum_finish_kernel adds the partial sums in block order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void colsum_rows_kernel(const float* m0, const float* m1, long rows, long rows_per_block, double* part) {
+    const float* m = blockIdx.y ? m1 : m0;
+    const long r0 = (long)blockIdx.x * rows_per_block;
+    const long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    const float* col = m + threadIdx.x;
+    double acc = 0.0;
+    long r = r0;
+    for (; r + 8 <= r1; r += 8) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = col[(r + i) * 256];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc += (double)v[i];
+    }
+    for (; r < r1; ++r) acc += (double)col[r * 256];
+    part[((long)blockIdx.x * 2 + blockIdx.y) * 256 + threadIdx.x] = acc;
+}
+__global__ __launch_bounds__(256) void colsum_finish_kernel(const double* part, int blocks, float* out) {
+    double acc = 0.0;   // out [2][256]: workgroup m finishes matrix m
+    for (int b = 0; b < blocks; ++b) acc += part[((long)b * 2 + blockIdx.x) * 256 + threadIdx.x];
+    out[blockIdx.x * 256 + threadIdx.x] = (float)acc;
+}
+constexpr int kCondColsumBlocks = 512;   // row blocks at the most: their fp64 partial sums and the 512 results fit the cpart pool
+static_assert(512 + (size_t)kCondColsumBlocks * 512 * 2 <= kCpartPoolFloats, "the conditioning-only column sums fit the cpart pool");
 
 // ---------------------------------------------------------------------------
 // host orchestration
@@ -261,7 +297,9 @@ static int backward_pipe() {
 // The part of a backward that follows the head deltas (dRGB columns 0..2, dV0 column kSigmaChannel, zeros in the padding
 // rows): the transposed weight stream, the delta chain, the weight / bias gradient products and the conditioning fold.
 // launch_pass_bwd seeds the head deltas with the compositing backward, launch_facenerf_bwd with the caller's d raw.
-static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
+// grads == nullptr (a frozen network): after the delta chain only what d aud / d latent need -- the column sums of dA[0] and
+// dA[5] and the d cond range of the fold; no weight-gradient product runs and no gradient tensor is written.
+static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grads, const float* aud, const float* expr,
                     const float* latent, const float* acts, int64_t Pp, const BwdWs& w, float* d_aud, float* d_expr,
                     float* d_latent, hipStream_t s) {
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
@@ -280,6 +318,24 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads& gr, 
         TRY(launch_pack_f32_bwd(p, w.wbwd, s));
         TRY(launch_delta_chain(w.wbwd, acts, Pp, w.dRGB, w.dV0, w.dV[0], w.dV[1], w.dA, s));
     }
+    if (!grads) {
+        if (C == 0) return IDN_OK;
+        float* db = w.cpart;                                        // [2][256]: db0', db5'
+        double* part = reinterpret_cast<double*>(w.cpart + 512);    // [blocks][2][256] (the pool is 256-byte aligned)
+        const int64_t chunks = Pp / 128;
+        const int64_t rows_per_block = (chunks + kCondColsumBlocks - 1) / kCondColsumBlocks * 128;
+        const int blocks = (int)((Pp + rows_per_block - 1) / rows_per_block);
+        hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 2), dim3(256), 0, s, (const float*)w.dA[0], (const float*)w.dA[5], (long)Pp,
+                           (long)rows_per_block, part);
+        IDN_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3(2), dim3(256), 0, s, (const double*)part, blocks, db);
+        IDN_HIP_CHECK(hipGetLastError());
+        FoldBwdArgs f{p, aud, expr, latent, db, db + 256, nullptr, nullptr, nullptr, nullptr, d_aud, d_latent, nullptr};
+        hipLaunchKernelGGL(fold_bwd_kernel<true>, dim3((C * 64 + 255) / 256), dim3(256), 0, s, f);
+        IDN_HIP_CHECK(hipGetLastError());
+        return IDN_OK;
+    }
+    const idn_facenerf_grads& gr = *grads;
     // weight and bias gradients: dW_l = delta_l^T a_{l-1} (contraction over the points), db_l = column sums.  The products in
     // kPassProducts' order (dw_gemm.h), each followed by the blocks of it that become gradients.
     DwPass q(w.part, kPartPoolFloats, w.cpart, kCpartPoolFloats, Pp, pipe, kX6ItemsPerPass, s);
@@ -334,14 +390,14 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads& gr, 
                       gr.views_w[0], d_aud, d_latent, d_expr};
         const int total = IDN_W * C + (IDN_W / 2) * p.dim_expr + C * 64;   // one wavefront per conditioning column at the end
         if (total > 0) {
-            hipLaunchKernelGGL(fold_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, s, f);
+            hipLaunchKernelGGL(fold_bwd_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, s, f);
             IDN_HIP_CHECK(hipGetLastError());
         }
     }
     return IDN_OK;
 }
 
-int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
+int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
                     const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s) {
@@ -499,7 +555,7 @@ int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& 
                            w.dRGB, w.dV0);
         IDN_HIP_CHECK(hipGetLastError());
     }
-    if (int e = bwd_tail(p, gr, aud, expr, latent, acts, Pp, w, d_aud, d_expr, d_latent, s)) return e;
+    if (int e = bwd_tail(p, &gr, aud, expr, latent, acts, Pp, w, d_aud, d_expr, d_latent, s)) return e;
     if (d_x) {
         static LaunchSetup setup;
         int num_cu = 0;

@@ -31,11 +31,9 @@ def _imread(path):
     return np.asarray(Image.open(path))
 
 
-def region_masks(H, W, face_rect, landmark, parse_img):
-    """The pixel regions the sampler draws from (audio_exp_nerf.py:143-175) -> (coords [H W, 2] float32 (row, col), mouth [H W],
-    rect [H W], torso [H, W]) as boolean masks.  Upstream's row/column convention is kept: pixel ROWS are compared against the
-    landmark / rect *x* bounds (:150-155).  The one definition of the regions: `select_pixels` draws from these masks and
-    `region_byte_map` packs them for the device-side sampler."""
+def _box_masks(H, W, face_rect, landmark):
+    """-> (coords [H W, 2] float32 (row, col), mouth box [H W], face rect [H W]); upstream's row/column convention is kept:
+    pixel ROWS are compared against the landmark / rect *x* bounds (audio_exp_nerf.py:150-155, train_torso.py:145-149)."""
     mouth = landmark[48:]
     max_x, min_x = np.max(mouth[:, 0]) + 20, np.min(mouth[:, 0]) - 20
     max_y, min_y = np.max(mouth[:, 1]) + 20, np.min(mouth[:, 1]) - 20
@@ -44,8 +42,30 @@ def region_masks(H, W, face_rect, landmark, parse_img):
     mouth_w = (coords[:, 0] >= min_x) & (coords[:, 0] <= max_x) & (coords[:, 1] >= min_y) & (coords[:, 1] <= max_y)
     rect_w = ((coords[:, 0] >= face_rect[0]) & (coords[:, 0] <= face_rect[0] + face_rect[2]) &
               (coords[:, 1] >= face_rect[1]) & (coords[:, 1] <= face_rect[1] + face_rect[3]))
+    return coords, mouth_w, rect_w
+
+
+def region_masks(H, W, face_rect, landmark, parse_img):
+    """The pixel regions the sampler draws from (audio_exp_nerf.py:143-175) -> (coords [H W, 2] float32 (row, col), mouth [H W],
+    rect [H W], torso [H, W]) as boolean masks.  Upstream's row/column convention is kept: pixel ROWS are compared against the
+    landmark / rect *x* bounds (:150-155).  The one definition of the regions: `select_pixels` draws from these masks and
+    `region_byte_map` packs them for the device-side sampler."""
+    coords, mouth_w, rect_w = _box_masks(H, W, face_rect, landmark)
     torso = (parse_img[:, :, 0] == 255) & (parse_img[:, :, 1] == 0) & (parse_img[:, :, 2] == 0)
     return coords, mouth_w, rect_w, torso
+
+
+def torso_region_masks(H, W, face_rect, landmark):
+    """The torso stage's regions (train_torso.py:136-153) -> (coords, mouth box [H W], rect [H W], drawn [H W], M).  M is the
+    mouth box's population; `drawn` marks the first M outside-rect pixels in row-major order -- the population upstream's mouth
+    block REALLY draws from: it indexes `coords_norect` with indices drawn from the mouth box's population (:168-169).  (All of
+    the outside pixels where M exceeds their number: there upstream raises IndexError.)  The one definition of the torso
+    regions: `torso_select_pixels` draws from them, `torso_region_byte_map` packs them."""
+    coords, mouth_w, rect_w = _box_masks(H, W, face_rect, landmark)
+    M = int(mouth_w.sum())
+    outside = ~rect_w
+    drawn = outside & (np.cumsum(outside) <= M)
+    return coords, mouth_w, rect_w, drawn, M
 
 
 REGION_NAMES = ("rect", "outside", "mouth", "torso")   # bit g of the byte map, row block g of a batch
@@ -76,16 +96,63 @@ def select_pixels(H, W, face_rect, landmark, parse_img, n_rand, mouth_rays, tors
     return np.concatenate([s_rect, s_norect, s_mouth, s_torso], 0)
 
 
+def torso_region_byte_map(H, W, face_rect, landmark):
+    """uint8 [H, W] for the torso stage: bit 0 = face rect minus mouth box, bit 1 = outside the face rect, bit 2 = the first M
+    outside-rect pixels in row-major order (`torso_region_masks`), bit 3 clear."""
+    _, mouth_w, rect_w, drawn, _ = torso_region_masks(H, W, face_rect, landmark)
+    return ((rect_w & ~mouth_w).astype(np.uint8) | ((~rect_w).astype(np.uint8) << 1) | (drawn.astype(np.uint8) << 2)).reshape(H, W)
+
+
+def torso_mouth_num(n_rand, use_highlight):
+    """train_torso.py:157: a quarter of the batch goes to the mouth block under `use_highlight`."""
+    return n_rand // 4 if use_highlight else 0
+
+
+def torso_select_pixels(H, W, face_rect, landmark, n_rand, use_highlight, sample_rate):
+    """-> int64 [n_rand, 2] (row, col), train_torso.py:136-170: draws AND rows in the order rect, outside, mouth, from the global
+    numpy RNG exactly like upstream -- the mouth block's indices are drawn from the mouth box's population and index
+    `coords_norect` (an index past its end raises IndexError, as upstream)."""
+    coords, mouth_w, rect_w, _, M = torso_region_masks(H, W, face_rect, landmark)
+    c_rect, c_norect = coords[rect_w & ~mouth_w], coords[~rect_w]
+    mouth_num = torso_mouth_num(n_rand, use_highlight)
+    sample_num = n_rand - mouth_num
+    rect_num = int(sample_num * sample_rate)
+    norect_num = sample_num - rect_num
+    s_rect = c_rect[np.random.choice(c_rect.shape[0], size=[rect_num], replace=False)]
+    s_norect = c_norect[np.random.choice(c_norect.shape[0], size=[norect_num], replace=False)]
+    s_mouth = c_norect[np.random.choice(M, size=[mouth_num], replace=False)]
+    return np.concatenate([s_rect, s_norect, s_mouth], 0).astype(np.int64)
+
+
+def gather_selected(sel, poses, target, bc_img, H, W, focal, cx, cy, device):
+    """Rays of the pixels `sel` (int64 [n, 2] (row, col), numpy) from each camera of `poses`, and their colours ->
+    ([batch_rays [2, n, 3] per pose], target_s [n, 3], bc_rgb [n, 3]) on `device`: the device-side pinhole kernel on the whole
+    frame, gathered there."""
+    sel = torch.from_numpy(sel)
+    flat = (sel[:, 0] * W + sel[:, 1]).to(device)
+    rays = []
+    for pose in poses:
+        rec = ops.frame_rays(torch.as_tensor(pose, dtype=torch.float32), H, W, focal, 0.0, 1.0, cx=cx, cy=cy, device=device)
+        rays.append(torch.stack([rec[flat, 0:3], rec[flat, 3:6]], 0))
+    return rays, target.reshape(-1, 3)[flat], bc_img.reshape(-1, 3)[flat]
+
+
 def sample_rays(pose, face_rect, target, bc_img, landmark, parse_img, H, W, focal, cx, cy, n_rand, mouth_rays,
                 torso_rays, sample_rate, device):
     """audio_exp_nerf.py:134-195 -> (batch_rays [2, n, 3], target_s [n, 3], bc_rgb [n, 3]) on `device`."""
-    sel = torch.from_numpy(select_pixels(H, W, face_rect, landmark, parse_img, n_rand, mouth_rays, torso_rays, sample_rate))
-    flat = (sel[:, 0] * W + sel[:, 1]).to(device)
-    rec = ops.frame_rays(torch.as_tensor(pose, dtype=torch.float32), H, W, focal, 0.0, 1.0, cx=cx, cy=cy, device=device)
-    batch_rays = torch.stack([rec[flat, 0:3], rec[flat, 3:6]], 0)
-    target_s = target.reshape(-1, 3)[flat]
-    bc_rgb = bc_img.reshape(-1, 3)[flat]
+    sel = select_pixels(H, W, face_rect, landmark, parse_img, n_rand, mouth_rays, torso_rays, sample_rate)
+    (batch_rays,), target_s, bc_rgb = gather_selected(sel, [pose], target, bc_img, H, W, focal, cx, cy, device)
     return batch_rays, target_s, bc_rgb
+
+
+def torso_sample_rays(pose, pose_torso, face_rect, target, bc_img, landmark, H, W, focal, cx, cy, n_rand, use_highlight,
+                      sample_rate, device):
+    """train_torso.py:130-183 -> (batch_rays, batch_rays_torso [2, n, 3] each, target_s [n, 3], bc_rgb [n, 3]) on `device`;
+    batch_rays_torso: the same pixels seen from `pose_torso` (the clip's frame-0 pose)."""
+    sel = torso_select_pixels(H, W, face_rect, landmark, n_rand, use_highlight, sample_rate)
+    (batch_rays, batch_rays_torso), target_s, bc_rgb = gather_selected(sel, [pose, pose_torso], target, bc_img, H, W, focal, cx,
+                                                                        cy, device)
+    return batch_rays, batch_rays_torso, target_s, bc_rgb
 
 
 class GetData(torch.utils.data.Dataset):
@@ -117,23 +184,50 @@ class GetData(torch.utils.data.Dataset):
     def __len__(self):
         return self.data_size
 
+    def _read_image(self, index):
+        return _imread(self.all_imgs[index])[..., ::-1].copy()  # upstream reads with cv2: BGR
+
+    def _sample(self, index, target, pose):
+        """-> (the frame's ray sets ..., target_s, bc_rgb) of one draw."""
+        a = self.args
+        parse = _imread(self.all_parse_imgs[index])
+        landmark = np.loadtxt(self.all_landmarks[index])
+        return sample_rays(pose, self.all_face_rects[index], target, self.background_img, landmark, parse, self.H, self.W,
+                           self.focal, self.cx, self.cy, a.N_rand, a.mouth_rays, a.torso_rays, a.sample_rate, self.device)
+
     def __getitem__(self, index):
         if index is None:
             index = np.random.choice(self.data_size)
-        raw = _imread(self.all_imgs[index])[..., ::-1].copy()  # upstream reads with cv2: BGR
-        raw_img = torch.tensor(raw)
+        raw_img = torch.tensor(self._read_image(index))
         self.H, self.W = raw_img.shape[0], raw_img.shape[1]
         target = raw_img.to(self.device).float() / 255.0
-        parse = _imread(self.all_parse_imgs[index])
         pose = self.all_poses[index][:3, :4]
-        landmark = np.loadtxt(self.all_landmarks[index])
-        a = self.args
-        batch_rays, target_s, bc_rgb = sample_rays(pose, self.all_face_rects[index], target, self.background_img,
-                                                   landmark, parse, self.H, self.W, self.focal, self.cx, self.cy,
-                                                   a.N_rand, a.mouth_rays, a.torso_rays, a.sample_rate, self.device)
+        *rays, target_s, bc_rgb = self._sample(index, target, pose)
         bc_rgb = bc_rgb if self.mode == "train" else self.background_img
         exp = torch.tensor(self.all_exprs[index], dtype=torch.float32)
-        return batch_rays, target_s, bc_rgb, self.auds, raw_img, pose, exp, index
+        return (*rays, target_s, bc_rgb, self.auds, raw_img, pose, exp, index)
+
+
+class TorsoGetData(GetData):
+    """The torso stage's host-side loader (``GetData`` of NeRFs/TorsoNeRF/train_torso.py:46-183): ``__getitem__`` returns the
+    9-tuple (batch_rays, batch_rays_torso, target_s, bc_rgb, auds, raw_img, pose, exp, index).  ``batch_rays_torso`` are the same
+    pixels seen from the clip's frame-0 pose; the images are RGB (upstream reads them with imageio here); no parsing image is
+    read; the pixel selection is ``torso_select_pixels``.  ``args`` needs gt_dirs, testskip, N_rand, sample_rate, use_highlight.
+    As upstream (:82), a non-train clip's ``data_size`` is its frame count divided by ``testskip`` once more."""
+
+    def __init__(self, data_dir, aud_file, mode, args, skip=1, device="cuda"):
+        super().__init__(data_dir, aud_file, mode, args, skip=skip, device=device)
+        if mode != "train":
+            self.data_size = len(self.all_imgs) // args.testskip
+
+    def _read_image(self, index):
+        return _imread(self.all_imgs[index])
+
+    def _sample(self, index, target, pose):
+        a = self.args
+        landmark = np.loadtxt(self.all_landmarks[index])
+        return torso_sample_rays(pose, self.all_poses[0][:3, :4], self.all_face_rects[index], target, self.background_img, landmark,
+                                 self.H, self.W, self.focal, self.cx, self.cy, a.N_rand, a.use_highlight, a.sample_rate, self.device)
 
 
 class ResidentFrames:
@@ -169,7 +263,7 @@ class ResidentFrames:
         if max_bytes is not None and need > max_bytes:
             raise ValueError(f"{n} frames of {self.H} x {self.W} need {need} bytes of device memory (4 per pixel and frame), more "
                              f"than max_bytes = {max_bytes}: raise max_bytes, take fewer frames (skip=), or use GetData")
-        self.counts = ops.sample_counts(args.N_rand, args.mouth_rays, args.torso_rays, args.sample_rate)
+        self.counts = self._counts(args)
         if min(self.counts) < 0:
             raise ValueError(f"N_rand {args.N_rand} is smaller than mouth_rays + torso_rays")
         from ._lib import SAMPLE_MAX_REGION
@@ -182,11 +276,7 @@ class ResidentFrames:
         for i, frame in enumerate(frames):
             fid = str(frame["img_id"])
             img_paths.append(os.path.join(data_dir, args.gt_dirs, fid + ".jpg"))
-            parse = _imread(os.path.join(data_dir, "parsing", fid + ".png"))
-            if parse.shape[:2] != (self.H, self.W):
-                raise ValueError(f"frame {fid}: parsing image is {parse.shape[:2]}, the clip's cx / cy say {(self.H, self.W)}")
-            landmark = np.loadtxt(os.path.join(data_dir, "ori_imgs", fid + ".lms"))
-            m = region_byte_map(self.H, self.W, np.array(frame["face_rect"], dtype=np.int32), landmark, parse)
+            m = self._region_map(fid, np.array(frame["face_rect"], dtype=np.int32))
             self.populations[i] = [int(((m >> g) & 1).sum()) for g in range(4)]
             for g in range(4):
                 if self.populations[i, g] < self.counts[g]:
@@ -203,7 +293,7 @@ class ResidentFrames:
         self.imgs = torch.empty((n, self.H, self.W, 3), dtype=torch.uint8, device=device)
         for i in range(n):
             self.maps[i].copy_(torch.from_numpy(maps[i]))
-            raw = _imread(img_paths[i])[..., ::-1].copy()        # upstream reads with cv2: BGR
+            raw = self._read_image(img_paths[i])
             if raw.shape != (self.H, self.W, 3):
                 raise ValueError(f"{img_paths[i]} is {raw.shape}, the clip's cx / cy say {(self.H, self.W, 3)}")
             self.imgs[i].copy_(torch.from_numpy(raw))
@@ -221,6 +311,28 @@ class ResidentFrames:
         if torch.device(device).type == "cuda":
             ops.byte_tables(device)                              # built here, so that batch() allocates nothing but its outputs
 
+    # ---- what the torso stage's loader (ResidentTorsoFrames) replaces
+    def _counts(self, args):
+        """(rect, outside, mouth, torso) picks of one batch."""
+        return ops.sample_counts(args.N_rand, args.mouth_rays, args.torso_rays, args.sample_rate)
+
+    def _region_map(self, fid, face_rect):
+        """The region byte map of frame `fid` (raises ValueError for a frame the sampler cannot serve)."""
+        parse = _imread(os.path.join(self.data_dir, "parsing", fid + ".png"))
+        if parse.shape[:2] != (self.H, self.W):
+            raise ValueError(f"frame {fid}: parsing image is {parse.shape[:2]}, the clip's cx / cy say {(self.H, self.W)}")
+        landmark = np.loadtxt(os.path.join(self.data_dir, "ori_imgs", fid + ".lms"))
+        return region_byte_map(self.H, self.W, face_rect, landmark, parse)
+
+    def _read_image(self, path):
+        return _imread(path)[..., ::-1].copy()                   # upstream reads with cv2: BGR
+
+    def _gather(self, index, sel):
+        """-> the sampled tensors of a batch, in the tuple's order."""
+        return ops.gather_rays(sel, self._cams[index], self.H, self.W, self.focal, self.imgs[index], self.background, self.cx, self.cy)
+
+    _no_sets = 2   # empty fields at the head of frame()'s tuple: batch_rays, target_s
+
     def __len__(self):
         return self.data_size
 
@@ -233,7 +345,7 @@ class ResidentFrames:
         target_s, which the eval forward never reads, are empty.  No file is read, no host meshgrid is built, nothing is copied
         from the device, nothing is allocated."""
         index = int(index)
-        return (self._no_rays, self._no_rays, self.background_unit, self.auds, self.imgs[index], self._poses_host[index],
+        return (*(self._no_rays,) * self._no_sets, self.background_unit, self.auds, self.imgs[index], self._poses_host[index],
                 self.exprs[index], index)
 
     def select(self, index, draw):
@@ -244,7 +356,43 @@ class ResidentFrames:
     def batch(self, index, draw):
         """-> (batch_rays [2, n, 3], target_s [n, 3], bc_rgb [n, 3], auds, raw_img, pose, expr, index), every tensor on the device."""
         index = int(index)
-        sel = self.select(index, draw)
-        batch_rays, target_s, bc_rgb = ops.gather_rays(sel, self._cams[index], self.H, self.W, self.focal, self.imgs[index],
-                                                       self.background, self.cx, self.cy)
-        return batch_rays, target_s, bc_rgb, self.auds, self.imgs[index], self.poses[index], self.exprs[index], index
+        return (*self._gather(index, self.select(index, draw)), self.auds, self.imgs[index], self.poses[index], self.exprs[index],
+                index)
+
+
+class ResidentTorsoFrames(ResidentFrames):
+    """``ResidentFrames`` for the torso stage: the resident counterpart of ``TorsoGetData``.  Same constructor arguments
+    (``args`` needs gt_dirs, N_rand, sample_rate, use_highlight); what differs from the head stage's loader:
+
+    - the byte map is ``torso_region_byte_map`` (no parsing image is read): bit 0 rect minus mouth box, bit 1 outside the rect,
+      bit 2 the first M outside-rect pixels in row-major order (M = the mouth box's population: what upstream's mouth block
+      really draws from), bit 3 clear; counts ``ops.sample_counts(N_rand, N_rand // 4 if use_highlight else 0, 0, sample_rate)``.
+      The sampler is the head stage's, unchanged: regions may overlap, and are drawn independently, as upstream's;
+    - the images are RGB;
+    - ``batch`` returns the 9-tuple (batch_rays, batch_rays_torso, target_s, bc_rgb, auds, raw_img, pose, expr, index), both ray
+      sets from one launch (``ops.gather_ray_pairs``; the second camera is the clip's frame-0 pose); ``frame`` the eval 9-tuple.
+
+    Beside ``ResidentFrames``' construction errors, ``ValueError`` where ``use_highlight`` is set and a frame's M exceeds its
+    outside population -- the frames on which upstream's mouth block can raise IndexError."""
+
+    _no_sets = 3
+
+    def _counts(self, args):
+        return ops.sample_counts(args.N_rand, torso_mouth_num(args.N_rand, args.use_highlight), 0, args.sample_rate)
+
+    def _region_map(self, fid, face_rect):
+        landmark = np.loadtxt(os.path.join(self.data_dir, "ori_imgs", fid + ".lms"))
+        *_, M = torso_region_masks(self.H, self.W, face_rect, landmark)
+        m = torso_region_byte_map(self.H, self.W, face_rect, landmark)
+        outside = int(((m >> 1) & 1).sum())
+        if self.args.use_highlight and M > outside:
+            raise ValueError(f"frame {fid}: the mouth box holds {M} pixels, more than the {outside} outside the face rect that "
+                             "the mouth block indexes with them (train_torso.py:168-169 raises IndexError there)")
+        return m
+
+    def _read_image(self, path):
+        return np.array(_imread(path))
+
+    def _gather(self, index, sel):
+        return ops.gather_ray_pairs(sel, self._cams[index], self._cams[0], self.H, self.W, self.focal, self.imgs[index],
+                                    self.background, self.cx, self.cy)

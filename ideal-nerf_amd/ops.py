@@ -217,10 +217,11 @@ def query_rays_train_fwd(packed, folded, rays, z, precision=_lib.IDN_PREC_BF16X6
     return raw, acts
 
 
-def pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
-    """Backward of one render pass (idealnerf_pass_bwd) from the slab of query_rays_train_fwd.  grads: as facenerf_bwd,
-    OVERWRITTEN; g_* = dL/d (rgb_map, rgb_fg, last_weight, acc_map), each may be None; d_aud / d_latent: accumulated."""
+def _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
+    """The checks and the call behind `pass_bwd` (grads: a dict) and `pass_bwd_cond` (grads: None)."""
     lib = _lib.load()
+    if grads is None:
+        grads = {}
     n, S = z.shape
     for t, name, shape in ((raw, "raw", (n, S, 4)), (rays, "rays", (n, RAY_FLOATS)), (bc, "bc_rgb", (n, 3)),
                            (g_rgb, "g_rgb_map", (n, 3)), (g_fg, "g_rgb_fg", (n, 3)), (g_lw, "g_last_weight", (n,)),
@@ -230,8 +231,24 @@ def pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g
     with _Launch(*tensors, *grads.values()) as L:
         ws = _workspace(lib.idealnerf_pass_bwd_workspace_bytes(n, S), z.device, L.stream)   # scratch of this (device, stream): two streams training on one GPU do not share it
         ptrs = [_ptr(t) for t in tensors]
-        check(lib.idealnerf_pass_bwd(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
+        if grads:
+            check(lib.idealnerf_pass_bwd(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
+        else:
+            check(lib.idealnerf_pass_bwd_cond(C.byref(p), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
     return grads
+
+
+def pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
+    """Backward of one render pass (idealnerf_pass_bwd) from the slab of query_rays_train_fwd.  grads: as facenerf_bwd,
+    OVERWRITTEN; g_* = dL/d (rgb_map, rgb_fg, last_weight, acc_map), each may be None; d_aud / d_latent: accumulated."""
+    return _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+
+
+def pass_bwd_cond(p, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
+    """`pass_bwd` for a network none of whose parameters takes a gradient (idealnerf_pass_bwd_cond): the same compositing
+    backward and delta chain, then only the column sums and the fold range d aud / d latent need.  d_aud / d_latent:
+    accumulated; nothing else is written."""
+    _pass_bwd(p, None, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
 
 
 def query_rays_fwd(packed, folded, rays, z, precision=IDN_PREC_F32) -> torch.Tensor:
@@ -698,27 +715,36 @@ def byte_tables(device):
     return t
 
 
-def gather_rays(sel, c2w, H, W, focal, image, background, cx=None, cy=None):
+def gather_rays(sel, c2w, H, W, focal, image, background, cx=None, cy=None, c2w_torso=None):
     """Rays and colours of the pixels `sel` (int64 [n], flat row-major) of one training frame (idealnerf_gather_rays) ->
     (batch_rays [2, n, 3], target_s [n, 3], bc_rgb [n, 3]) fp32.  image / background: uint8 [H, W, 3] on the device; c2w: the
-    camera on the HOST (it travels as kernel arguments), or `camera_floats` of it.  No [H W, 11] ray tensor exists."""
+    camera on the HOST (it travels as kernel arguments), or `camera_floats` of it.  No [H W, 11] ray tensor exists.
+    c2w_torso: `gather_ray_pairs`."""
     lib = _lib.load()
     _shape(sel, "sel", None)
     _shape(image, "image", H, W, 3)
     _shape(background, "background", H, W, 3)
     n = sel.shape[0]
-    m = camera_floats(c2w)
+    cams = [camera_floats(c2w)] + ([] if c2w_torso is None else [camera_floats(c2w_torso)])
     with _Launch(sel, image, background) as L:
         tt, tb = byte_tables(L.device)
-        batch_rays = torch.empty((2, n, 3), dtype=torch.float32, device=sel.device)
+        rays = [torch.empty((2, n, 3), dtype=torch.float32, device=sel.device) for _ in cams]
         target_s = torch.empty((n, 3), dtype=torch.float32, device=sel.device)
         bc_rgb = torch.empty((n, 3), dtype=torch.float32, device=sel.device)
-        check(lib.idealnerf_gather_rays(_ptr(sel, "sel", torch.int64), n, m, int(H), int(W), float(focal),
-                                        -1.0 if cx is None else float(cx), -1.0 if cy is None else float(cy),
-                                        _ptr(image, "image", torch.uint8), _ptr(background, "background", torch.uint8),
-                                        _ptr(tt, "target table"), _ptr(tb, "background table"),
-                                        batch_rays.data_ptr(), target_s.data_ptr(), bc_rgb.data_ptr(), L.stream))
-    return batch_rays, target_s, bc_rgb
+        entry = lib.idealnerf_gather_rays if c2w_torso is None else lib.idealnerf_gather_ray_pairs
+        check(entry(_ptr(sel, "sel", torch.int64), n, *cams, int(H), int(W), float(focal),
+                    -1.0 if cx is None else float(cx), -1.0 if cy is None else float(cy),
+                    _ptr(image, "image", torch.uint8), _ptr(background, "background", torch.uint8),
+                    _ptr(tt, "target table"), _ptr(tb, "background table"),
+                    *[r.data_ptr() for r in rays], target_s.data_ptr(), bc_rgb.data_ptr(), L.stream))
+    return (*rays, target_s, bc_rgb)
+
+
+def gather_ray_pairs(sel, c2w, c2w_torso, H, W, focal, image, background, cx=None, cy=None):
+    """`gather_rays` with the torso stage's second camera for the same pixels, in the same launch (idealnerf_gather_ray_pairs)
+    -> (batch_rays, batch_rays_torso, target_s, bc_rgb); batch_rays_torso [2, n, 3] is what `gather_rays` returns for c2w_torso,
+    bit for bit."""
+    return gather_rays(sel, c2w, H, W, focal, image, background, cx, cy, c2w_torso=c2w_torso)
 
 
 def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals, u, n_importance,

@@ -51,11 +51,15 @@ def xavier_state_dict(module, seed, sigma_gain=None, sigma_bias=None):
     return module
 
 
-def write_clip_directory(d, size, n_frames, seed=0, flat=False, N_rand=64, mouth_rays=8, torso_rays=4, sample_rate=0.95):
+def write_clip_directory(d, size, n_frames, seed=0, flat=False, N_rand=64, mouth_rays=8, torso_rays=4, sample_rate=0.95,
+                         dim_expr=76, face_rect=None, mouth_range=None):
     """An n_frames-frame directory in the reference's on-disk format (data_util/process_data.py:250-288), size x size: seeded
     poses, expressions, DeepSpeech windows and landmarks; face rect, mouth landmarks and torso rows at fixed fractions of the
     frame.  flat: every frame is one colour inside the face rect over the (other) background colour, instead of noise.
-    For tests and for tools/train_head.py's timing runs.  -> (loader flags as a namespace, the transforms metadata)."""
+    dim_expr: the length of the frames' `exp` vectors (the torso network's head pair takes 79); face_rect: [x, y, w, h] instead
+    of the fixed fraction; mouth_range: (lo, hi) the mouth landmarks are drawn from, on both axes, instead of the fixed fraction.
+    For tests and for tools/train_head.py's and tools/train_torso.py's timing runs.  -> (loader flags as a namespace, the
+    transforms metadata)."""
     import json
     import os
     from types import SimpleNamespace
@@ -65,7 +69,8 @@ def write_clip_directory(d, size, n_frames, seed=0, flat=False, N_rand=64, mouth
     k = size / 64.0
     for sub in ("head_imgs", "ori_imgs", "parsing"):
         os.makedirs(os.path.join(d, sub))
-    rect = [int(4 * k), int(4 * k), int(50 * k), int(50 * k)]
+    rect = [int(4 * k), int(4 * k), int(50 * k), int(50 * k)] if face_rect is None else [int(v) for v in face_rect]
+    mouth_lo, mouth_hi = (28 * k, 36 * k) if mouth_range is None else mouth_range
     face, back = np.array([40, 90, 200], np.uint8), np.array([200, 160, 30], np.uint8)
     bc = np.broadcast_to(back, (H, W, 3)).copy() if flat else rs.randint(0, 255, (H, W, 3), dtype=np.uint8)
     frames = []
@@ -80,11 +85,11 @@ def write_clip_directory(d, size, n_frames, seed=0, flat=False, N_rand=64, mouth
         par[int(50 * k):, int(4 * k):int(60 * k)] = (255, 0, 0)
         Image.fromarray(par).save(os.path.join(d, "parsing", f"{i}.png"))
         lms = rs.uniform(6 * k, 58 * k, (68, 2))
-        lms[48:] = rs.uniform(28 * k, 36 * k, (20, 2))
+        lms[48:] = rs.uniform(mouth_lo, mouth_hi, (20, 2))
         np.savetxt(os.path.join(d, "ori_imgs", f"{i}.lms"), lms)
         c2w = torch.cat([frame(H, W, seed=seed + 20 + (0 if flat else i))["c2w"], torch.tensor([[0.0, 0.0, 0.0, 1.0]])], 0)
         frames.append({"img_id": i, "aud_id": n_frames - 1 - i, "transform_matrix": c2w.double().tolist(),
-                       "face_rect": rect, "exp": rs.standard_normal(76).tolist()})
+                       "face_rect": rect, "exp": rs.standard_normal(dim_expr).tolist()})
     Image.fromarray(bc).save(os.path.join(d, "bc.jpg"), quality=95)
     np.save(os.path.join(d, "aud.npy"), rs.standard_normal((n_frames, 16, 29)).astype(np.float32))
     meta = {"focal_len": 1200.0 * W / 450.0, "cx": W / 2, "cy": H / 2, "frames": frames}

@@ -41,6 +41,13 @@ def train_step(network, optimizer, data, latent_codes, global_step, dataset_size
         loss = loss + img2mse(extras['rgb0'], target)
     latent_code_loss = torch.norm(latent_code) * network.args.lc_weight
     loss = loss + latent_code_loss * 10
+    new_lrate = _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay)
+    return dict(loss=loss.detach(), psnr=psnr, latent_code_loss=latent_code_loss.detach(), lr=new_lrate)
+
+
+def _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay):
+    """The tail both stages' steps share: backward, the gradient all-reduce inside a process group, the Adam step and the
+    decayed learning rate for the next one -> that rate."""
     loss.backward()
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         from .parallel import average_gradients   # one bucketed all-reduce; a no-op for a single rank
@@ -49,7 +56,25 @@ def train_step(network, optimizer, data, latent_codes, global_step, dataset_size
     new_lrate = decayed_lr(lrate, lrate_decay, global_step)
     for group in optimizer.param_groups:
         group['lr'] = new_lrate
-    return dict(loss=loss.detach(), psnr=psnr, latent_code_loss=latent_code_loss.detach(), lr=new_lrate)
+    return new_lrate
+
+
+def torso_train_step(network, optimizer, data, latent_codes, global_step, dataset_size, lrate=5e-4, lrate_decay=500):
+    """One iteration of the torso stage's loop (NeRFs/TorsoNeRF/train_torso.py:516-541) on ``train_torso.Network``: ``data`` is
+    the torso loader's 9-tuple (batch_rays, batch_rays_torso, target_s, bg_img, auds, raw_img, pose, expr, index); the loss is
+    mse(rgb_com, target) + mse(rgb_com0, target), with no latent term.  ``optimizer`` holds what the stage trains (the torso
+    pair and the audio nets); a head pair whose parameters do not require gradients runs the conditioning-only backward."""
+    batch_rays, batch_rays_torso, target_s, bg_img, auds, raw_img, pose, expr, index = data
+    latent_code = latent_codes[int(index)]
+    rgb, rgb0 = network([(batch_rays, batch_rays_torso, target_s, bg_img, auds, raw_img, pose, expr, latent_code, index),
+                         global_step, dataset_size])
+    target = target_s.reshape(-1, 3).to(rgb.device, torch.float32)
+    optimizer.zero_grad()
+    img_loss = img2mse(rgb, target)
+    psnr = mse2psnr(img_loss.detach())
+    loss = img_loss + img2mse(rgb0, target)
+    new_lrate = _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay)
+    return dict(loss=loss.detach(), psnr=psnr, lr=new_lrate)
 
 
 logger = logging.getLogger("adnerf")
@@ -64,9 +89,10 @@ def draw_index(global_step, rank=0, world=1):
 
 
 def _as_loader_item(item):
-    """What the reference's DataLoader makes of a GetData item, as far as Network.forward reads it: the pose as a tensor."""
-    batch_rays, target_s, bc_rgb, auds, raw_img, pose, expr, index = item
-    return batch_rays, target_s, bc_rgb, auds, raw_img, torch.as_tensor(pose, dtype=torch.float32), expr, index
+    """What the reference's DataLoader makes of a GetData item (either stage's: the tuples end in raw_img, pose, expr, index), as
+    far as Network.forward reads it: the pose as a tensor."""
+    *head, pose, expr, index = item
+    return (*head, torch.as_tensor(pose, dtype=torch.float32), expr, index)
 
 
 def _summary_writer(logdir):
@@ -120,7 +146,6 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if dist_on else (0, 1)
     basedir, expname = args.basedir, args.expname
     run_dir = os.path.join(basedir, expname)
-    N_iters = args.N_iters + 1
 
     if loader == "resident":
         dataset_train = dataset.ResidentFrames(args.datadir, args.aud_file, "train", args, device=device, max_bytes=max_bytes,
@@ -157,28 +182,50 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
             global_step, saved_codes = checkpoint.load_checkpoint(ckpt_path, network, optimizer, map_location=device)
             latent_codes.data = saved_codes.to(device)
 
+    network.train()
+
+    def validate(step):
+        if frames_val is None:
+            return validation_frame(network, dataset_val, latent_codes, step, sample_seed), None
+        return resident_validation_frame(network, frames_val, latent_codes, step, sample_seed)
+
+    global_step = _run_epochs(
+        args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step,
+        batch=lambda it, step: (dataset_train.batch(it, draw_index(step, rank, world)) if loader == "resident"
+                                else _as_loader_item(dataset_train[it])),
+        step_fn=lambda data, step: train_step(network, optimizer, data, latent_codes, step, data_size, lrate=args.lrate,
+                                              lrate_decay=args.lrate_decay),
+        scalars_of=lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"],
+                                     latent_code_loss=info["latent_code_loss"].item()),
+        log_line=lambda sc: f"LatentLoss: {sc['latent_code_loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}",
+        validate=validate, checkpoint_name=lambda epoch: 'head.tar')
+    return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
+
+
+def _run_epochs(args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step, *, batch, step_fn,
+                scalars_of, log_line, validate, checkpoint_name):
+    """The skeleton both stages' ``train`` share (audio_exp_nerf.py:527-593, train_torso.py:509-574): epochs over the frames
+    in order from ``global_step`` on, and per step ``step_fn(batch(it, global_step), global_step)``, the log line every
+    ``i_print`` steps, ``validate(global_step) -> (image, scores or None)`` every ``100 * i_print`` and the checkpoint
+    ``checkpoint_name(epoch)`` every ``i_weights`` -- recording the COMPLETED steps; a resumed run enters its first epoch at
+    frame ``global_step % data_size``.  Rank 0 alone logs, validates and saves.  -> the global step reached."""
+    from . import checkpoint
+    run_dir = os.path.join(args.basedir, args.expname)
+    N_iters = args.N_iters + 1
     writer = _summary_writer(run_dir) if rank == 0 else None
     start = int(global_step / data_size)
     logger.info(f"start: {start}, global_step:{global_step}")
-    network.train()
     done = 0
     try:
         for epoch in range(start, N_iters):
             for it in range(global_step % data_size if epoch == start else 0, data_size):
                 if steps is not None and done >= steps:
                     break
-                if loader == "resident":
-                    data = dataset_train.batch(it, draw_index(global_step, rank, world))
-                else:
-                    data = _as_loader_item(dataset_train[it])
-                info = train_step(network, optimizer, data, latent_codes, global_step, data_size, lrate=args.lrate,
-                                  lrate_decay=args.lrate_decay)
+                info = step_fn(batch(it, global_step), global_step)
 
                 if global_step % args.i_print == 0 and rank == 0:
-                    scalars = dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"],
-                                   latent_code_loss=info["latent_code_loss"].item())
-                    logger.info(f"[TRAIN] epoch: {epoch} Iter: {it} LatentLoss: {scalars['latent_code_loss']}  "
-                                f"PSNR: {scalars['psnr']} LR: {info['lr']}")
+                    scalars = scalars_of(info)
+                    logger.info(f"[TRAIN] epoch: {epoch} Iter: {it} {log_line(scalars)}")
                     for k, v in scalars.items():
                         if writer is not None:
                             writer.add_scalar('train/' + k, v, global_step=global_step)
@@ -186,10 +233,7 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
                         on_log("train", global_step, scalars)
 
                 if global_step % (100 * args.i_print) == 0 and rank == 0:
-                    if frames_val is None:
-                        image, scores = validation_frame(network, dataset_val, latent_codes, global_step, sample_seed), None
-                    else:
-                        image, scores = resident_validation_frame(network, frames_val, latent_codes, global_step, sample_seed)
+                    image, scores = validate(global_step)
                     if writer is not None:
                         writer.add_image("val/rgb_fine", image, global_step=global_step)
                         if scores is not None:
@@ -202,7 +246,7 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
                     logger.info('Saved test set and turn back to trainning mode')
 
                 if global_step % args.i_weights == 0 and rank == 0:
-                    path = os.path.join(run_dir, 'head.tar')
+                    path = os.path.join(run_dir, checkpoint_name(epoch))
                     checkpoint.save_checkpoint(path, network, optimizer, latent_codes, global_step + 1)
                     logger.info(f'Saved checkpoints at {path} and start to test with network')
                 global_step += 1
@@ -214,7 +258,7 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     finally:
         if writer is not None:
             writer.close()
-    return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
+    return global_step
 
 
 def _validation_index(n, global_step, sample_seed):
@@ -222,41 +266,45 @@ def _validation_index(n, global_step, sample_seed):
     return int(torch.randint(n, (1,), generator=gen))
 
 
-def validation_frame(network, dataset_val, latent_codes, global_step, sample_seed=0):
+def validation_frame(network, dataset_val, latent_codes, global_step, sample_seed=0, flip=True):
     """audio_exp_nerf.py:568-581: one randomly chosen validation frame rendered in eval mode under no_grad with
     ``latent_codes[0]``, stacked over its ground truth, channels flipped to RGB -> [3, 2 H, W] on the host; the network
     goes back to train mode.  The frame is chosen by a generator of its own seeded from (sample_seed, global_step) --
-    upstream shuffles its validation loader -- so a validation neither depends on nor disturbs the training draws."""
+    upstream shuffles its validation loader -- so a validation neither depends on nor disturbs the training draws.
+    Either stage's loader and network: the item ends in (raw_img, pose, expr, index) and the forward's first output is the
+    frame; flip=False for the torso stage, whose images are RGB already (train_torso.py:558-560)."""
     val_i = _validation_index(len(dataset_val), global_step, sample_seed)
     network.eval()
     try:
-        batch_rays, target_s, bg_img, auds, raw_img, pose, expr, index = _as_loader_item(dataset_val[val_i])
-        data = batch_rays, target_s, bg_img, auds, raw_img, pose, expr, latent_codes[0], index
+        item = _as_loader_item(dataset_val[val_i])
         with torch.no_grad():
-            rgb, _, _, _, _ = network([data, global_step, dataset_val.data_size])
+            rgb = network([(*item[:-1], latent_codes[0], item[-1]), global_step, dataset_val.data_size])[0]
     finally:
         network.train()
+    return _pred_over_label(rgb, item[-4], flip)
+
+
+def _pred_over_label(rgb, raw_img, flip):
     pred_with_label = torch.cat((rgb.cpu().permute(2, 0, 1), raw_img.cpu().permute(2, 0, 1) / 255.0), dim=1)
-    return pred_with_label[[2, 1, 0], :, :]
+    return pred_with_label[[2, 1, 0], :, :] if flip else pred_with_label
 
 
-def resident_validation_frame(network, frames_val, latent_codes, global_step, sample_seed=0):
-    """``validation_frame`` from a resident validation clip (``dataset.ResidentFrames(mode="val")``): the same frame index from
-    the same generator, the frame's inputs from ``frames_val.frame`` (no file read, no host meshgrid), and the render scored on
-    the device against the frame's ground truth, whole frame and per sampling region (``ops.frame_scores``) -> (image as
-    ``validation_frame``, dict(frame, groups, mse, psnr, ssim) with one float per ``ops.SCORE_GROUPS``; nan where a group has no
-    pixel or window).  The scores are read back here, together with the image: the validation moment's one host sync."""
+def resident_validation_frame(network, frames_val, latent_codes, global_step, sample_seed=0, flip=True):
+    """``validation_frame`` from a resident validation clip (``dataset.ResidentFrames(mode="val")``, or the torso stage's): the
+    same frame index from the same generator, the frame's inputs from ``frames_val.frame`` (no file read, no host meshgrid), and
+    the render scored on the device against the frame's ground truth, whole frame and per sampling region
+    (``ops.frame_scores``) -> (image as ``validation_frame``, dict(frame, groups, mse, psnr, ssim) with one float per
+    ``ops.SCORE_GROUPS``; nan where a group has no pixel or window).  The scores are read back here, together with the image:
+    the validation moment's one host sync."""
     from . import ops
     val_i = _validation_index(len(frames_val), global_step, sample_seed)
     network.eval()
     try:
         data = frames_val.frame(val_i)
         with torch.no_grad():
-            rgb, _, _, _, _ = network([(*data[:7], latent_codes[0], data[7]), global_step, frames_val.data_size])
+            rgb = network([(*data[:-1], latent_codes[0], data[-1]), global_step, frames_val.data_size])[0]
             table = ops.frame_scores(rgb, frames_val.imgs[val_i], frames_val.maps[val_i])
     finally:
         network.train()
-    raw_img = data[4]
-    pred_with_label = torch.cat((rgb.cpu().permute(2, 0, 1), raw_img.cpu().permute(2, 0, 1) / 255.0), dim=1)
     scores = {k: [float(x) for x in v] for k, v in ops.summarise_scores(table).items()}
-    return pred_with_label[[2, 1, 0], :, :], dict(scores, frame=val_i, groups=list(ops.SCORE_GROUPS))
+    return _pred_over_label(rgb, data[-4], flip), dict(scores, frame=val_i, groups=list(ops.SCORE_GROUPS))

@@ -119,3 +119,97 @@ class Network(HeadNetwork):
             all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
         k_extract = ['rgb_map', 'disp_map', 'acc_map', 'last_weight', 'rgb_map_fg']
         return [all_ret[k] for k in k_extract] + [{k: v for k, v in all_ret.items() if k not in k_extract}]
+
+
+def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30,
+          val="reference"):
+    """The reference's torso-stage ``train()`` (NeRFs/TorsoNeRF/train_torso.py:443-574) on the flags ``args``
+    (``config_parser().parse_args()``): write_config, the datasets, ``Network`` + ``init_weights`` (the head pair's expression
+    width is the length of the clip's ``exp`` vectors: upstream's literal 79 on upstream's data), ``latent_codes = ones[n, 32]``
+    (saved, not optimised), Adam over the torso pair and the two audio nets only, the newest ``*head.tar*`` of
+    ``basedir/expname`` with strict=False (and its latent codes), then the newest ``*torso.tar*`` strictly (latent codes, step,
+    optimiser state), and ``train.train``'s loop: a log line every ``i_print`` steps, one validation frame every
+    ``100 * i_print`` (rendered by ``Network.forward`` in eval mode -- the torso pair at the frame's own pose, as upstream --
+    and stacked over its truth without a channel flip: the torso loader's images are RGB) and ``{epoch:06d}_torso.tar`` every
+    ``i_weights``.
+
+    The head pair is in eval mode and its parameters do not require gradients: its backward is the conditioning-only plan
+    (``autograd.RenderRaysFn.backward``), and its weights leave training bit for bit as they entered.
+
+    loader / val / steps / sample_seed / on_log / on_step / max_bytes and the two departures from upstream (the checkpoint
+    records COMPLETED steps; a resumed run enters its epoch at ``global_step % n_frames``): as ``train.train`` -- with
+    ``dataset.ResidentTorsoFrames`` and ``dataset.TorsoGetData`` as the two loaders.  ``on_log("train", ...)`` carries
+    {loss, psnr, learning_rate}.  -> dict(network, optimizer, latent_codes, global_step, data_size)."""
+    import os
+    from . import checkpoint, dataset, train as T
+    from .audio_exp_nerf import init_weights
+    from .config import to_render_config
+    from .helper import write_config
+
+    if loader not in ("resident", "reference"):
+        raise ValueError(f"loader must be 'resident' or 'reference', got {loader!r}")
+    if val not in ("reference", "resident"):
+        raise ValueError(f"val must be 'reference' or 'resident', got {val!r}")
+    dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
+    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if dist_on else (0, 1)
+    run_dir = os.path.join(args.basedir, args.expname)
+
+    if loader == "resident":
+        dataset_train = dataset.ResidentTorsoFrames(args.datadir, args.aud_file, "train", args, device=device, max_bytes=max_bytes,
+                                                    seed=sample_seed)
+    else:
+        dataset_train = dataset.TorsoGetData(args.datadir, args.aud_file, mode="train", args=args, device=device)
+    dataset_val = dataset.TorsoGetData(args.datadir, args.aud_file, mode="val", args=args, skip=args.testskip, device=device)
+    T.logger.info(f'dataset_val length: {dataset_val.data_size}')
+    frames_val = None
+    if val == "resident" and rank == 0:
+        frames_val = dataset.ResidentTorsoFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device,
+                                                 max_bytes=max_bytes, seed=sample_seed)
+    data_size = dataset_train.data_size
+    if rank == 0:
+        write_config(args)
+
+    cfg = to_render_config(args)
+    cfg.dim_expr = len(dataset_val.all_exprs[0])
+    network = Network(dataset_val.H, dataset_val.W, dataset_val.focal, near=args.near, far=args.far, chunk=args.chunk,
+                      N_samlpes=args.N_samples, N_importance=args.N_importance, args=cfg, dim_aud_body=args.dim_aud_body,
+                      dim_expr_head=cfg.dim_expr).to(device)
+    latent_codes = torch.ones(data_size, 32, dtype=torch.float32, device=device)
+    network.apply(init_weights)
+    trained = [p for m in (network.torso_coarse_nerf, network.torso_fine_nerf, network.aud_net, network.aud_att_net)
+               for p in m.parameters()]
+    optimizer = torch.optim.Adam(params=trained, lr=args.lrate, betas=(0.9, 0.999))
+
+    global_step = 0
+    if args.ft_path is None or args.ft_path == 'None':
+        head_path = checkpoint.latest_checkpoint(run_dir, contains="head.tar")
+        if head_path is not None:
+            T.logger.info(f'Found ckpts:{head_path}')
+            _, saved_codes = checkpoint.load_checkpoint(head_path, network, map_location=device, strict=False)
+            latent_codes.data = saved_codes.to(device)
+        torso_path = checkpoint.latest_checkpoint(run_dir, contains="torso.tar")
+        if torso_path is not None:
+            T.logger.info(f'Found ckpts:{torso_path}')
+            global_step, saved_codes = checkpoint.load_checkpoint(torso_path, network, optimizer, map_location=device)
+            latent_codes.data = saved_codes.to(device)
+
+    network.train()
+    for m in (network.face_nerf_coarse, network.face_nerf_fine):   # frozen in this stage (train_torso.py:476-479, 512-513)
+        m.requires_grad_(False)
+        m.eval()                                                   # (as upstream, until the first validation's network.train())
+
+    def validate(step):
+        if frames_val is None:
+            return T.validation_frame(network, dataset_val, latent_codes, step, sample_seed, flip=False), None
+        return T.resident_validation_frame(network, frames_val, latent_codes, step, sample_seed, flip=False)
+
+    global_step = T._run_epochs(
+        args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step,
+        batch=lambda it, step: (dataset_train.batch(it, T.draw_index(step, rank, world)) if loader == "resident"
+                                else T._as_loader_item(dataset_train[it])),
+        step_fn=lambda data, step: T.torso_train_step(network, optimizer, data, latent_codes, step, data_size, lrate=args.lrate,
+                                                      lrate_decay=args.lrate_decay),
+        scalars_of=lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"]),
+        log_line=lambda sc: f" PSNR: {sc['psnr']} LR: {sc['learning_rate']}",
+        validate=validate, checkpoint_name=lambda epoch: '{:06d}_torso.tar'.format(epoch))
+    return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)

@@ -317,6 +317,17 @@ int idealnerf_gather_rays(const int64_t* sel, int64_t n, const float* c2w, int H
                           float* batch_rays, float* target_s, float* bc_rgb, void* stream);
 
 /*
+ * idealnerf_gather_ray_pairs: idealnerf_gather_rays with a second camera for the same pixels, in the same launch -- the torso
+ * stage's loader (NeRFs/TorsoNeRF/train_torso.py:130-183), whose batch_rays_torso are the selected pixels seen from the clip's
+ * frame-0 pose.  batch_rays_torso [2, n, 3] comes from c2w_torso by the same operations in the same order as batch_rays from
+ * c2w: each equals what idealnerf_gather_rays writes for that camera, bit for bit.  Additive entry: the ABI version is unchanged.
+ */
+int idealnerf_gather_ray_pairs(const int64_t* sel, int64_t n, const float* c2w, const float* c2w_torso, int H, int W, float focal,
+                               float cx, float cy, const uint8_t* image, const uint8_t* background, const float* target_table,
+                               const float* background_table, float* batch_rays, float* batch_rays_torso, float* target_s,
+                               float* bc_rgb, void* stream);
+
+/*
  * Frame scores: how far a rendered frame is from its ground truth, on the device.  Additive entries: the ABI version is unchanged.
  *
  * pred [H, W, 3] fp32, truth [H, W, 3] uint8, regions [H, W] uint8 (the region byte map idealnerf_sample_pixels draws from: bit 0
@@ -439,6 +450,21 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
                        const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
                        const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
                        float* d_latent, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * idealnerf_pass_bwd for a FROZEN network (the head pair of the torso stage, train_torso.py:476-479): none of its parameters
+ * takes a gradient, but the conditioning it was given does.  The arguments of idealnerf_pass_bwd without `grads`, the same
+ * workspace size; d_aud / d_latent are ACCUMULATED (+=) exactly as idealnerf_pass_bwd documents, and nothing else is written.
+ * It runs that entry's compositing backward and delta chain, then -- instead of the sixteen weight-gradient products -- the
+ * column sums of the two delta matrices the conditioning reaches (pts_linears.0 and .5; fp64, fixed order, no atomics: the
+ * result is a function of the inputs alone) and the conditioning range of the fold.  Both d_aud and d_latent NULL: nothing
+ * is launched.  Additive entry: the ABI version is unchanged.
+ */
+int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, const float* expr, const float* latent,
+                            const float* acts, const float* raw, const float* z, const float* rays, const float* bc_rgb,
+                            int64_t n_rays, int n_samples, const float* g_rgb_map, const float* g_rgb_fg,
+                            const float* g_last_weight, const float* g_acc, float* d_aud, float* d_latent, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /*
  * FaceNeRF.forward with gradients (models/face_nerf.py:40-80): the module trained on pre-embedded rows, outside
