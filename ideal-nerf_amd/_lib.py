@@ -66,6 +66,24 @@ class RenderOpts(C.Structure):
     _fields_ = [("colour_gate", C.c_int), ("gate_counters", fp)]
 
 
+DW_MAX_PRODUCTS, DW_MAX_TAKES, DW_MAX_COLSUM_TAKES = 16, 4, 2   # IDN_DW_MAX_*
+
+
+class DwTake(C.Structure):
+    _fields_ = [("row0", C.c_int), ("col0", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("out", fp), ("ldo", C.c_int)]
+
+
+class DwColsumTake(C.Structure):
+    _fields_ = [("col0", C.c_int), ("cols", C.c_int), ("out", fp)]
+
+
+class DwProduct(C.Structure):
+    _fields_ = [("delta", fp), ("ld_delta", C.c_int), ("N", C.c_int), ("acts", fp), ("ld_acts", C.c_int), ("K", C.c_int),
+                ("acts2", fp), ("want_colsum", C.c_int), ("n_takes", C.c_int), ("takes", DwTake * DW_MAX_TAKES),
+                ("n_colsum_takes", C.c_int), ("colsum_takes", DwColsumTake * DW_MAX_COLSUM_TAKES),
+                ("splits", C.c_int), ("chunks_per_split", C.c_int)]
+
+
 ABI_VERSION = 4   # idealnerf_version(): 4 since idn_render_args carries `rng_mode / rng_seed / rng_ray0` (3: `fused_march`)
 
 # name -> (restype, argtypes); mirrors include/idealnerf.h one to one
@@ -123,6 +141,8 @@ PROTOTYPES = {
                                          fp, fp, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_dw_gemm_workspace_bytes": (C.c_size_t, []),
     "idealnerf_dw_gemm": (C.c_int, [fp, C.c_int, fp, C.c_int, C.c_int64, fp, fp, C.c_int, fp, C.c_size_t, fp]),
+    "idealnerf_dw_products_workspace_bytes": (C.c_size_t, []),
+    "idealnerf_dw_products": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(DwProduct), C.c_int, fp, C.c_size_t, fp]),
     "idealnerf_profile_begin": (None, []),
     "idealnerf_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "idealnerf_profile_end_kinds": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -422,6 +422,13 @@ int idealnerf_dw_gemm(const float* delta, int ld_delta, const float* acts, int l
     return launch_dw_gemm(delta, ld_delta, acts, ld_acts, rows, dW, db, pipe, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+size_t idealnerf_dw_products_workspace_bytes(void) { return dw_products_workspace_bytes(); }
+
+int idealnerf_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* products, int n, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return launch_dw_products(rows, pipe, x6_items, products, n, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 void idealnerf_profile_begin(void) {
     g_prof_n = 0;
     g_prof_on = true;

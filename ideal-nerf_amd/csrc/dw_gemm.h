@@ -81,8 +81,8 @@ constexpr size_t kPartPoolFloats = (size_t)kMaxSplits * kPartFloatsPerSplit, kCp
 static_assert(pass_sum(kPipeX6, 1) <= kPartFloatsPerSplit && pass_sum(kPipeF32, 1) <= kPartFloatsPerSplit, "a pass's partial blocks fit");
 static_assert(kMaxSplits * pass_sum(kPipeX6, 2) <= kCpartPoolFloats && kMaxSplits * pass_sum(kPipeF32, 2) <= kCpartPoolFloats, "a pass's column sums fit");
 
-// where a product's partial blocks went: part [splits][N][K], cpart [splits][N] or null
-struct DwProduct { const float *part, *cpart; int splits, N, K; };
+// where a product's partial blocks went: part [splits][N][K], cpart [splits][N] or null; chunks_per_split: what its kernel was given
+struct DwProduct { const float *part, *cpart; int splits, N, K, chunks_per_split; };
 
 // The dW products of ONE backward pass over P rows: fp32 products launch as they are named, the 256 x 256 bf16-piece products
 // and every reduction are queued; finish() launches the x6 batch, then one reduce_batch_kernel.  Fixed-size, on the stack.

@@ -705,7 +705,7 @@ int DwPass::product(const float* A, int lda, int N, const float* B, int ldb, int
         ProfScope prof(s, P, IDN_PROF_DW_GEMM);
         if (int e = sh->launch(g, splits, s)) return e;
     }
-    *h = DwProduct{g.part, g.cpart, splits, N, K};
+    *h = DwProduct{g.part, g.cpart, splits, N, K, cps};
     part_next += part_floats, part_left -= part_floats;
     cpart_next += cpart_floats, cpart_left -= cpart_floats;
     return IDN_OK;
@@ -719,7 +719,7 @@ int DwPass::take(const DwProduct& h, int row0, int col0, int rows, int cols, flo
 }
 int DwPass::take_colsum(const DwProduct& h, int col0, int cols, float* out) {   // the column sums are a 1 x N block per split
     if (!h.cpart) return fail(IDN_EINVAL, "gemm_tn: the product kept no column sums");
-    return take(DwProduct{h.cpart, nullptr, h.splits, 1, h.N}, 0, col0, 1, cols, out, cols);
+    return take(DwProduct{h.cpart, nullptr, h.splits, 1, h.N, h.chunks_per_split}, 0, col0, 1, cols, out, cols);
 }
 
 int DwPass::finish() {   // once: the queues are not reset
@@ -751,6 +751,82 @@ int launch_dw_gemm(const float* delta, int ld_delta, const float* acts, int ld_a
     int e = db ? q.take_colsum(h, 0, 256, db) : IDN_OK;
     if (!e) e = q.take(h, 0, 0, 256, 256, dW, 256);
     return e ? e : q.finish();
+}
+
+// A list of products through ONE DwPass over pools of a pass's size (carve_bwd, train.hip), named as bwd_tail names them:
+// product, its column-sum takes, its takes; finish.  Everything that can be refused without the device is refused in a first
+// walk over the records, before DwPass::product touches HIP (it opts the x6 kernel into its LDS and launches the fp32 shapes
+// as they are named).
+size_t dw_products_workspace_bytes() { return al256(kPartPoolFloats * 4) + al256(kCpartPoolFloats * 4); }
+int launch_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* pr, int n, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (!pr) return fail(IDN_EINVAL, "dw_products: NULL pointer");
+    if (n < 1 || n > IDN_DW_MAX_PRODUCTS) return fail(IDN_EINVAL, "dw_products: %d products outside [1, %d]", n, IDN_DW_MAX_PRODUCTS);
+    if (pipe != kPipeX6 && pipe != kPipeF32) return fail(IDN_EINVAL, "dw_products: pipe %d", pipe);
+    if (rows <= 0 || rows % 128) return fail(IDN_EINVAL, "dw_products: rows %lld is not a positive multiple of 128", (long long)rows);
+    if (rows > (int64_t)1 << 24) return fail(IDN_EUNSUPPORTED, "dw_products: rows %lld exceed 2^24", (long long)rows);
+    if (pipe == kPipeX6 && (x6_items < 1 || x6_items > kMaxTnBatch))
+        return fail(IDN_EINVAL, "dw_products: x6_items %d outside [1, %d]", x6_items, kMaxTnBatch);
+    int n_x6 = 0, n_red = 0;
+    size_t part_per_split = 0, cpart_per_split = 0;
+    for (int i = 0; i < n; ++i) {
+        const idn_dw_product& t = pr[i];
+        if (!t.delta || !t.acts) return fail(IDN_EINVAL, "dw_products: product %d: NULL pointer", i);
+        const bool x6 = t.N == 256 && t.K == 256 && pipe == kPipeX6;
+        bool known = x6;
+        for (const DwShape& sh : kF32Shapes) known = known || (sh.N == t.N && sh.K == t.K);
+        if (!known) return fail(IDN_EUNSUPPORTED, "dw_products: product %d: no instantiation for %d x %d", i, t.N, t.K);
+        const int b_cols = t.acts2 ? 128 : t.K;   // a split B: two 128-column matrices
+        if (t.ld_delta < t.N || t.ld_acts < b_cols) return fail(IDN_EINVAL, "dw_products: product %d: row pitch %d / %d < %d / %d", i, t.ld_delta, t.ld_acts, t.N, b_cols);
+        // the fp32 kernels move 16-byte pieces of a row
+        if (t.ld_delta % 4 || t.ld_acts % 4 || ((uintptr_t)t.delta | (uintptr_t)t.acts | (uintptr_t)t.acts2) % 16)
+            return fail(IDN_EINVAL, "dw_products: product %d: operands are not 16-byte aligned row by row", i);
+        if (t.acts2 && !x6) return fail(IDN_EINVAL, "dw_products: product %d: a split B needs the 256 x 256 bf16-piece kernel", i);
+        if (t.acts2) {   // the kernel reaches both matrices from the lower address with 32-bit byte offsets (DwPass::product)
+            const uintptr_t lo = (uintptr_t)(t.acts < t.acts2 ? t.acts : t.acts2), hi = (uintptr_t)(t.acts < t.acts2 ? t.acts2 : t.acts);
+            if (hi - lo >= (uintptr_t)1 << 31) return fail(IDN_EUNSUPPORTED, "dw_products: product %d: split B matrices more than 2 GiB apart", i);
+        }
+        if (x6 && ++n_x6 > x6_items) return fail(IDN_EINVAL, "dw_products: more 256 x 256 products than x6_items (%d)", x6_items);
+        if (t.n_takes < 0 || t.n_takes > IDN_DW_MAX_TAKES || t.n_colsum_takes < 0 || t.n_colsum_takes > IDN_DW_MAX_COLSUM_TAKES)
+            return fail(IDN_EINVAL, "dw_products: product %d: %d takes / %d column-sum takes", i, t.n_takes, t.n_colsum_takes);
+        if (t.n_colsum_takes && !t.want_colsum) return fail(IDN_EINVAL, "dw_products: product %d kept no column sums", i);
+        if ((n_red += t.n_takes + t.n_colsum_takes) > kMaxReduceItems)
+            return fail(IDN_EINVAL, "dw_products: more than %d takes in one pass", kMaxReduceItems);
+        for (int j = 0; j < t.n_takes; ++j) {
+            const idn_dw_take& k = t.takes[j];
+            if (!k.out) return fail(IDN_EINVAL, "dw_products: product %d take %d: NULL pointer", i, j);
+            if (k.row0 < 0 || k.col0 < 0 || k.rows < 1 || k.cols < 1 || k.row0 + k.rows > t.N || k.col0 + k.cols > t.K || k.ldo < k.cols)
+                return fail(IDN_EINVAL, "dw_products: product %d take %d leaves the %d x %d block (or its pitch is short)", i, j, t.N, t.K);
+        }
+        for (int j = 0; j < t.n_colsum_takes; ++j) {
+            const idn_dw_colsum_take& k = t.colsum_takes[j];
+            if (!k.out) return fail(IDN_EINVAL, "dw_products: product %d column-sum take %d: NULL pointer", i, j);
+            if (k.col0 < 0 || k.cols < 1 || k.col0 + k.cols > t.N)
+                return fail(IDN_EINVAL, "dw_products: product %d column-sum take %d leaves the %d columns", i, j, t.N);
+        }
+        part_per_split += (size_t)t.N * t.K;
+        cpart_per_split += t.want_colsum ? t.N : 0;
+    }
+    // no product runs more than kMaxSplits splits: the list fits the pools if one split of it does (as a pass's does, dw_gemm.h)
+    if (part_per_split > kPartFloatsPerSplit || cpart_per_split * kMaxSplits > kCpartPoolFloats)
+        return fail(IDN_EWORKSPACE, "dw_products: the list's partial blocks do not fit the pools of a pass");
+    if (!ws || ws_bytes < dw_products_workspace_bytes())
+        return fail(IDN_EWORKSPACE, "dw_products workspace %zu < %zu", ws_bytes, dw_products_workspace_bytes());
+    float* part = reinterpret_cast<float*>(ws);
+    float* cpart = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + al256(kPartPoolFloats * 4));
+    DwPass q(part, kPartPoolFloats, cpart, kCpartPoolFloats, rows, pipe, x6_items, s);
+    for (int i = 0; i < n; ++i) {
+        idn_dw_product& t = pr[i];
+        DwProduct h;
+        if (int e = q.product(t.delta, t.ld_delta, t.N, t.acts, t.ld_acts, t.K, t.want_colsum != 0, &h, t.acts2)) return e;
+        for (int j = 0; j < t.n_colsum_takes; ++j)
+            if (int e = q.take_colsum(h, t.colsum_takes[j].col0, t.colsum_takes[j].cols, t.colsum_takes[j].out)) return e;
+        for (int j = 0; j < t.n_takes; ++j) {
+            const idn_dw_take& k = t.takes[j];
+            if (int e = q.take(h, k.row0, k.col0, k.rows, k.cols, k.out, k.ldo)) return e;
+        }
+        t.splits = h.splits, t.chunks_per_split = h.chunks_per_split;
+    }
+    return q.finish();
 }
 
 }  // namespace idn

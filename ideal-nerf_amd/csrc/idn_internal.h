@@ -305,6 +305,9 @@ int launch_delta_chain_x6(const float* packed_bwd, const float* acts, int64_t p_
 size_t dw_gemm_workspace_bytes();
 int launch_dw_gemm(const float* delta, int ld_delta, const float* acts, int ld_acts, int64_t rows, float* dW, float* db, int pipe,
                    void* ws, size_t ws_bytes, hipStream_t s);
+// a list of products of any of the pass's shapes through one pass plan (idealnerf_dw_products)
+size_t dw_products_workspace_bytes();
+int launch_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* products, int n, void* ws, size_t ws_bytes, hipStream_t s);
 
 // train.hip: backward of one render pass
 size_t bwd_workspace_bytes(int64_t n_points);

@@ -480,6 +480,105 @@ def dw_gemm(delta, acts, pipe=0, with_bias=True):
     return dW, db
 
 
+DW_SHAPES = ((256, 256), (256, 64), (128, 256), (128, 64), (128, 128), (64, 128))   # N x K with a kernel (csrc/dw_gemm.hip)
+DW_MAX_X6_ITEMS, DW_MAX_REDUCE_ITEMS = 12, 32                                         # kMaxTnBatch, kMaxReduceItems (csrc/dw_gemm.h)
+
+
+_dw_products_ws = {}
+
+
+def dw_products(rows, products, pipe=0, x6_items=1):
+    """Test aid: a list of weight-gradient products through one pass plan, as a training pass runs them (idealnerf_dw_products).
+    Each product is a dict:
+        delta [rows, ld_delta], N, acts [rows, ld_acts], K   ->  block = delta[:, :N]^T acts[:, :K]  (N x K one of DW_SHAPES)
+        delta_col0 (optional, a multiple of 4): the product's delta columns start there, delta[:, delta_col0 : delta_col0 + N]
+        acts2 [rows, ld_acts] (optional; pipe 0, 256 x 256): output columns 128..255 from acts2[:, :128], 0..127 from acts[:, :128]
+               (the two matrices less than 2 GiB apart, or the library refuses: take them from ONE allocation, as a pass's are)
+        colsum (bool): keep the column sums of delta[:, :N]
+        takes: [(row0, col0, n_rows, n_cols, out, out_row0, out_col0)]: out[out_row0 + r, out_col0 + c] = block[row0 + r, col0 + c],
+               out 2-D (its width is the pitch); nothing else of out is written
+        colsum_takes: [(col0, n_cols, out, out0)]: out[out0 + c] = column sum col0 + c, out 1-D
+    pipe 0: the 256 x 256 products as six bf16 piece products, the CUs divided among x6_items of them; 1: all on the fp32 pipe.
+    Returns [(splits, chunks_per_split)], the plan each product ran with."""
+    lib = _lib.load()
+    E = IdealNerfError
+    if not 1 <= len(products) <= _lib.DW_MAX_PRODUCTS:
+        raise E(f"dw_products: {len(products)} products outside [1, {_lib.DW_MAX_PRODUCTS}]")
+    if pipe not in (0, 1):
+        raise E(f"dw_products: pipe {pipe}")
+    if rows <= 0 or rows % 128:
+        raise E(f"dw_products: rows {rows} is not a positive multiple of 128")
+    if pipe == 0 and not 1 <= x6_items <= DW_MAX_X6_ITEMS:
+        raise E(f"dw_products: x6_items {x6_items} outside [1, {DW_MAX_X6_ITEMS}]")
+    n_x6 = n_red = 0
+    tensors = []
+    for i, t in enumerate(products):
+        N, K = int(t["N"]), int(t["K"])
+        if (N, K) not in DW_SHAPES:
+            raise E(f"dw_products: product {i}: no instantiation for {N} x {K}")
+        _shape(t["delta"], f"product {i}: delta", rows, None)
+        _shape(t["acts"], f"product {i}: acts", rows, None)
+        b_cols = K if t.get("acts2") is None else 128   # a split B: two 128-column matrices
+        if t["delta"].shape[1] < N or t["acts"].shape[1] < b_cols:
+            raise E(f"dw_products: product {i}: row pitch {t['delta'].shape[1]} / {t['acts'].shape[1]} < {N} / {b_cols}")
+        d0 = int(t.get("delta_col0", 0))
+        if d0 < 0 or d0 % 4 or d0 + N > t["delta"].shape[1]:
+            raise E(f"dw_products: product {i}: delta columns {d0} .. {d0 + N} of {t['delta'].shape[1]}")
+        x6 = pipe == 0 and (N, K) == (256, 256)
+        if t.get("acts2") is not None:
+            if not x6:
+                raise E(f"dw_products: product {i}: a split B needs the 256 x 256 bf16-piece kernel")
+            _shape(t["acts2"], f"product {i}: acts2", rows, t["acts"].shape[1])
+        n_x6 += x6
+        if n_x6 > x6_items:
+            raise E(f"dw_products: more 256 x 256 products than x6_items ({x6_items})")
+        takes, ctakes = t.get("takes", ()), t.get("colsum_takes", ())
+        if len(takes) > _lib.DW_MAX_TAKES or len(ctakes) > _lib.DW_MAX_COLSUM_TAKES:
+            raise E(f"dw_products: product {i}: {len(takes)} takes / {len(ctakes)} column-sum takes")
+        if ctakes and not t.get("colsum"):
+            raise E(f"dw_products: product {i} kept no column sums")
+        n_red += len(takes) + len(ctakes)
+        if n_red > DW_MAX_REDUCE_ITEMS:
+            raise E(f"dw_products: more than {DW_MAX_REDUCE_ITEMS} takes in one pass")
+        for j, (row0, col0, nr, nc, out, o_r, o_c) in enumerate(takes):
+            if min(row0, col0) < 0 or min(nr, nc) < 1 or row0 + nr > N or col0 + nc > K:
+                raise E(f"dw_products: product {i} take {j} leaves the {N} x {K} block")
+            _shape(out, f"product {i} take {j}: out", None, None)
+            if min(o_r, o_c) < 0 or o_r + nr > out.shape[0] or o_c + nc > out.shape[1]:
+                raise E(f"dw_products: product {i} take {j} does not fit out {list(out.shape)}")
+            tensors.append(out)
+        for j, (col0, nc, out, o0) in enumerate(ctakes):
+            if col0 < 0 or nc < 1 or col0 + nc > N:
+                raise E(f"dw_products: product {i} column-sum take {j} leaves the {N} columns")
+            _shape(out, f"product {i} column-sum take {j}: out", None)
+            if o0 < 0 or o0 + nc > out.shape[0]:
+                raise E(f"dw_products: product {i} column-sum take {j} does not fit out {list(out.shape)}")
+            tensors.append(out)
+        tensors += [t["delta"], t["acts"], t.get("acts2")]
+    with _Launch(*tensors) as L:
+        recs = (_lib.DwProduct * len(products))()
+        for r, t in zip(recs, products):
+            r.delta, r.ld_delta, r.N = _ptr(t["delta"], "delta") + 4 * int(t.get("delta_col0", 0)), t["delta"].shape[1], int(t["N"])
+            r.acts, r.ld_acts, r.K = _ptr(t["acts"], "acts"), t["acts"].shape[1], int(t["K"])
+            r.acts2, r.want_colsum = _ptr(t.get("acts2"), "acts2"), int(bool(t.get("colsum")))
+            takes, ctakes = t.get("takes", ()), t.get("colsum_takes", ())
+            r.n_takes, r.n_colsum_takes = len(takes), len(ctakes)
+            for k, (row0, col0, nr, nc, out, o_r, o_c) in zip(r.takes, takes):
+                k.row0, k.col0, k.rows, k.cols, k.ldo = row0, col0, nr, nc, out.shape[1]
+                k.out = _ptr(out, "out") + 4 * (o_r * out.shape[1] + o_c)
+            for k, (col0, nc, out, o0) in zip(r.colsum_takes, ctakes):
+                k.col0, k.cols, k.out = col0, nc, _ptr(out, "out") + 4 * o0
+        nbytes = lib.idealnerf_dw_products_workspace_bytes()
+        # pools of its own: the tests put NaN into operand columns no gradient may depend on, and so into partial blocks -- not
+        # into the scratch a later backward on this stream multiplies whole delta matrices from (_workspace)
+        key = (str(L.device), int(L.stream))
+        ws = _dw_products_ws.get(key)
+        if ws is None:
+            ws = _dw_products_ws[key] = torch.zeros(nbytes, dtype=torch.uint8, device=L.device)
+        check(lib.idealnerf_dw_products(rows, int(pipe), int(x6_items), recs, len(products), ws.data_ptr(), ws.numel(), L.stream))
+        return [(r.splits, r.chunks_per_split) for r in recs]
+
+
 AUDIO_NET_MAX_BWD_WINDOWS = 8
 
 

@@ -512,6 +512,51 @@ int idealnerf_dw_gemm(const float* delta, int ld_delta, const float* acts, int l
                       int pipe, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Test aid (no reference counterpart): a LIST of weight-gradient products through one pass plan, as a training pass runs
+ * them -- every shape the backward is built for (256 x 256, 128 x 128, 128 x 256, 256 x 64, 128 x 64, 64 x 128 as N x K), the
+ * 256 x 256 ones of the bf16-piece pipe as one batched launch, every block taken out by the pass's one reduction launch.
+ *   product i:  part = delta[rows, :N]^T . acts[rows, :K]  (acts2 != NULL, bf16-piece pipe, 256 x 256 only: output columns
+ *               0..127 from acts[:, :128], columns 128..255 from acts2[:, :128], both at pitch ld_acts and less than
+ *               2 GiB apart: one allocation, as the activation slab of a pass is);
+ *   take:       out[r * ldo + c] = part[row0 + r][col0 + c], r < rows, c < cols -- nothing else of `out` is written;
+ *   colsum take: out[c] = column sum of delta[:, col0 + c], c < cols (want_colsum must be set).
+ * rows: a positive multiple of 128; pitches in floats, multiples of 4, >= N / K (ld_acts >= 128 with acts2); operand
+ * pointers 16-byte aligned.
+ * pipe: IDN_DW_PIPE_BF16X6 (the 256 x 256 products as bf16 pieces, x6_items = how many of them the list may name: the CUs
+ * are divided among that many) or IDN_DW_PIPE_F32 (every product on the fp32 matrix pipe; x6_items is not used).
+ * On success every record's `splits` / `chunks_per_split` hold the plan it ran with.  Argument errors are found before any
+ * HIP call: IDN_EINVAL, IDN_EUNSUPPORTED (a shape with no kernel), IDN_EWORKSPACE.
+ */
+#define IDN_DW_MAX_PRODUCTS 16
+#define IDN_DW_MAX_TAKES 4
+#define IDN_DW_MAX_COLSUM_TAKES 2
+typedef struct idn_dw_take {
+    int row0, col0, rows, cols;
+    float* out;
+    int ldo;
+} idn_dw_take;
+typedef struct idn_dw_colsum_take {
+    int col0, cols;
+    float* out;
+} idn_dw_colsum_take;
+typedef struct idn_dw_product {
+    const float* delta;
+    int ld_delta, N;
+    const float* acts;
+    int ld_acts, K;
+    const float* acts2;
+    int want_colsum;
+    int n_takes;
+    idn_dw_take takes[IDN_DW_MAX_TAKES];
+    int n_colsum_takes;
+    idn_dw_colsum_take colsum_takes[IDN_DW_MAX_COLSUM_TAKES];
+    int splits, chunks_per_split; /* out */
+} idn_dw_product;
+size_t idealnerf_dw_products_workspace_bytes(void);
+int idealnerf_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* products, int n, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/*
  * AudioNet.forward (models/audio_net.py:43-69: the per-frame audio latent of audio_exp_nerf.py:258-259, or of the eight windows
  * under the attention smoother, :235-257) as ONE kernel, and its backward as one: windows [n, 16, 29] (win_size 16) ->
  * out [n, dim_aud].  Parameters in nn.Conv1d / nn.Linear layout ([C_out, C_in, 3] / [out, in], fp32, contiguous):

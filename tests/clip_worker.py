@@ -178,7 +178,9 @@ def main():
             res = torso(path, rank, perturb, None if seed == "none" else int(seed), draws)
         if res is not None:
             res = {k: v for k, v in res.items() if k not in ("seconds", "frames_per_s")}
-        print(json.dumps({"rank": rank, "result": res}), flush=True)
+        # line and newline in ONE write: the ranks share a pipe, and on an unbuffered stdout print() writes the two apart
+        sys.stdout.write(json.dumps({"rank": rank, "result": res}) + "\n")
+        sys.stdout.flush()
     finally:
         if world > 1:
             dist.destroy_process_group()

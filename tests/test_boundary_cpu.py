@@ -48,13 +48,16 @@ def test_ctypes_structs_match_c_layout(idn, tmp_path):
     prog = tmp_path / "sz.c"
     prog.write_text(
         '#include <stdio.h>\n#include <stddef.h>\n#include "idealnerf.h"\n'
-        'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(idn_facenerf_params), '
+        'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(idn_facenerf_params), '
         'sizeof(idn_composite_out), sizeof(idn_render_args), offsetof(idn_facenerf_params, dim_aud), '
         'offsetof(idn_render_args, t_vals), offsetof(idn_render_args, tap_inds), '
         'offsetof(idn_render_args, workspace_bytes), offsetof(idn_render_args, precision_fine_plus1), '
         'sizeof(idn_frame), offsetof(idn_frame, focal), offsetof(idn_frame, rays_out), sizeof(idn_audio_net_params), '
         'offsetof(idn_audio_net_params, dim_aud), sizeof(idn_audio_net_grads), offsetof(idn_render_args, rng_mode), '
-        'offsetof(idn_render_args, rng_seed), offsetof(idn_render_args, rng_ray0));return 0;}\n')
+        'offsetof(idn_render_args, rng_seed), offsetof(idn_render_args, rng_ray0), '
+        'sizeof(idn_dw_take), offsetof(idn_dw_take, out), offsetof(idn_dw_take, ldo), sizeof(idn_dw_colsum_take), sizeof(idn_dw_product), '
+        'offsetof(idn_dw_product, acts2), offsetof(idn_dw_product, takes), offsetof(idn_dw_product, colsum_takes), '
+        'offsetof(idn_dw_product, chunks_per_split));return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
@@ -64,8 +67,13 @@ def test_ctypes_structs_match_c_layout(idn, tmp_path):
             L.RenderArgs.workspace_bytes.offset, L.RenderArgs.precision_fine_plus1.offset,
             C.sizeof(L.Frame), L.Frame.focal.offset, L.Frame.rays_out.offset,
             C.sizeof(L.AudioNetParams), L.AudioNetParams.dim_aud.offset, C.sizeof(L.AudioNetGrads),
-            L.RenderArgs.rng_mode.offset, L.RenderArgs.rng_seed.offset, L.RenderArgs.rng_ray0.offset]
+            L.RenderArgs.rng_mode.offset, L.RenderArgs.rng_seed.offset, L.RenderArgs.rng_ray0.offset,
+            C.sizeof(L.DwTake), L.DwTake.out.offset, L.DwTake.ldo.offset, C.sizeof(L.DwColsumTake), C.sizeof(L.DwProduct),
+            L.DwProduct.acts2.offset, L.DwProduct.takes.offset, L.DwProduct.colsum_takes.offset, L.DwProduct.chunks_per_split.offset]
     assert got == want
+    hdr = open(HEADER).read()
+    for name, val in (("PRODUCTS", L.DW_MAX_PRODUCTS), ("TAKES", L.DW_MAX_TAKES), ("COLSUM_TAKES", L.DW_MAX_COLSUM_TAKES)):
+        assert re.search(rf"#define IDN_DW_MAX_{name} {val}\b", hdr), name
 
 
 def test_c_abi_argument_errors_without_gpu(idn):
@@ -129,6 +137,95 @@ def test_c_abi_argument_errors_without_gpu(idn):
     per_ray = lib.idealnerf_render_workspace_bytes(1000, 64, 128) / 1000
     assert 5000 < per_ray < 5500  # 5*S + 5*(S+Ni) floats per ray (z and raw of both passes), rounded up per buffer
     assert lib.idealnerf_render_workspace_bytes(10 ** 6, 64, 128) == lib.idealnerf_render_workspace_bytes(32768, 64, 128)
+    # a list of dW products through one pass plan: everything that needs no device is refused before any HIP call
+    L = idn._lib
+    ws_bytes = lib.idealnerf_dw_products_workspace_bytes()
+    assert ws_bytes == 256 * (9 * 65536 + 6 * 16384 + 4 * 8192) * 4 + 256 * 256 * 16 * 4   # the two pools of a pass (csrc/dw_gemm.h)
+
+    def product(N=256, K=256, ld_delta=256, ld_acts=None, acts2=None, colsum=True, takes=((0, 0, 1, 1, 4096, 256),), ctakes=()):
+        r = L.DwProduct()
+        r.delta, r.ld_delta, r.N, r.acts, r.ld_acts, r.K = 4096, ld_delta, N, 8192, K if ld_acts is None else ld_acts, K
+        r.acts2, r.want_colsum, r.n_takes, r.n_colsum_takes = acts2, int(colsum), len(takes), len(ctakes)
+        for k, v in zip(r.takes, takes):
+            k.row0, k.col0, k.rows, k.cols, k.out, k.ldo = v
+        for k, v in zip(r.colsum_takes, ctakes):
+            k.col0, k.cols, k.out = v
+        return r
+
+    def refused(recs, rows=256, pipe=0, x6_items=1, n=None, ws=4096, nbytes=ws_bytes):
+        arr = (L.DwProduct * len(recs))(*recs)
+        rc = lib.idealnerf_dw_products(rows, pipe, x6_items, arr, len(recs) if n is None else n, ws, nbytes, None)
+        return rc, lib.idealnerf_last_error()
+
+    assert lib.idealnerf_dw_products(256, 0, 1, None, 1, 4096, ws_bytes, None) == -1 and b"NULL" in lib.idealnerf_last_error()
+    for n in (0, -1, L.DW_MAX_PRODUCTS + 1):
+        rc, msg = refused([product()], n=n)
+        assert rc == -1 and b"products outside" in msg, n
+    rc, msg = refused([product()], pipe=2)
+    assert rc == -1 and b"pipe" in msg
+    for rows in (0, -128, 100, 192):
+        rc, msg = refused([product()], rows=rows)
+        assert rc == -1 and b"multiple of 128" in msg, rows
+    for x6_items in (0, 13):     # kMaxTnBatch = 12
+        rc, msg = refused([product()], x6_items=x6_items)
+        assert rc == -1 and b"x6_items" in msg
+    r = product()
+    r.acts = None
+    rc, msg = refused([r])
+    assert rc == -1 and b"NULL" in msg
+    for N, K in ((64, 64), (64, 256), (256, 128), (128, 32), (0, 0), (255, 256)):
+        for pipe in (0, 1):
+            rc, msg = refused([product(N=N, K=K)], pipe=pipe)
+            assert rc == -2 and b"no instantiation" in msg, (N, K)
+    for N in (64, 128, 256):      # the host layer's table of shapes is the library's: the others stop at the workspace check
+        for K in (64, 128, 256):
+            rc, _ = refused([product(N=N, K=K, takes=())], pipe=1, nbytes=0)
+            assert rc == (-4 if (N, K) in idn.ops.DW_SHAPES else -2), (N, K)
+    for kw in (dict(N=128, K=64, ld_delta=124), dict(N=128, K=64, ld_delta=256, ld_acts=60), dict(ld_delta=252)):
+        rc, msg = refused([product(**kw)], pipe=1)
+        assert rc == -1 and b"row pitch" in msg, kw
+    rc, msg = refused([product(N=128, K=64, ld_delta=130)], pipe=1)     # rows of 16-byte pieces
+    assert rc == -1 and b"aligned" in msg
+    rc, msg = refused([product(acts2=12288)], pipe=1)
+    assert rc == -1 and b"split B" in msg
+    rc, msg = refused([product(N=128, K=128, acts2=12288)], pipe=0)
+    assert rc == -1 and b"split B" in msg
+    for far in (8192 + (1 << 31), 8192 + (5 << 30)):     # acts at 8192: 32-bit byte offsets from the lower of the two
+        rc, msg = refused([product(acts2=far)], pipe=0)
+        assert rc == -2 and b"2 GiB apart" in msg
+    r = product(acts2=8192 + (1 << 31) - 16)             # (the last distance that fits: on to the workspace check)
+    assert refused([r], nbytes=0)[0] == -4
+    r.acts, r.acts2 = r.acts2, r.acts                    # ... and with acts2 below acts
+    assert refused([r], nbytes=0)[0] == -4
+    r.acts += 16
+    rc, msg = refused([r], nbytes=0)
+    assert rc == -2 and b"2 GiB apart" in msg
+    rc, msg = refused([product(), product()], x6_items=1)
+    assert rc == -1 and b"x6_items" in msg
+    rc, msg = refused([product()] * 13, x6_items=12)
+    assert rc == -1 and b"x6_items" in msg
+    r = product()
+    r.n_takes = L.DW_MAX_TAKES + 1
+    rc, msg = refused([r])
+    assert rc == -1 and b"takes" in msg
+    four = ((0, 0, 1, 1, 4096, 256),) * 4
+    rc, msg = refused([product(N=64, K=128, takes=four, ctakes=((0, 1, 4096),))] * 7, pipe=1)     # 35 reductions > kMaxReduceItems = 32
+    assert rc == -1 and b"more than 32 takes" in msg
+    for take in ((0, 0, 65, 128, 4096, 128), (1, 0, 64, 128, 4096, 128), (0, 1, 64, 128, 4096, 128), (-1, 0, 1, 1, 4096, 128),
+                 (0, 0, 0, 1, 4096, 128), (0, 0, 3, 128, 4096, 127), (0, 0, 3, 128, None, 128)):
+        rc, msg = refused([product(N=64, K=128, takes=(take,))], pipe=1)
+        assert rc == -1 and (b"leaves the 64 x 128 block" in msg or b"NULL" in msg), take
+    rc, msg = refused([product(N=64, K=128, colsum=False, ctakes=((0, 3, 4096),))], pipe=1)
+    assert rc == -1 and b"kept no column sums" in msg
+    for ctake in ((62, 3, 4096), (-1, 1, 4096), (0, 0, 4096), (0, 3, None)):
+        rc, msg = refused([product(N=64, K=128, ctakes=(ctake,))], pipe=1)
+        assert rc == -1 and (b"leaves the 64 columns" in msg or b"NULL" in msg), ctake
+    rc, msg = refused([product()] * 12, pipe=1)      # twelve 256 x 256 blocks per split: more than the pools of a pass hold
+    assert rc == -4 and b"pools of a pass" in msg
+    rc, msg = refused([product()], nbytes=ws_bytes - 1)
+    assert rc == -4 and b"workspace" in msg
+    rc, msg = refused([product()], ws=None)
+    assert rc == -4 and b"workspace" in msg
 
 
 def test_product_path_refuses_cpu_tensors(idn):
@@ -808,3 +905,38 @@ def test_ops_validate_shapes_before_the_c_call(idn):
         ops.frame_rays(torch.eye(4), 8, 8, 10.0, 0.1, 1.0, device="cpu")
     with pytest.raises(E, match="t_vals"):
         ops.render_rays_fwd(rays, bc, None, None, None, None, torch.zeros(8, 2), None, 0)
+    # a list of dW products: the refusals of the C entry, on CPU tensors, before any pointer is taken
+    d256, a256, a64, a128 = torch.zeros(256, 256), torch.zeros(256, 256), torch.zeros(256, 64), torch.zeros(256, 128)
+    o2, o1 = torch.zeros(300, 300), torch.zeros(300)
+
+    def prod(**kw):
+        return dict(dict(delta=d256, N=256, acts=a256, K=256, colsum=True, takes=[(0, 0, 256, 256, o2, 0, 0)]), **kw)
+
+    for bad, kw, match in (
+            ([], {}, "products outside"), ([prod()] * 17, dict(pipe=1), "products outside"),
+            ([prod()], dict(pipe=2), "pipe 2"), ([prod()], dict(x6_items=0), "x6_items"), ([prod()], dict(x6_items=13), "x6_items"),
+            ([prod(N=64, K=64)], {}, "no instantiation for 64 x 64"), ([prod(N=256, K=128)], dict(pipe=1), "no instantiation"),
+            ([prod(delta=torch.zeros(128, 256))], {}, r"delta must be \[256, \*\]"),
+            ([prod(acts=torch.zeros(128, 256))], {}, r"acts must be \[256, \*\]"),
+            ([prod(delta=a128)], {}, "row pitch 128 / 256 < 256 / 256"), ([prod(N=128, K=128, acts=a64)], dict(pipe=1), "row pitch"),
+            ([prod(acts2=a256)], dict(pipe=1), "split B"), ([prod(N=128, K=128, acts2=a256)], {}, "split B"),
+            ([prod(acts=a64, acts2=a64)], {}, "row pitch 256 / 64 < 256 / 128"), ([prod(acts=a128, acts2=a256)], {}, r"acts2 must be \[256, 128\]"), ([prod(acts2=a128)], {}, r"acts2 must be \[256, 256\]"),
+            ([prod(), prod()], dict(x6_items=1), "more 256 x 256 products than x6_items"),
+            ([prod(takes=[(0, 0, 1, 1, o2, 0, 0)] * 5)], {}, "5 takes"),
+            ([prod(colsum_takes=[(0, 1, o1, 0)] * 3)], {}, "3 column-sum takes"),
+            ([prod(N=64, K=128, acts=a128, takes=[(0, 0, 1, 1, o2, 0, 0)] * 4, colsum_takes=[(0, 1, o1, 0)])] * 7, dict(pipe=1), "more than 32 takes"),
+            ([prod(takes=[(1, 0, 256, 256, o2, 0, 0)])], {}, "leaves the 256 x 256 block"),
+            ([prod(takes=[(0, 200, 3, 57, o2, 0, 0)])], {}, "leaves the 256 x 256 block"),
+            ([prod(takes=[(0, 0, 256, 256, o2, 45, 0)])], {}, "does not fit out"),
+            ([prod(takes=[(0, 0, 256, 256, o2, 0, 45)])], {}, "does not fit out"),
+            ([prod(takes=[(0, 0, 256, 256, o1, 0, 0)])], {}, r"out must be \[\*, \*\]"),
+            ([prod(colsum=False, colsum_takes=[(0, 256, o1, 0)])], {}, "kept no column sums"),
+            ([prod(colsum_takes=[(1, 256, o1, 0)])], {}, "leaves the 256 columns"),
+            ([prod(colsum_takes=[(0, 256, o1, 45)])], {}, "does not fit out")):
+        with pytest.raises(E, match=match):
+            ops.dw_products(256, bad, **kw)
+    for rows in (0, 100, 192):
+        with pytest.raises(E, match="multiple of 128"):
+            ops.dw_products(rows, [prod()])
+    with pytest.raises(E, match="must live on the GPU"):
+        ops.dw_products(256, [prod(colsum_takes=[(0, 256, o1, 0)])])
