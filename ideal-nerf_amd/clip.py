@@ -118,12 +118,19 @@ def render_head_clip(network, dataset, path, global_step, *, latent_code, frames
 
 def _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose):
     """The per-frame body of the head + torso clip loop: once per clip the smoothed audio features, then
-    pairs(j) -> (rgb of the head pair at poses[j], last_weight and rgb_fg of the torso pair at torso_pose), on the device."""
+    pairs(j) -> (rgb of the head pair at poses[j], last_weight and rgb_fg of the torso pair at torso_pose), on the device.
+    expr: one vector for the whole clip, a track [F, E] whose row j goes to frame j of the clip (ValueError here, before
+    anything is rendered, where F is not the clip's length), or None for a head pair without expression columns."""
     device = next(network.parameters()).device
     f32 = lambda t: torch.as_tensor(t).to(device=device, dtype=torch.float32)
     poses_host = torch.as_tensor(poses).detach().to(device="cpu", dtype=torch.float32)   # the camera travels as kernel arguments
     poses_dev, torso_host = f32(poses), torch.as_tensor(torso_pose).detach().to(device="cpu", dtype=torch.float32)
-    bc_img, expr, latent_code = f32(bc_img), f32(expr), f32(latent_code)
+    bc_img, latent_code = f32(bc_img), f32(latent_code)
+    expr = None if expr is None else f32(expr)
+    per_frame = expr is not None and expr.dim() == 2
+    if per_frame and expr.shape[0] != poses_host.shape[0]:
+        raise ValueError(f"expr holds {expr.shape[0]} rows, the clip has {poses_host.shape[0]} frames: pass one row per frame "
+                         "of the clip, or one vector for all of them")
     H, W = int(bc_img.shape[0]), int(bc_img.shape[1])
     with torch.no_grad():
         aud_smo = clip_audio_features(network.aud_net, network.aud_att_net, f32(auds), network.args.smo_size)
@@ -133,8 +140,8 @@ def _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose):
 
     def pairs(j):
         signal = network.torso_signal(aud_smo[j], poses_dev[j])
-        rgb, _, _, _, _, _ = network.render_pair(expr=expr, latent_code=latent_code, aud_para=aud_smo[j],
-                                                 render_poses=poses_host[j][:3, :4], network_nerf=head, **kw)
+        rgb, _, _, _, _, _ = network.render_pair(expr=expr[j] if per_frame else expr, latent_code=latent_code,
+                                                 aud_para=aud_smo[j], render_poses=poses_host[j][:3, :4], network_nerf=head, **kw)
         _, _, _, last_w, rgb_fg, _ = network.render_pair(expr=None, latent_code=None, aud_para=signal,
                                                          render_poses=torso_host[:3, :4], network_nerf=torso, **kw)
         return rgb, last_w, rgb_fg
@@ -145,7 +152,10 @@ def _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose):
 def render_torso_clip(network, poses, auds, bc_img, path, *, expr, latent_code, torso_pose, aud_ids=None, frames=None,
                       seed=None, fps=25, codec="MJPG", swap_rb=False, still_every=0, still_path=None, group=None):
     """The head + torso clip loop for a ``train_torso.Network``.  poses [F, >=3, 4], auds [F, 16, 29] (the clip's
-    DeepSpeech windows), bc_img [H, W, 3] in [0, 1], torso_pose [>=3, 4] (the fixed camera of the torso pair).
+    DeepSpeech windows), bc_img [H, W, 3] in [0, 1], torso_pose [>=3, 4] (the fixed camera of the torso pair).  expr: one
+    expression vector for the whole clip, or a track [F, E] -- row j goes to frame j of the clip, whatever ``frames`` selects
+    (another first dimension than F raises ValueError before anything is rendered) --, or None for a head pair built with
+    ``dim_expr_head=0``.
 
     Once per clip (on every rank: it is small, and the ranks stay independent): the smoothed audio feature of
     every frame (``clip_audio_features``, test_torso.py:478-498).  Per frame j: the torso signal
@@ -256,7 +266,8 @@ def score_head_clip(network, frames, global_step, *, latent_code, frame_ids=None
 def score_torso_clip(network, poses, auds, bc_img, truth, *, regions=None, expr, latent_code, torso_pose, frames=None,
                      path=None, seed=None, group=None, fps=25, codec="MJPG", swap_rb=False):
     """``render_torso_clip`` with the ground truth beside it: truth uint8 [F, H, W, 3] and (optionally) regions uint8 [F, H, W]
-    (``dataset.region_byte_map``) on the device, indexed like poses.  Per frame the same two render pairs; what is scored is
+    (``dataset.region_byte_map``) on the device, indexed like poses; expr as there (one vector, or a track [F, E] indexed by
+    the clip's frame number).  Per frame the same two render pairs; what is scored is
     the FLOAT composite ``rgb * last_weight[..., None] + rgb_fg`` -- a torch expression with one frame-sized temporary, since
     the fused tail (``ops.compose_to8b``) keeps the composite in registers and hands out bytes only; with ``path`` the clip's
     bytes still come from that fused tail, so the file is ``render_torso_clip``'s.  Everything else, and the return value, as

@@ -396,3 +396,99 @@ class ResidentTorsoFrames(ResidentFrames):
     def _gather(self, index, sel):
         return ops.gather_ray_pairs(sel, self._cams[index], self._cams[0], self.H, self.W, self.focal, self.imgs[index],
                                     self.background, self.cx, self.cy)
+
+
+# ---- test-time loaders: a trained model on a track that is not its training clip -----------------------------------------
+
+def load_test_data(datadir, aud_file, test_pose_file, testskip=1, test_size=-1, aud_start=0):
+    """The torso test's track (``load_test_data``, NeRFs/TorsoNeRF/load_audface.py:87-114) -> (poses [F, 4, 4] float32,
+    auds [F, 16, 29] float32, bc_img uint8 [H, W, 3], [H, W, focal, cx, cy], aud_ids, torso_pose [4, 4] float64).
+
+    ``test_pose_file`` and ``aud_file`` are opened as given (not joined to ``datadir``, which only supplies ``bc.jpg`` and with
+    it H and W); focal, cx, cy are the pose file's.  Frame i of ``frames[::testskip]`` takes audio row
+    ``min(aud_start + i, n_aud - 1)`` and ``aud_ids[i] = aud_start + i`` (the row is clamped, the id is not).  The track ends
+    after the frame that makes its length ``test_size`` or ``n_aud`` -- tested after the frame is taken, so ``test_size <= 0``
+    never ends it.  ``torso_pose`` is frame 0 of the unskipped pose file."""
+    with open(test_pose_file) as fp:
+        meta = json.load(fp)
+    aud_features = np.load(aud_file)
+    n_aud = aud_features.shape[0]
+    poses, auds, aud_ids = [], [], []
+    for frame in meta["frames"][::testskip]:
+        i = len(poses)
+        poses.append(np.array(frame["transform_matrix"]))
+        auds.append(aud_features[min(aud_start + i, n_aud - 1)])
+        aud_ids.append(aud_start + i)
+        if len(poses) == test_size or len(poses) == n_aud:
+            break
+    bc_img = np.array(_imread(os.path.join(datadir, "bc.jpg")))
+    hwfcxy = [bc_img.shape[0], bc_img.shape[1], float(meta["focal_len"]), float(meta["cx"]), float(meta["cy"])]
+    torso_pose = np.array(meta["frames"][0]["transform_matrix"])
+    return np.array(poses).astype(np.float32), np.array(auds).astype(np.float32), bc_img, hwfcxy, aud_ids, torso_pose
+
+
+def load_test_exprs(path, testskip, n):
+    """-> float32 [n, E]: the ``exp`` vectors of ``frames[::testskip][:n]`` of a ``transforms_exp_*.json``-style file.
+    ValueError if the file holds fewer than ``n``."""
+    with open(path) as fp:
+        frames = json.load(fp)["frames"][::testskip]
+    if len(frames) < n:
+        raise ValueError(f"{path} holds {len(frames)} expression vectors at testskip {testskip}, the track needs {n}")
+    return np.asarray([f["exp"] for f in frames[:n]], dtype=np.float32).reshape(n, -1)
+
+
+class DrivingFrames(torch.utils.data.Dataset):
+    """The eval script's loader (``GetData``, NeRFs/HeadNeRF/test/eval_aud_exp_nerf.py:46-124): an identity driven by another
+    performance.  Poses and cx, cy come from ``<data_dir>/transforms_exp_{mode}.json`` (``frames[::skip]``; H, W =
+    int(2 cy), int(2 cx)), the audio rows are 0 .. n-1 from the START of the audio file (not the frames' ``aud_id``;
+    ``aud_file`` as given if it exists, else under ``data_dir``), and the expressions (``frames[::skip]``, as many as there are
+    identity frames) and the focal length (``focal_len``) come from ``args.evalExpr_path``.
+
+    ``__getitem__(j)`` is the 8-tuple ``Network.forward`` reads in eval mode, in ``GetData``'s field positions: (empty
+    batch_rays, empty target_s, the background in [0, 1], the whole audio track, a zero uint8 image of the frame's shape -- only
+    its shape is read --, the pose [3, 4], expression j, j).  No image, landmark or parsing file is opened: the identity's
+    ``head_imgs/`` need not exist.  ``clip.render_head_clip`` takes it as it takes ``GetData``.
+
+    Where upstream fails at the first missing frame, this raises ``ValueError`` at construction: fewer expressions than
+    frames, fewer audio rows than frames, ``evalExpr_path`` unset, a ``bc.jpg`` of another shape than (H, W)."""
+
+    def __init__(self, data_dir, aud_file, mode, args, skip=1, device="cuda"):
+        self.data_dir, self.aud_file, self.mode, self.args, self.device = data_dir, aud_file, mode, args, device
+        expr_path = getattr(args, "evalExpr_path", None)
+        if expr_path is None or expr_path == "None":
+            raise ValueError("DrivingFrames needs args.evalExpr_path: the transforms_exp_*.json of the driving performance")
+        with open(os.path.join(data_dir, f"transforms_exp_{mode}.json")) as fp:
+            self.meta_identity = json.load(fp)
+        with open(expr_path) as fp:
+            self.meta_expr = json.load(fp)
+        self.focal = float(self.meta_expr["focal_len"])
+        self.cx, self.cy = float(self.meta_identity["cx"]), float(self.meta_identity["cy"])
+        self.H, self.W = int(self.cy * 2), int(self.cx * 2)
+        self.skip = skip
+        self.all_poses = [np.array(f["transform_matrix"]) for f in self.meta_identity["frames"][::skip]]
+        self.data_size = n = len(self.all_poses)
+        exprs = [f["exp"] for f in self.meta_expr["frames"][::skip][:n]]
+        if len(exprs) < n:
+            raise ValueError(f"{expr_path} holds {len(exprs)} expression vectors at skip {skip}, the identity has {n} frames")
+        self.all_exprs = exprs
+        aud_path = aud_file if os.path.exists(aud_file) else os.path.join(data_dir, aud_file)
+        self.aud_features = np.load(aud_path)
+        if self.aud_features.shape[0] < n:
+            raise ValueError(f"{aud_path} holds {self.aud_features.shape[0]} audio rows, the identity has {n} frames")
+        background = np.array(_imread(os.path.join(data_dir, "bc.jpg")))
+        if background.shape != (self.H, self.W, 3):
+            raise ValueError(f"{os.path.join(data_dir, 'bc.jpg')} is {background.shape}, the identity's cx / cy say "
+                             f"{(self.H, self.W, 3)}")
+        self.background_img = torch.tensor(background / 255.0).to(device)
+        self.auds = torch.tensor(np.asarray(self.aud_features[:n]), dtype=torch.float)
+        self._exprs = torch.tensor(np.asarray(exprs), dtype=torch.float32)
+        self._raw_img = torch.zeros((self.H, self.W, 3), dtype=torch.uint8)
+        self._no_rays = torch.empty(0, dtype=torch.float32)
+
+    def __len__(self):
+        return self.data_size
+
+    def __getitem__(self, index):
+        index = int(index)
+        return (self._no_rays, self._no_rays, self.background_img, self.auds, self._raw_img, self.all_poses[index][:3, :4],
+                self._exprs[index], index)

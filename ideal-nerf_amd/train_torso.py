@@ -121,6 +121,26 @@ class Network(HeadNetwork):
         return [all_ret[k] for k in k_extract] + [{k: v for k, v in all_ret.items() if k not in k_extract}]
 
 
+def load_stage_checkpoints(run_dir, network, optimizer=None, device=None):
+    """How the torso stage finds its weights (train_torso.py:489-499): the newest ``*head.tar*`` of ``run_dir`` with
+    strict=False (the head pair and the audio nets), then the newest ``*torso.tar*`` strictly, with the optimiser state where
+    an ``optimizer`` is given.  -> (the torso checkpoint's step, else 0; the latent codes of the last file loaded, else None).
+    What ``train`` resumes from and what ``drive.drive_torso`` renders with."""
+    import logging
+    from . import checkpoint
+    log = logging.getLogger("adnerf")
+    global_step, codes = 0, None
+    head_path = checkpoint.latest_checkpoint(run_dir, contains="head.tar")
+    if head_path is not None:
+        log.info(f'Found ckpts:{head_path}')
+        _, codes = checkpoint.load_checkpoint(head_path, network, map_location=device, strict=False)
+    torso_path = checkpoint.latest_checkpoint(run_dir, contains="torso.tar")
+    if torso_path is not None:
+        log.info(f'Found ckpts:{torso_path}')
+        global_step, codes = checkpoint.load_checkpoint(torso_path, network, optimizer, map_location=device)
+    return global_step, codes
+
+
 def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30,
           val="reference"):
     """The reference's torso-stage ``train()`` (NeRFs/TorsoNeRF/train_torso.py:443-574) on the flags ``args``
@@ -141,7 +161,7 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     ``dataset.ResidentTorsoFrames`` and ``dataset.TorsoGetData`` as the two loaders.  ``on_log("train", ...)`` carries
     {loss, psnr, learning_rate}.  -> dict(network, optimizer, latent_codes, global_step, data_size)."""
     import os
-    from . import checkpoint, dataset, train as T
+    from . import dataset, train as T
     from .audio_exp_nerf import init_weights
     from .config import to_render_config
     from .helper import write_config
@@ -182,15 +202,8 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
 
     global_step = 0
     if args.ft_path is None or args.ft_path == 'None':
-        head_path = checkpoint.latest_checkpoint(run_dir, contains="head.tar")
-        if head_path is not None:
-            T.logger.info(f'Found ckpts:{head_path}')
-            _, saved_codes = checkpoint.load_checkpoint(head_path, network, map_location=device, strict=False)
-            latent_codes.data = saved_codes.to(device)
-        torso_path = checkpoint.latest_checkpoint(run_dir, contains="torso.tar")
-        if torso_path is not None:
-            T.logger.info(f'Found ckpts:{torso_path}')
-            global_step, saved_codes = checkpoint.load_checkpoint(torso_path, network, optimizer, map_location=device)
+        global_step, saved_codes = load_stage_checkpoints(run_dir, network, optimizer, device)
+        if saved_codes is not None:
             latent_codes.data = saved_codes.to(device)
 
     network.train()
