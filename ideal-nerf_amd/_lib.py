@@ -143,6 +143,9 @@ PROTOTYPES = {
     "idealnerf_dw_gemm": (C.c_int, [fp, C.c_int, fp, C.c_int, C.c_int64, fp, fp, C.c_int, fp, C.c_size_t, fp]),
     "idealnerf_dw_products_workspace_bytes": (C.c_size_t, []),
     "idealnerf_dw_products": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(DwProduct), C.c_int, fp, C.c_size_t, fp]),
+    "idealnerf_delta_chain_workspace_bytes": (C.c_size_t, []),
+    "idealnerf_delta_chain": (C.c_int, [C.POINTER(FaceNerfParams), C.c_int, fp, C.c_int64, fp, fp, fp, fp, C.c_int,
+                                        C.POINTER(C.c_int), fp, C.c_size_t, fp]),
     "idealnerf_profile_begin": (None, []),
     "idealnerf_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "idealnerf_profile_end_kinds": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

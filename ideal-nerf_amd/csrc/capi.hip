@@ -429,6 +429,16 @@ int idealnerf_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* 
     return launch_dw_products(rows, pipe, x6_items, products, n, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+size_t idealnerf_delta_chain_workspace_bytes(void) { return delta_chain_workspace_bytes(); }
+
+int idealnerf_delta_chain(const idn_facenerf_params* p, int pipe, const float* acts, int64_t p_pad, const float* d_rgb,
+                          float* dv0, float* dv21, float* da, int max_blocks, int* blocks_out, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    if (int e = check_params(p)) return e;
+    return launch_delta_chain_alone(*p, pipe, acts, p_pad, d_rgb, dv0, dv21, da, max_blocks, blocks_out, workspace,
+                                    workspace_bytes, (hipStream_t)stream);
+}
+
 void idealnerf_profile_begin(void) {
     g_prof_n = 0;
     g_prof_on = true;

@@ -267,8 +267,8 @@ int launch_sample_pdf(const float* z, const float* weights, const float* cdf_in,
 
 // ---------------------------------------------------------------------------
 // Backward delta chain (mlp_f32_bwd.hip): the transposed weights as a second fragment stream.
-// Stage s computes D_in^T = W_s^T . D_out^T for 32 points per wave, masks it with the saved
-// activation and keeps it in registers as the next stage's B operand.
+// Stage s computes D_in^T = W_s^T . D_out^T for 32 points per wave, masks it with the layer's
+// packed ReLU bits and keeps it in registers as the next stage's B operand.
 //   0 rgb_linear^T (K 3, padded)   1 views_linears.2^T   2 views_linears.1^T
 //   3 views_linears.0[:, :256]^T + alpha_linear^T as k-channel 128 (K 129, padded)
 //   4..10 pts_linears.7 .. pts_linears.1 ^T (pts_linears.5: its 256 hidden columns)
@@ -294,12 +294,19 @@ int launch_pack_f32_bwd(const idn_facenerf_params& p, float* packed_bwd, hipStre
 // d_rgb: [p_pad, 64] (cols 0..2 = d raw rgb), dv0: [p_pad, 256] (col 128 = d raw sigma; cols 0..127 are written),
 // acts: the forward's activation slab, dv2/dv1: [p_pad, 128], da[l]: [p_pad, 256] = delta of pts_linears.l
 int launch_delta_chain(const float* packed_bwd, const float* acts, int64_t p_pad, const float* d_rgb, float* dv0,
-                       float* dv2, float* dv1, float* const da[8], hipStream_t s);
+                       float* dv2, float* dv1, float* const da[8], hipStream_t s, int max_grid = 0,
+                       int* grid_out = nullptr);   // max_grid > 0 caps the grid; grid_out: the grid that was launched
 // the same chain as six bf16 piece products per fp32 product (its own transposed stream, twice the fragments)
 size_t bwd_stream_floats_x6();
 int launch_pack_bf16x6_bwd(const idn_facenerf_params& p, float* packed_bwd, hipStream_t s);
 int launch_delta_chain_x6(const float* packed_bwd, const float* acts, int64_t p_pad, const float* d_rgb, float* dv0,
-                          float* dv2, float* dv1, float* const da[8], hipStream_t s);
+                          float* dv2, float* dv1, float* const da[8], hipStream_t s, int max_grid = 0,
+                          int* grid_out = nullptr);
+// the chain alone, as bwd_tail launches it for `pipe` (idealnerf_delta_chain); da: [8][p_pad, 256], dv21: [p_pad, 256]
+size_t delta_chain_workspace_bytes();
+int launch_delta_chain_alone(const idn_facenerf_params& p, int pipe, const float* acts, int64_t p_pad, const float* d_rgb,
+                             float* dv0, float* dv21, float* da, int max_blocks, int* blocks_out, void* ws, size_t ws_bytes,
+                             hipStream_t s);
 
 // dw_gemm.hip: one 256 x 256 weight-gradient product in isolation (idealnerf_dw_gemm); pipe: IDN_DW_PIPE_*
 size_t dw_gemm_workspace_bytes();

@@ -5,8 +5,9 @@
 // NeRFs/HeadNeRF/train/audio_exp_nerf.py:534-552) by one kernel built like the forward one
 // (mlp_f32.hip): a wave owns 32 points, the TRANSPOSED weights are the streamed A operand, the
 // delta of one layer is the accumulator tile set that becomes the B operand of the next, and the
-// only HBM traffic per layer is the mask (the saved post-ReLU activation, read in accumulator
-// layout) and the delta itself, written row-major for the weight-gradient GEMMs (dw_gemm.hip).
+// only HBM traffic per layer is the mask (the forward's packed ReLU bits, one uint4 per lane and
+// layer in accumulator layout) and the delta itself, written row-major for the weight-gradient
+// GEMMs (dw_gemm.hip).
 // The separate GEMMs moved three P x 256 matrices per layer and sat on the HBM/MFMA ridge.
 #include "mlp_x6.h"
 
@@ -308,8 +309,15 @@ __global__ __launch_bounds__(256, 1) void delta_chain_kernel(DeltaArgs a) {
     __syncthreads();
 }
 
+// grid of either chain kernel: one persistent workgroup per CU at the most (max_grid > 0: that many at the most)
+static int chain_grid(int64_t ntiles, int num_cu, int max_grid) {
+    int64_t g = ntiles < num_cu ? ntiles : num_cu;
+    if (max_grid > 0 && g > max_grid) g = max_grid;
+    return (int)g;
+}
+
 int launch_delta_chain(const float* packed_bwd, const float* acts, int64_t p_pad, const float* d_rgb, float* dv0,
-                       float* dv2, float* dv1, float* const da[8], hipStream_t s) {
+                       float* dv2, float* dv1, float* const da[8], hipStream_t s, int max_grid, int* grid_out) {
     if (p_pad <= 0) return IDN_OK;
     if (p_pad % 128) return fail(IDN_EINVAL, "delta chain: p_pad %lld is not a multiple of 128", (long long)p_pad);
     static LaunchSetup setup;
@@ -321,12 +329,13 @@ int launch_delta_chain(const float* packed_bwd, const float* acts, int64_t p_pad
         }, &num_cu))
         return e;
     const int64_t ntiles = p_pad / 128;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
+    const int grid = chain_grid(ntiles, num_cu, max_grid);
     DeltaArgs a{packed_bwd, acts, (long)p_pad, d_rgb, dv0, dv2, dv1, {}};
     for (int l = 0; l < 8; ++l) a.da[l] = da[l];
     ProfScope prof(s, p_pad, IDN_PROF_DELTA_CHAIN);
     hipLaunchKernelGGL(delta_chain_kernel, dim3(grid), dim3(256), kDeltaLds, s, a);
     IDN_HIP_CHECK(hipGetLastError());
+    if (grid_out) *grid_out = grid;
     return IDN_OK;
 }
 
@@ -596,7 +605,7 @@ __global__ __launch_bounds__(256, 1) void delta_chain_x6_kernel(DeltaArgs a) {
 }  // namespace x6
 
 int launch_delta_chain_x6(const float* packed_bwd, const float* acts, int64_t p_pad, const float* d_rgb, float* dv0,
-                          float* dv2, float* dv1, float* const da[8], hipStream_t s) {
+                          float* dv2, float* dv1, float* const da[8], hipStream_t s, int max_grid, int* grid_out) {
     if (p_pad <= 0) return IDN_OK;
     if (p_pad % 128) return fail(IDN_EINVAL, "delta chain: p_pad %lld is not a multiple of 128", (long long)p_pad);
     static LaunchSetup setup;
@@ -608,12 +617,47 @@ int launch_delta_chain_x6(const float* packed_bwd, const float* acts, int64_t p_
         }, &num_cu))
         return e;
     const int64_t ntiles = p_pad / 128;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
+    const int grid = chain_grid(ntiles, num_cu, max_grid);
     DeltaArgs a{packed_bwd, acts, (long)p_pad, d_rgb, dv0, dv2, dv1, {}};
     for (int l = 0; l < 8; ++l) a.da[l] = da[l];
     ProfScope prof(s, p_pad, IDN_PROF_DELTA_CHAIN_X6);
     hipLaunchKernelGGL(x6::delta_chain_x6_kernel, dim3(grid), dim3(256), x6::kDelta6Lds, s, a);
     IDN_HIP_CHECK(hipGetLastError());
+    if (grid_out) *grid_out = grid;
+    return IDN_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The chain alone (idealnerf_delta_chain): the two launches bwd_tail makes for `pipe`, on the caller's matrices, with the
+// grid capped at max_blocks so that a few hundred rows make one workgroup walk several tiles.  Every argument is checked
+// before the first HIP call.
+// ---------------------------------------------------------------------------
+size_t delta_chain_workspace_bytes() { return bwd_stream_floats_x6() * sizeof(float); }
+
+int launch_delta_chain_alone(const idn_facenerf_params& p, int pipe, const float* acts, int64_t p_pad, const float* d_rgb,
+                             float* dv0, float* dv21, float* da, int max_blocks, int* blocks_out, void* ws, size_t ws_bytes,
+                             hipStream_t s) {
+    if (!acts || !d_rgb || !dv0 || !dv21 || !da) return fail(IDN_EINVAL, "delta_chain: NULL pointer");
+    if (p_pad <= 0 || p_pad % 128) return fail(IDN_EINVAL, "delta_chain: p_pad %lld is not a positive multiple of 128", (long long)p_pad);
+    if (p_pad > (int64_t)1 << 24) return fail(IDN_EUNSUPPORTED, "delta_chain: p_pad %lld exceeds 2^24", (long long)p_pad);
+    if (pipe != IDN_DW_PIPE_BF16X6 && pipe != IDN_DW_PIPE_F32) return fail(IDN_EINVAL, "delta_chain: pipe %d", pipe);
+    if (max_blocks < 0) return fail(IDN_EINVAL, "delta_chain: max_blocks %d < 0", max_blocks);
+    for (const void* q : {(const void*)acts, (const void*)d_rgb, (const void*)dv0, (const void*)dv21, (const void*)da, (const void*)ws})
+        if ((uintptr_t)q & 15) return fail(IDN_EINVAL, "delta_chain: operands are not 16-byte aligned");
+    if (!ws || ws_bytes < delta_chain_workspace_bytes())
+        return fail(IDN_EWORKSPACE, "delta_chain workspace %zu < %zu", ws_bytes, delta_chain_workspace_bytes());
+    float* wbwd = static_cast<float*>(ws);
+    float* dal[8];
+    for (int l = 0; l < 8; ++l) dal[l] = da + (size_t)l * (size_t)p_pad * 256;
+    int grid = 0;   // the grid the chain launcher launched
+    if (pipe == IDN_DW_PIPE_BF16X6) {
+        if (int e = launch_pack_bf16x6_bwd(p, wbwd, s)) return e;
+        if (int e = launch_delta_chain_x6(wbwd, acts, p_pad, d_rgb, dv0, dv21, dv21 + 128, dal, s, max_blocks, &grid)) return e;
+    } else {
+        if (int e = launch_pack_f32_bwd(p, wbwd, s)) return e;
+        if (int e = launch_delta_chain(wbwd, acts, p_pad, d_rgb, dv0, dv21, dv21 + 128, dal, s, max_blocks, &grid)) return e;
+    }
+    if (blocks_out) *blocks_out = grid;
     return IDN_OK;
 }
 

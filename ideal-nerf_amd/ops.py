@@ -579,6 +579,57 @@ def dw_products(rows, products, pipe=0, x6_items=1):
         return [(r.splits, r.chunks_per_split) for r in recs]
 
 
+_delta_chain_ws = {}
+
+
+def delta_chain(p, pipe, acts, d_rgb, dv0, max_blocks=0, dv21=None, da=None):
+    """Test aid: the backward delta chain of a training pass alone (idealnerf_delta_chain): the transposed-weight pack and the
+    fused chain kernel of `pipe` (0: six bf16 piece products, what a pass runs; 1: fp32 MFMA) on the caller's matrices.
+        p: params_struct of the network;  acts [idealnerf_train_acts_floats(p_pad)]: only its mask tail is read
+        d_rgb [p_pad, 64]: columns 0..2 = d raw rgb;  dv0 [p_pad, 256]: column 128 = d raw sigma, columns 0..127 are WRITTEN
+        max_blocks: 0 = the grid of a pass (min(p_pad / 128, CUs)); k > 0: at most k workgroups
+        dv21 [p_pad, 256], da [8, p_pad, 256]: optional outputs to write into (views into larger buffers are welcome)
+    p_pad = dv0.shape[0], a positive multiple of 128.  Returns (dv21, da, blocks): views_linears.2's | views_linears.1's delta
+    side by side, da[l] = delta of pts_linears.l, and the grid that ran."""
+    lib = _lib.load()
+    E = IdealNerfError
+    if not isinstance(p, _lib.FaceNerfParams):
+        raise E("delta_chain: p must be a params_struct")
+    if pipe not in (0, 1):
+        raise E(f"delta_chain: pipe {pipe}")
+    if isinstance(max_blocks, bool) or not isinstance(max_blocks, int) or max_blocks < 0:
+        raise E(f"delta_chain: max_blocks {max_blocks} < 0")
+    _shape(dv0, "dv0", None, 256)
+    p_pad = dv0.shape[0]
+    if p_pad <= 0 or p_pad % 128 or p_pad > 1 << 24:
+        raise E(f"delta_chain: p_pad {p_pad} is not a positive multiple of 128 up to 2^24")
+    _shape(acts, "acts", lib.idealnerf_train_acts_floats(p_pad))
+    _shape(d_rgb, "d_rgb", p_pad, 64)
+    _shape(dv21, "dv21", p_pad, 256)
+    _shape(da, "da", 8, p_pad, 256)
+    for t, name in ((acts, "acts"), (d_rgb, "d_rgb"), (dv0, "dv0"), (dv21, "dv21"), (da, "da")):
+        if t is not None and t.dtype != torch.float32:
+            raise E(f"{name} must be {torch.float32} (got {t.dtype})")
+    with _Launch(acts, d_rgb, dv0, dv21, da) as L:
+        ptrs = [_ptr(t, name) for t, name in ((acts, "acts"), (d_rgb, "d_rgb"), (dv0, "dv0"))]   # raises for CPU tensors
+        if dv21 is None:
+            dv21 = torch.empty((p_pad, 256), dtype=torch.float32, device=L.device)
+        if da is None:
+            da = torch.empty((8, p_pad, 256), dtype=torch.float32, device=L.device)
+        ptrs += [_ptr(dv21, "dv21"), _ptr(da, "da")]
+        if any(q % 16 for q in ptrs):
+            raise E("delta_chain: operands are not 16-byte aligned")
+        # a stream buffer of its own: the tests put NaN into weight columns the chain must not read
+        key = str(L.device)   # (one per device: calls on other streams of it are the caller's to order)
+        ws = _delta_chain_ws.get(key)
+        if ws is None:
+            ws = _delta_chain_ws[key] = torch.zeros(lib.idealnerf_delta_chain_workspace_bytes(), dtype=torch.uint8, device=L.device)
+        blocks = C.c_int(0)
+        check(lib.idealnerf_delta_chain(C.byref(p), int(pipe), ptrs[0], p_pad, ptrs[1], ptrs[2], ptrs[3], ptrs[4], int(max_blocks),
+                                        C.byref(blocks), ws.data_ptr(), ws.numel(), L.stream))
+    return dv21, da, blocks.value
+
+
 AUDIO_NET_MAX_BWD_WINDOWS = 8
 
 

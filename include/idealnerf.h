@@ -557,6 +557,29 @@ int idealnerf_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* 
                           size_t workspace_bytes, void* stream);
 
 /*
+ * Test aid (no reference counterpart): the backward delta chain of a training pass alone -- the transposed-weight pack and
+ * the fused chain kernel, exactly the two launches idealnerf_pass_bwd / idealnerf_facenerf_bwd make between the head deltas
+ * and the weight-gradient products -- on the caller's matrices, so that tests/ can hold every element of the eleven delta
+ * matrices to fp64.
+ *   pipe:   IDN_DW_PIPE_BF16X6 (what a pass runs) or IDN_DW_PIPE_F32 (what it runs under IDN_BACKWARD_PIPE=f32).
+ *   acts:   a slab of idealnerf_train_acts_floats(p_pad) floats; only its ReLU-mask tail is read.
+ *   d_rgb:  [p_pad, 64], columns 0..2 = d raw rgb; the other columns are not read.
+ *   dv0:    [p_pad, 256], in and out: column 128 = d raw sigma on entry; columns 0..127 are WRITTEN with views_linears.0's
+ *           delta; columns 129..255 are neither read nor written.
+ *   dv21:   [p_pad, 256], WRITTEN: views_linears.2's delta in columns 0..127, views_linears.1's in columns 128..255.
+ *   da:     [8][p_pad, 256], WRITTEN: da[l] = delta of pts_linears.l.
+ *   max_blocks: 0 = the grid of a pass, min(p_pad / 128, CUs); k > 0 caps it at k workgroups, so that a call of a few
+ *           hundred rows makes one workgroup walk several 128-row tiles.  blocks_out (may be NULL): the grid that ran.
+ *   workspace: idealnerf_delta_chain_workspace_bytes() bytes, the transposed weight stream.
+ * p_pad: a positive multiple of 128, at most 2^24; every pointer 16-byte aligned.  Argument errors are found before any
+ * HIP call: IDN_EINVAL, IDN_EUNSUPPORTED (p_pad above 2^24), IDN_EWORKSPACE.  Additive entry: the ABI version is unchanged.
+ */
+size_t idealnerf_delta_chain_workspace_bytes(void);
+int idealnerf_delta_chain(const idn_facenerf_params* p, int pipe, const float* acts, int64_t p_pad, const float* d_rgb,
+                          float* dv0, float* dv21, float* da, int max_blocks, int* blocks_out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/*
  * AudioNet.forward (models/audio_net.py:43-69: the per-frame audio latent of audio_exp_nerf.py:258-259, or of the eight windows
  * under the attention smoother, :235-257) as ONE kernel, and its backward as one: windows [n, 16, 29] (win_size 16) ->
  * out [n, dim_aud].  Parameters in nn.Conv1d / nn.Linear layout ([C_out, C_in, 3] / [out, in], fp32, contiguous):

@@ -226,6 +226,46 @@ def test_c_abi_argument_errors_without_gpu(idn):
     assert rc == -4 and b"workspace" in msg
     rc, msg = refused([product()], ws=None)
     assert rc == -4 and b"workspace" in msg
+    # the delta chain alone: the same, in the order NULL, p_pad, pipe, max_blocks, alignment, workspace
+    dc_bytes = lib.idealnerf_delta_chain_workspace_bytes()
+    assert dc_bytes == 3264 * 256 * 4     # the six-piece transposed stream: 3264 fragments of 64 lanes x 4 floats
+    fp_ = idn._lib.FaceNerfParams()
+
+    def chain(p=fp_, pipe=0, acts=4096, p_pad=256, d_rgb=8192, dv0=12288, dv21=16384, da=20480, max_blocks=0, ws=24576, nbytes=dc_bytes):
+        blocks = C.c_int(-7)
+        rc = lib.idealnerf_delta_chain(None if p is None else C.byref(p), pipe, acts, p_pad, d_rgb, dv0, dv21, da, max_blocks,
+                                       C.byref(blocks), ws, nbytes, None)
+        assert blocks.value == -7         # (nothing ran)
+        return rc, lib.idealnerf_last_error()
+
+    rc, msg = chain(p=None)
+    assert rc == -1 and b"params is NULL" in msg
+    rc, msg = chain()
+    assert rc == -1 and b"pts_linears.0 is NULL" in msg
+    for i in range(8):
+        fp_.pts_w[i] = fp_.pts_b[i] = 4096
+    for i in range(3):
+        fp_.views_w[i] = fp_.views_b[i] = 4096
+    fp_.alpha_w = fp_.alpha_b = fp_.rgb_w = fp_.rgb_b = 4096
+    for name in ("acts", "d_rgb", "dv0", "dv21", "da"):
+        rc, msg = chain(**{name: None})
+        assert rc == -1 and b"NULL" in msg, name
+    for p_pad in (0, -128, 100, 192):
+        rc, msg = chain(p_pad=p_pad)
+        assert rc == -1 and b"multiple of 128" in msg, p_pad
+    rc, msg = chain(p_pad=(1 << 24) + 128)
+    assert rc == -2 and b"2^24" in msg
+    for pipe in (-1, 2):                  # (IDN_DW_PIPE_BF16X6_PASS is a dw_gemm split count, not a chain)
+        rc, msg = chain(pipe=pipe)
+        assert rc == -1 and b"pipe" in msg
+    rc, msg = chain(max_blocks=-1)
+    assert rc == -1 and b"max_blocks" in msg
+    for name in ("acts", "d_rgb", "dv0", "dv21", "da", "ws"):
+        rc, msg = chain(**{name: 4096 + 4})
+        assert rc == -1 and b"aligned" in msg, name
+    for kw in (dict(nbytes=dc_bytes - 1), dict(nbytes=0), dict(ws=None)):
+        rc, msg = chain(pipe=1, p_pad=1 << 24, **kw)
+        assert rc == -4 and b"workspace" in msg, kw
 
 
 def test_product_path_refuses_cpu_tensors(idn):
@@ -940,3 +980,30 @@ def test_ops_validate_shapes_before_the_c_call(idn):
             ops.dw_products(rows, [prod()])
     with pytest.raises(E, match="must live on the GPU"):
         ops.dw_products(256, [prod(colsum_takes=[(0, 256, o1, 0)])])
+    # the delta chain alone: every shape, dtype and device, on CPU tensors
+    lib = idn._lib.load()
+    pp = idn._lib.FaceNerfParams()
+    slab = lambda rows: torch.zeros(lib.idealnerf_train_acts_floats(rows))
+    assert slab(256).numel() == 256 * (2560 + 88)
+
+    def chain(p=pp, pipe=0, acts=None, d_rgb=None, dv0=None, **kw):
+        return ops.delta_chain(p, pipe, slab(256) if acts is None else acts, torch.zeros(256, 64) if d_rgb is None else d_rgb,
+                               torch.zeros(256, 256) if dv0 is None else dv0, **kw)
+
+    for kw, match in (
+            (dict(p=None), "params_struct"), (dict(pipe=2), "pipe 2"), (dict(max_blocks=-1), "max_blocks"), (dict(max_blocks=1.5), "max_blocks"),
+            (dict(dv0=torch.zeros(256, 128)), r"dv0 must be \[\*, 256\]"), (dict(dv0=torch.zeros(256 * 256)), r"dv0 must be \[\*, 256\]"),
+            (dict(dv0=torch.zeros(192, 256)), "multiple of 128"), (dict(dv0=torch.zeros(0, 256)), "multiple of 128"),
+            (dict(acts=slab(128)), r"acts must be \[677888\]"), (dict(acts=slab(256)[:-1]), r"acts must be \[677888\]"),
+            (dict(acts=slab(256).reshape(256, -1)), r"acts must be \[677888\]"),
+            (dict(d_rgb=torch.zeros(256, 3)), r"d_rgb must be \[256, 64\]"), (dict(d_rgb=torch.zeros(128, 64)), r"d_rgb must be \[256, 64\]"),
+            (dict(dv21=torch.zeros(256, 128)), r"dv21 must be \[256, 256\]"), (dict(dv21=torch.zeros(128, 256)), r"dv21 must be \[256, 256\]"),
+            (dict(da=torch.zeros(8, 128, 256)), r"da must be \[8, 256, 256\]"), (dict(da=torch.zeros(7, 256, 256)), r"da must be \[8, 256, 256\]"),
+            (dict(da=torch.zeros(8 * 256, 256)), r"da must be \[8, 256, 256\]"),
+            (dict(acts=slab(256).double()), "acts must be torch.float32"), (dict(d_rgb=torch.zeros(256, 64, dtype=torch.float16)), "d_rgb must be torch.float32"),
+            (dict(dv0=torch.zeros(256, 256, dtype=torch.float64)), "dv0 must be torch.float32"),
+            (dict(dv21=torch.zeros(256, 256, dtype=torch.int32)), "dv21 must be torch.float32"),
+            (dict(da=torch.zeros(8, 256, 256, dtype=torch.bfloat16)), "da must be torch.float32"),
+            ({}, "must live on the GPU"), (dict(dv21=torch.zeros(256, 256), da=torch.zeros(8, 256, 256)), "must live on the GPU")):
+        with pytest.raises(E, match=match):
+            chain(**kw)
