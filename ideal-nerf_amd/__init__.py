@@ -7,6 +7,7 @@ at the repository root makes it importable).  Layout mirrors the reference:
     idealnerf_amd.models.audio_net.*               <- models/audio_net.py
     idealnerf_amd.helper                           <- NeRFs/HeadNeRF/helper.py (render math)
     idealnerf_amd.audio_exp_nerf.Network           <- NeRFs/HeadNeRF/train/audio_exp_nerf.py
+    idealnerf_amd.agg_aud_exp_nerf.Network         <- NeRFs/HeadNeRF/train/agg_aud_exp_nerf.py (FaceNeRFAgg; train_agg.train)
     idealnerf_amd.train_torso.Network              <- NeRFs/TorsoNeRF/train_torso.py (composite)
     idealnerf_amd.parallel                         <- row-band tiling + RCCL all-gather; frame shares + ordered assembly
     idealnerf_amd.clip                             <- the eval / test scripts' clip loops (eval_aud_exp_nerf.py, test_torso.py)

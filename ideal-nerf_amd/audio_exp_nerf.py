@@ -41,22 +41,60 @@ class Network(nn.Module):
         # upstream's class reads from its import-time `args` global (audio_exp_nerf.py:25-26,213-226)
         from . import config
         if args is None:
-            args = config.default_render_config("head")
+            args = config.default_render_config(self.config_kind)
         else:
-            config.check_against_current(args, "head")
+            config.check_against_current(args, self.config_kind)
         self.args = args
         self.H, self.W, self.focal, self.near, self.far = H, W, focal, near, far
         self.chunk, self.intrinsic = chunk, intrinsic
         self.N_samples, self.N_importance = N_samlpes, N_importance
         self.output_ch, self.skips = 4, [4]
-        mk = lambda: FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=63, dim_aud=args.dim_aud, output_ch=4,
-                              skips=self.skips, dim_latent=args.dim_latent, dim_expr=args.dim_expr,
-                              input_ch_views=27, use_viewdirs=args.use_viewdirs)
-        self.face_nerf_coarse = mk()
-        self.face_nerf_fine = mk()
+        self.face_nerf_coarse = self.make_nerf()
+        self.face_nerf_fine = self.make_nerf()
         self.aud_net = AudioNet(args.dim_aud, args.win_size)
         self.aud_att_net = AudioAttNet()
-        self.ds_aud_net = DeepSpeechAudNet()
+        if self.deepspeech_net:
+            self.ds_aud_net = DeepSpeechAudNet()
+
+    # ---- what a variant of the head renderer replaces (agg_aud_exp_nerf.Network) -----
+    config_kind = "head"    # whose process flags a Network built without args= reads (config.FLAG_TABLES)
+    deepspeech_net = True   # the 29-wide DeepSpeech squeeze is one of the submodules (a checkpoint-prefix contract)
+
+    def make_nerf(self):
+        """One network of the coarse / fine pair."""
+        args = self.args
+        return FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=63, dim_aud=args.dim_aud, output_ch=4,
+                        skips=self.skips, dim_latent=args.dim_latent, dim_expr=args.dim_expr,
+                        input_ch_views=27, use_viewdirs=args.use_viewdirs)
+
+    def audio_feature(self, auds, index, global_step, dataset_size):
+        """audio_exp_nerf.py:236-262: the frame's audio feature from the clip's DeepSpeech windows."""
+        args = self.args
+        single = lambda net: net(auds[index].unsqueeze(0) if auds[index].dim() == 2 else auds[index])
+        if args.dim_aud > 29 and global_step >= args.nosmo_iters:
+            return self.smoothed_audio_feature(auds, index, dataset_size)
+        if args.dim_aud > 29:
+            return single(self.aud_net)
+        return single(self.ds_aud_net)
+
+    def smoothed_audio_feature(self, auds, index, dataset_size):
+        """The attention-smoothed feature of the smo_size window around `index`, zero-padded at the clip's ends (:238-256)."""
+        half = int(self.args.smo_size / 2)
+        left_i, right_i = index - half, index + half
+        pad_left, pad_right = 0, 0
+        if left_i < 0:
+            pad_left, left_i = -left_i, 0
+        if right_i > dataset_size:
+            pad_right, right_i = right_i - dataset_size, dataset_size
+        win = auds[left_i:right_i]
+        if pad_left > 0:
+            win = torch.cat((torch.zeros_like(win)[:pad_left], win), dim=0)
+        if pad_right > 0:
+            win = torch.cat((win, torch.zeros_like(win)[:pad_right]), dim=0)
+        return self.aud_att_net(self.aud_net(win))
+
+    def expr_feature(self, expr):
+        return expr if self.args.dim_expr > 0 else None
 
     # ---- forward: audio_exp_nerf.py:221-272 ----------------------------------------
     def forward(self, inputs):
@@ -75,27 +113,8 @@ class Network(nn.Module):
         latent_code = torch.squeeze(latent_code).to(dev)
         index = int(index)
 
-        aud_feature, expr_feature = auds[index], None
-        if args.dim_aud > 29 and global_step >= args.nosmo_iters:
-            half = int(args.smo_size / 2)
-            left_i, right_i = index - half, index + half
-            pad_left, pad_right = 0, 0
-            if left_i < 0:
-                pad_left, left_i = -left_i, 0
-            if right_i > dataset_size:
-                pad_right, right_i = right_i - dataset_size, dataset_size
-            win = auds[left_i:right_i]
-            if pad_left > 0:
-                win = torch.cat((torch.zeros_like(win)[:pad_left], win), dim=0)
-            if pad_right > 0:
-                win = torch.cat((win, torch.zeros_like(win)[:pad_right]), dim=0)
-            aud_feature = self.aud_att_net(self.aud_net(win))
-        elif args.dim_aud > 29:
-            aud_feature = self.aud_net(aud_feature.unsqueeze(0) if aud_feature.dim() == 2 else aud_feature)
-        else:
-            aud_feature = self.ds_aud_net(aud_feature.unsqueeze(0) if aud_feature.dim() == 2 else aud_feature)
-        if args.dim_expr > 0:
-            expr_feature = expr
+        aud_feature = self.audio_feature(auds, index, global_step, dataset_size)
+        expr_feature = self.expr_feature(expr)
         render_poses = None if pose_host is None else pose_host[:3, :4]
         return self.render_dynamic_face(H=raw_img.shape[1], W=raw_img.shape[1], focal=self.focal, expr=expr_feature,
                                         poses=pose, latent_code=latent_code, render_poses=render_poses,

@@ -6,7 +6,9 @@ activation-saving MLP variant, backward is two C calls (fine pass, coarse pass),
 compositing-backward + 11 layers of MFMA GEMMs + the conditioning fold.  Gradients reach
 every FaceNeRF parameter of both networks, ``aud_para`` (and through it the audio nets,
 which stay ordinary autograd modules) and ``latent_code``.  Sampled depths are detached
-exactly as upstream (:345); ``expr`` is data.
+exactly as upstream (:345); ``expr`` is data.  A FaceNeRFAgg pair (agg_aud_exp_nerf.Network) goes through the same function:
+each network's fused feature is its conditioning vector, its columns of ``views_linears.0`` are a bias term
+(``_pass_bwd``), and torch carries the feature's gradient into ``agg_linears`` and the audio nets.
 
 ``FaceNeRFFn`` is the same machinery for ``FaceNeRF.forward`` on pre-embedded rows (models/face_nerf.py:40-80): the
 activation-saving forward in the rows' mode, and a backward seeded by dL/d out that also returns d x and d expr.
@@ -43,31 +45,53 @@ def _train_query(net, folded, rays, z):
 def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, frozen=False):
     """One pass's backward -> its 24 parameter gradients by PARAM_KEYS.  frozen = (need_aud, need_latent) for a network none of
     whose parameters needs a gradient: the conditioning-only plan -- d_aud / d_latent alone, each only if needed (neither: no
-    launch at all), and None for every parameter."""
+    launch at all), and None for every parameter.
+
+    A network whose ``bias_columns()`` is a block E of ``views_linears.0.weight`` (FaceNeRFAgg: E @ aud is part of that layer's
+    bias) gets, from the layer's bias gradient b: dE = outer(b, aud) appended to the kernels' weight gradient, and
+    d_aud += E^T b (frozen: b alone, from the conditioning-only plan's deltas)."""
+    ext = net.bias_columns()
     if frozen:
         d_aud, d_latent = (d if want else None for d, want in zip((d_aud, d_latent), frozen))
         if d_aud is not None or d_latent is not None:
-            ops.pass_bwd_cond(net.kernel_params(), aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+            args = (net.kernel_params(), aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+            if ext is not None and d_aud is not None:
+                b = torch.empty(ext.shape[0], dtype=torch.float32, device=ext.device)
+                ops.pass_bwd_cond(*args, b)
+                d_aud.addmv_(ext.detach().t(), b)
+            else:
+                ops.pass_bwd_cond(*args)
         return dict.fromkeys(PARAM_KEYS)
-    sd = dict(net.named_parameters())
+    sd = net.kernel_tensors()
     # (no column stays uninitialised: the fold kernel writes all conditioning columns, the GEMM reductions all others)
     grads = {k: torch.empty_like(sd[k]) for k in PARAM_KEYS}
-    return ops.pass_bwd(net.kernel_params(), grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+    ops.pass_bwd(net.kernel_params(), grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+    if ext is not None:
+        b = grads["views_linears.0.bias"]
+        if d_aud is not None:
+            d_aud.addmv_(ext.detach().t(), b)
+        grads["views_linears.0.weight"] = torch.cat((grads["views_linears.0.weight"], torch.outer(b, aud)), dim=1)
+    return grads
 
 
 class RenderRaysFn(torch.autograd.Function):
     """outputs: rgb_map, disp_map, acc_map [, rgb0, disp0, acc0, z_std, last_weight]
     [, rgb_fg [, rgb_fg0, last_weight0]]  (middle group when N_importance > 0, last group for the
-    torso variant).  disp / z_std carry no gradient."""
+    torso variant).  disp / z_std carry no gradient.
 
-    N_FIXED = 13  # non-parameter arguments of forward
+    ``aud`` is the coarse network's conditioning vector and, with ``aud_fine`` None, the fine network's too (a FaceNeRF pair:
+    one audio feature, one gradient buffer both passes accumulate into).  ``aud_fine``: the fine network's own vector (a
+    FaceNeRFAgg pair: each network fuses its feature with its own ``agg_linears``), with a gradient of its own."""
+
+    N_FIXED = 14  # non-parameter arguments of forward
 
     @staticmethod
-    def forward(ctx, coarse, fine, S, Ni, with_fg, rays, bc, expr, t_rand, u, aud, latent, lindisp, *params):
+    def forward(ctx, coarse, fine, S, Ni, with_fg, rays, bc, expr, t_rand, u, aud, aud_fine, latent, lindisp, *params):
         dev = rays.device
         f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
         aud_d, expr_d, lat_d = f32(aud), f32(expr), f32(latent)
-        fc = coarse.folded_bias(aud_d, expr_d, lat_d)
+        aud_fd = aud_d if aud_fine is None else f32(aud_fine)
+        fc = coarse.cond_folded_bias(aud_d, expr_d, lat_d)
         z_c = ops.coarse_depths(rays, linspace01(S, dev), t_rand, lindisp=lindisp)
         raw_c, acts_c = _train_query(coarse, fc, rays, z_c)
         if Ni > 0:   # coarse compositing + importance sampling + merge: one kernel, the weights stay on chip
@@ -78,8 +102,11 @@ class RenderRaysFn(torch.autograd.Function):
         # zero tensors autograd would have to allocate and fill (a fill launch each): the C backward takes NULL for them
         ctx.set_materialize_grads(False)
         ctx.nets, ctx.Ni, ctx.with_fg = (coarse, fine), Ni, with_fg
-        ctx.cond = (aud_d, expr_d, lat_d)
-        ctx.needs = (aud is not None and aud.requires_grad, latent is not None and latent.requires_grad)
+        ctx.cond = (aud_d, aud_fd, expr_d, lat_d)
+        need_aud = aud is not None and aud.requires_grad
+        # (need d aud of the coarse pass, of the fine pass -- one and the same where the vector is shared --, need d latent)
+        ctx.needs = (need_aud, need_aud if aud_fine is None else aud_fine.requires_grad, latent is not None and latent.requires_grad)
+        ctx.shared_aud = aud_fine is None
         if Ni == 0:
             ctx.saved = (rays, bc, raw_c, z_c, acts_c)
             outs = [comp_c["rgb_map"], comp_c["disp_map"], comp_c["acc_map"]]
@@ -87,7 +114,7 @@ class RenderRaysFn(torch.autograd.Function):
                 outs.append(comp_c["rgb_fg"])
             ctx.mark_non_differentiable(outs[1])
             return tuple(outs)
-        ff = fine.folded_bias(aud_d, expr_d, lat_d)
+        ff = fine.cond_folded_bias(aud_fd, expr_d, lat_d)
         z_f = smp["z_fine"]
         raw_f, acts_f = _train_query(fine, ff, rays, z_f)
         comp_f = ops.composite_fwd(raw_f, z_f, rays, bc, with_fg=with_fg, with_weights=False)
@@ -103,32 +130,37 @@ class RenderRaysFn(torch.autograd.Function):
     def backward(ctx, *g):
         coarse, fine = ctx.nets
         Ni, with_fg = ctx.Ni, ctx.with_fg
-        aud, expr, lat = ctx.cond
-        need_aud, need_lat = ctx.needs
+        aud, aud_f, expr, lat = ctx.cond
+        need_aud, need_aud_f, need_lat = ctx.needs
         # the plan of each network, from what autograd asks for: a network none of whose 24 parameters needs a gradient runs the
         # conditioning-only backward (and nothing at all if neither aud nor latent needs one either)
         need_p = ctx.needs_input_grad[RenderRaysFn.N_FIXED:]
         frozen_c, frozen_f = not any(need_p[:len(PARAM_KEYS)]), not any(need_p[len(PARAM_KEYS):])
         both_frozen = frozen_c and (frozen_f or Ni == 0)
-        d_aud = torch.zeros_like(aud) if aud is not None and (need_aud or not both_frozen) else None
         d_lat = torch.zeros_like(lat) if lat is not None and (need_lat or not both_frozen) else None
+        if ctx.shared_aud:
+            d_aud = d_aud_f = torch.zeros_like(aud) if aud is not None and (need_aud or not both_frozen) else None
+        else:
+            d_aud = torch.zeros_like(aud) if need_aud or not frozen_c else None
+            d_aud_f = torch.zeros_like(aud_f) if Ni > 0 and (need_aud_f or not frozen_f) else None
         c = lambda t: None if t is None else t.contiguous()
         if Ni == 0:
             rays, bc, raw_c, z_c, acts_c = ctx.saved
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[0]), c(g[3]) if with_fg else None,
-                           None, c(g[2]), d_aud, d_lat, frozen=frozen_c and ctx.needs)
+                           None, c(g[2]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat))
             gf = {k: None for k in PARAM_KEYS}
         else:
             rays, bc, raw_c, z_c, acts_c, raw_f, z_f, acts_f = ctx.saved
-            gf = _pass_bwd(fine, aud, expr, lat, acts_f, raw_f, z_f, rays, bc, c(g[0]), c(g[8]) if with_fg else None,
-                           c(g[7]), c(g[2]), d_aud, d_lat, frozen=frozen_f and ctx.needs)
+            gf = _pass_bwd(fine, aud_f, expr, lat, acts_f, raw_f, z_f, rays, bc, c(g[0]), c(g[8]) if with_fg else None,
+                           c(g[7]), c(g[2]), d_aud_f, d_lat, frozen=frozen_f and (need_aud_f, need_lat))
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[3]), c(g[9]) if with_fg else None,
-                           c(g[10]) if with_fg else None, c(g[5]), d_aud, d_lat, frozen=frozen_c and ctx.needs)
+                           c(g[10]) if with_fg else None, c(g[5]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat))
         ctx.saved = None
         param_grads = [gc[k] for k in PARAM_KEYS] + [gf[k] for k in PARAM_KEYS]
         fixed = [None] * RenderRaysFn.N_FIXED
         fixed[10] = d_aud if need_aud else None
-        fixed[11] = d_lat if need_lat else None
+        fixed[11] = d_aud_f if need_aud_f and not ctx.shared_aud else None
+        fixed[12] = d_lat if need_lat else None
         return (*fixed, *param_grads)
 
 
@@ -142,8 +174,14 @@ def render_rays_apply(network, coarse, fine, rays, bc_rgb, aud_para, latent_code
     t_rand, u = network.draw_randoms(n, S, Ni, perturb, pytest, dev)
     pc, pf = dict(coarse.named_parameters()), dict(fine.named_parameters())
     params = [pc[k] for k in PARAM_KEYS] + [pf[k] for k in PARAM_KEYS]
-    outs = RenderRaysFn.apply(coarse, fine, S, Ni, with_fg, rays, bc, expr, t_rand, u, aud_para, latent_code, bool(lindisp),
-                              *params)
+    # each network's conditioning vector (FaceNeRF: the audio feature itself, one for both; FaceNeRFAgg: its fused feature,
+    # computed here with autograd on, so that torch carries its gradient into agg_linears and the audio nets)
+    cond, expr_k = coarse.conditioning(aud_para, expr)
+    cond_fine = fine.conditioning(aud_para, expr)[0] if Ni > 0 else None
+    if cond_fine is cond:
+        cond_fine = None
+    outs = RenderRaysFn.apply(coarse, fine, S, Ni, with_fg, rays, bc, expr_k, t_rand, u, cond, cond_fine, latent_code,
+                              bool(lindisp), *params)
     ret = {'rgb_map': outs[0], 'disp_map': outs[1], 'acc_map': outs[2]}
     if Ni > 0:
         ret.update(rgb0=outs[3], disp0=outs[4], acc0=outs[5], z_std=outs[6], last_weight=outs[7])

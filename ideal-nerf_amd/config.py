@@ -77,7 +77,11 @@ TORSO_FLAGS = [
     ("i_img", int, 500, "store"), ("i_weights", int, 10000, "store"), ("i_testset", int, 10000, "store"),
     ("i_video", int, 50000, "store"),
 ]
-FLAG_TABLES = {"head": FLAGS, "torso": TORSO_FLAGS}
+# NeRFs/HeadNeRF/train/agg_aud_exp_nerf.py takes the head parser (:23) and reads `args.use_highlight` (:151), a switch that
+# parser does not define: as shipped, the trainer ends on its own feat_agg.txt files ("unrecognized arguments").  The agg
+# surface is the head one plus that switch, so that those files and that trainer have a parser they run with.
+AGG_FLAGS = FLAGS + [("use_highlight", bool, False, "store_true")]
+FLAG_TABLES = {"head": FLAGS, "torso": TORSO_FLAGS, "agg": AGG_FLAGS}
 
 
 def make_parser(kind: str = "head") -> argparse.ArgumentParser:

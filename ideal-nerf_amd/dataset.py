@@ -230,6 +230,22 @@ class TorsoGetData(GetData):
                                  self.H, self.W, self.focal, self.cx, self.cy, a.N_rand, a.use_highlight, a.sample_rate, self.device)
 
 
+class AggGetData(TorsoGetData):
+    """The feature-aggregation trainer's host-side loader (``GetData`` of NeRFs/HeadNeRF/train/agg_aud_exp_nerf.py:43-172): the
+    torso stage's pixel recipe (``torso_select_pixels``: ``N_rand // 4`` mouth picks under ``use_highlight``, draws and rows in
+    the order rect, outside, mouth, the mouth block indexing ``coords_norect``), RGB images, no parsing read and
+    ``data_size = len // testskip`` outside train mode -- on ONE camera: ``__getitem__`` returns the reference's 8-tuple
+    (batch_rays, target_s, bc_rgb, auds, raw_img, pose, exp, index).  ``args`` as ``TorsoGetData``'s."""
+
+    def _sample(self, index, target, pose):
+        a = self.args
+        landmark = np.loadtxt(self.all_landmarks[index])
+        sel = torso_select_pixels(self.H, self.W, self.all_face_rects[index], landmark, a.N_rand, a.use_highlight, a.sample_rate)
+        (batch_rays,), target_s, bc_rgb = gather_selected(sel, [pose], target, self.background_img, self.H, self.W, self.focal,
+                                                          self.cx, self.cy, self.device)
+        return batch_rays, target_s, bc_rgb
+
+
 class ResidentFrames:
     """The training clip resident on the device, drawn from by the device-side sampler: the opt-in second data path beside
     ``GetData`` (which stays the reference's host-side loader, numpy draw sequence included).
@@ -396,6 +412,16 @@ class ResidentTorsoFrames(ResidentFrames):
     def _gather(self, index, sel):
         return ops.gather_ray_pairs(sel, self._cams[index], self._cams[0], self.H, self.W, self.focal, self.imgs[index],
                                     self.background, self.cx, self.cy)
+
+
+class ResidentAggFrames(ResidentTorsoFrames):
+    """``ResidentFrames`` for the feature-aggregation trainer: the resident counterpart of ``AggGetData``.  The torso stage's
+    byte map, counts, construction errors and RGB images (``ResidentTorsoFrames``) with the head stage's single camera:
+    ``batch`` returns the 8-tuple (batch_rays, target_s, bc_rgb, auds, raw_img, pose, expr, index) from ``ops.gather_rays``,
+    ``frame`` the eval 8-tuple (``mode="val"``)."""
+
+    _no_sets = 2
+    _gather = ResidentFrames._gather
 
 
 # ---- test-time loaders: a trained model on a track that is not its training clip -----------------------------------------

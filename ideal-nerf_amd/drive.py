@@ -32,7 +32,7 @@ def _same_on_every_rank(build):
 
 
 def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", still_every=10, seed=None, group=None,
-               precision=None):
+               precision=None, model="head"):
     """The eval script's ``eval()`` on the flags ``args`` (``helper.config_parser().parse_args()``): ``DrivingFrames(args.datadir,
     args.aud_file, "val", args, skip=args.testskip)``, a ``Network`` with ``to_render_config(args)`` and the loader's focal
     length, the checkpoint ``args.ft_path`` -- else the newest ``*.tar`` of ``basedir/expname`` --, read whole and without
@@ -42,16 +42,17 @@ def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", st
     ``global_step`` is 0 as upstream, which selects the unsmoothed audio path of ``Network.forward``; pass the checkpoint's step
     for the smoothed one.  ``out`` defaults to upstream's ``V_{datadir[8:]}_{aud_file[-9:-4]}_N_ExpPose0.avi`` under
     ``args.save_path``; every ``still_every``-th frame is also written there as ``{datadir[8:]}_{aud_file[-9:-4]}_ExpPose_{i}.jpg``.
-    ``precision``: ``set_render_precision``'s.  ValueError where ``args.dim_expr`` is not the expression track's width.
+    ``precision``: ``set_render_precision``'s.  ``model``: "head", or "agg" for a run of ``train_agg.train``
+    (``agg_aud_exp_nerf.Network``; its newest ``{epoch:06d}_head.tar``).  ValueError where the network's expression width --
+    ``args.dim_expr``, the agg pair's 79 -- is not the expression track's.
     -> ``render_head_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
-    from .audio_exp_nerf import Network
+    from .agg_aud_exp_nerf import DIM_EXPR, build_head_network
     frames = dataset.DrivingFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device)
     width = len(frames.all_exprs[0])
-    if args.dim_expr != width:
-        raise ValueError(f"dim_expr is {args.dim_expr}, the expression track {args.evalExpr_path} is {width} wide")
-    network = _same_on_every_rank(lambda: Network(
-        frames.H, frames.W, frames.focal, near=args.near, far=args.far, chunk=args.chunk, intrinsic=None,
-        N_samlpes=args.N_samples, N_importance=args.N_importance, args=to_render_config(args))).to(device)
+    dim_expr = DIM_EXPR if model == "agg" else args.dim_expr
+    if dim_expr != width:
+        raise ValueError(f"dim_expr is {dim_expr}, the expression track {args.evalExpr_path} is {width} wide")
+    network = _same_on_every_rank(lambda: build_head_network(args, frames.H, frames.W, frames.focal, model)).to(device)
     latent_code = torch.zeros(32, dtype=torch.float32)
     if not args.no_reload:
         path = args.ft_path if not _unset(args.ft_path) else checkpoint.latest_checkpoint(os.path.join(args.basedir, args.expname))

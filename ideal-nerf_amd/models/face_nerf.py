@@ -46,8 +46,9 @@ def set_render_precision(network, mode: str):
 def invalidate_packed(module):
     """Drop the cached weight streams of every FaceNeRF under `module` (needed only after writes through
     ``.data``, which PyTorch's version counters do not see)."""
+    from .face_nerf_agg import FaceNeRFAgg
     for m in module.modules():
-        if isinstance(m, FaceNeRF):
+        if isinstance(m, (FaceNeRF, FaceNeRFAgg)):
             m.invalidate_packed()
 
 
@@ -116,6 +117,22 @@ class FaceNeRF(nn.Module):
     def kernel_params(self):
         sd = {k: v for k, v in self.named_parameters()}
         return ops.params_struct(sd, self.dim_aud, self.dim_expr, self.dim_latent)
+
+    # -- what autograd.RenderRaysFn asks of a model class (FaceNeRFAgg answers the same questions with its fused feature)
+    def kernel_tensors(self):
+        """The tensors ``kernel_params`` points at, by state_dict key: a gradient of the kernels has these shapes."""
+        return dict(self.named_parameters())
+
+    def bias_columns(self):
+        """No column of ``views_linears.0`` multiplies the conditioning vector here."""
+        return None
+
+    def conditioning(self, aud, expr=None):
+        """-> (this network's conditioning vector, the expression the kernels see)."""
+        return aud, expr
+
+    def cond_folded_bias(self, cond, expr=None, latent_code=None) -> torch.Tensor:
+        return self.folded_bias(cond, expr, latent_code)
 
     def packed_weights(self, precision: str = None) -> torch.Tensor:
         """MFMA-fragment weight stream for `precision`, rebuilt only when a parameter changed."""

@@ -6,7 +6,11 @@ The per-point network is the FaceNeRF one, so it runs on the same fused HIP kern
 fused feature takes the place of ``aud`` in the folded biases of layers 0 and 5, and its
 columns of ``views_linears.0`` (a per-frame constant) are folded into that layer's bias
 on the host side.  Same constructor, ``forward`` and state_dict keys as the reference.
-Inference only.
+
+``forward`` is an inference entry.  Training goes through the agg ``Network`` (agg_aud_exp_nerf.py): there the fused
+feature g is computed by torch with autograd on and enters ``autograd.RenderRaysFn`` as this network's conditioning vector;
+the methods below (``conditioning``, ``cond_folded_bias``, ``kernel_params``, ``kernel_tensors``, ``bias_columns``) are
+what that function asks of either model class.
 """
 import torch
 import torch.nn as nn
@@ -41,6 +45,56 @@ class FaceNeRFAgg(nn.Module):
 
     def _param_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    def invalidate_packed(self):
+        """As ``FaceNeRF.invalidate_packed``: drop the cached weight streams and the cached trunk columns of
+        ``views_linears.0`` (needed only after writes through ``.data``)."""
+        self._packed.clear()
+        self._packed_key.clear()
+        self._views0 = None
+
+    def train(self, mode: bool = True):
+        self.invalidate_packed()
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self.invalidate_packed()
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self.invalidate_packed()
+        return super()._apply(fn, *args, **kwargs)
+
+    def kernel_params(self):
+        """idn_facenerf_params of the equivalent FaceNeRF, with ``views_linears.0``'s own bias (the backward reads no bias)."""
+        return self._kernel_params()[0]
+
+    def kernel_tensors(self):
+        """The tensors ``kernel_params`` points at, by state_dict key: a gradient of the kernels has these shapes
+        (``views_linears.0.weight`` without its feature columns)."""
+        return self._kernel_params()[1]
+
+    def bias_columns(self):
+        """The columns of ``views_linears.0.weight`` that multiply the conditioning vector ([128, dim_agg]): their product
+        with it is part of that layer's bias (``cond_folded_bias``), so their gradient and their share of the conditioning
+        vector's come from the layer's bias gradient (``autograd._pass_bwd``)."""
+        return self.views_linears[0].weight[:, self.W + self.input_views_ch:]
+
+    def conditioning(self, aud, expr=None):
+        """-> (this network's conditioning vector, the expression the kernels see): the fused feature, with autograd where it
+        is on, and None -- the expression went into the feature."""
+        return self.agg_feature(aud, expr), None
+
+    def cond_folded_bias(self, cond, expr=None, latent_code=None) -> torch.Tensor:
+        """``folded_bias`` from the fused feature itself."""
+        dev = self.alpha_linear.weight.device
+        with torch.no_grad():
+            v0 = self.views_linears[0]
+            agg = cond.detach().to(dev, torch.float32)
+            bias = (v0.bias + self.bias_columns() @ agg).contiguous()
+            ps, _keep = self._kernel_params(bias)
+            lat = None if latent_code is None else latent_code.detach().to(dev, torch.float32).contiguous()
+            return ops.fold_conditioning(ps, agg.contiguous(), None, lat, dev)
 
     def _kernel_params(self, views0_bias=None):
         """idn_facenerf_params of the equivalent FaceNeRF(dim_aud=dim_agg, dim_expr=0, dim_latent)."""
@@ -83,12 +137,7 @@ class FaceNeRFAgg(nn.Module):
         dev = self.alpha_linear.weight.device
         with torch.no_grad():
             agg = self.agg_feature(aud.to(dev, torch.float32), None if expr is None else expr.to(dev, torch.float32))
-            n_h = self.W + self.input_views_ch
-            v0 = self.views_linears[0]
-            bias = (v0.bias + v0.weight[:, n_h:] @ agg).contiguous()
-            ps, _keep = self._kernel_params(bias)
-            lat = None if latent_code is None else latent_code.detach().to(dev, torch.float32).contiguous()
-            return ops.fold_conditioning(ps, agg.contiguous(), None, lat, dev)
+        return self.cond_folded_bias(agg, None, latent_code)
 
     def forward(self, x, aud, expr=None, latent_code=None):
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):

@@ -217,7 +217,7 @@ def query_rays_train_fwd(packed, folded, rays, z, precision=_lib.IDN_PREC_BF16X6
     return raw, acts
 
 
-def _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
+def _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias=None):
     """The checks and the call behind `pass_bwd` (grads: a dict) and `pass_bwd_cond` (grads: None)."""
     lib = _lib.load()
     if grads is None:
@@ -235,6 +235,14 @@ def _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, 
             check(lib.idealnerf_pass_bwd(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
         else:
             check(lib.idealnerf_pass_bwd_cond(C.byref(p), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
+            if d_views0_bias is not None:
+                _shape(d_views0_bias, "d_views0_bias", W_HID // 2)
+                # The pass's delta chain has left views_linears.0's deltas in the workspace: the tenth [p_pad, 256] matrix of
+                # csrc/train.hip: carve_bwd (eight of pts_linears.l, one of views_linears.2 | .1, then dV0: columns 0..127).
+                # Their column sums over the pass's points, in fp64, before anything else on this stream touches the scratch.
+                p_pad = (n * S + 127) // 128 * 128
+                dv0 = ws[9 * p_pad * 1024:10 * p_pad * 1024].view(torch.float32).view(p_pad, 256)
+                d_views0_bias.copy_(torch.sum(dv0[:n * S, :W_HID // 2], dim=0, dtype=torch.float64))
     return grads
 
 
@@ -244,11 +252,19 @@ def pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g
     return _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
 
 
-def pass_bwd_cond(p, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent):
+def pass_bwd_cond(p, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias=None):
     """`pass_bwd` for a network none of whose parameters takes a gradient (idealnerf_pass_bwd_cond): the same compositing
     backward and delta chain, then only the column sums and the fold range d aud / d latent need.  d_aud / d_latent:
-    accumulated; nothing else is written."""
-    _pass_bwd(p, None, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+    accumulated; nothing else is written.
+
+    d_views0_bias [128] (optional, OVERWRITTEN): the gradient of views_linears.0's bias -- what `pass_bwd` returns as that
+    entry of `grads` -- for a network whose conditioning also reaches that bias (FaceNeRFAgg).  The C entry does not return it;
+    it is summed here from the deltas the entry leaves in this stream's workspace, whose place there is csrc/train.hip's
+    carve_bwd (tests/test_agg_gpu.py::test_agg_frozen_pair_d_aud_vs_fp64 fails if that layout moves).  Needs d_aud or
+    d_latent: with both None the entry launches nothing."""
+    if d_views0_bias is not None and d_aud is None and d_latent is None:
+        raise IdealNerfError("pass_bwd_cond: d_views0_bias needs d_aud or d_latent (with neither the pass is not run)")
+    _pass_bwd(p, None, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias)
 
 
 def query_rays_fwd(packed, folded, rays, z, precision=IDN_PREC_F32) -> torch.Tensor:

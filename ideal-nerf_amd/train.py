@@ -132,10 +132,20 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     {frame, groups, mse, psnr, ssim: one value per ops.SCORE_GROUPS}); ``on_step(global_step, info)`` runs after every step.
     Inside a process group every rank trains (``train_step`` all-reduces the gradients); rank 0 alone logs and saves.
     -> dict(network, optimizer, latent_codes, global_step, data_size)."""
+    from . import dataset
+    return _train_head_model(args, "head", dataset.ResidentFrames, dataset.GetData, lambda epoch: 'head.tar', True, loader=loader,
+                             sample_seed=sample_seed, device=device, steps=steps, on_log=on_log, on_step=on_step,
+                             max_bytes=max_bytes, val=val)
+
+
+def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name, flip, *, loader, sample_seed, device, steps,
+                      on_log, on_step, max_bytes, val):
+    """The body of ``train`` for a head-stage model (``agg_aud_exp_nerf.HEAD_MODELS``): its two loader classes, its checkpoint
+    name per epoch, and whether the validation image is channel-flipped (the loader reads BGR)."""
     import numpy as np
-    from . import checkpoint, dataset
-    from .audio_exp_nerf import Network, init_weights
-    from .config import to_render_config
+    from . import checkpoint
+    from .agg_aud_exp_nerf import build_head_network
+    from .audio_exp_nerf import init_weights
     from .helper import write_config
 
     if loader not in ("resident", "reference"):
@@ -148,24 +158,23 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     run_dir = os.path.join(basedir, expname)
 
     if loader == "resident":
-        dataset_train = dataset.ResidentFrames(args.datadir, args.aud_file, "train", args, device=device, max_bytes=max_bytes,
-                                               seed=sample_seed)
+        dataset_train = resident_cls(args.datadir, args.aud_file, "train", args, device=device, max_bytes=max_bytes,
+                                     seed=sample_seed)
     else:
-        dataset_train = dataset.GetData(args.datadir, args.aud_file, mode="train", args=args, device=device)
-    dataset_val = dataset.GetData(args.datadir, args.aud_file, mode="val", args=args, skip=args.testskip, device=device)
+        dataset_train = reference_cls(args.datadir, args.aud_file, mode="train", args=args, device=device)
+    dataset_val = reference_cls(args.datadir, args.aud_file, mode="val", args=args, skip=args.testskip, device=device)
     logger.info(f'dataset_val length: {dataset_val.data_size}')
     frames_val = None
     if val == "resident" and rank == 0:
-        frames_val = dataset.ResidentFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device,
-                                            max_bytes=max_bytes, seed=sample_seed)
+        frames_val = resident_cls(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device,
+                                  max_bytes=max_bytes, seed=sample_seed)
     data_size = dataset_train.data_size
     H, W, focal = dataset_val.H, dataset_val.W, dataset_val.focal
     intrinsic = np.array([[focal, 0., W / 2], [0, focal, H / 2], [0, 0, 1.]])
     if rank == 0:
         write_config(args)
 
-    network = Network(H, W, focal, near=args.near, far=args.far, chunk=args.chunk, intrinsic=intrinsic,
-                      N_samlpes=args.N_samples, N_importance=args.N_importance, args=to_render_config(args)).to(device)
+    network = build_head_network(args, H, W, focal, model, intrinsic).to(device)
     latent_codes = torch.ones(data_size, 32, dtype=torch.float32, device=device)
     network.apply(init_weights)
     latent_codes.requires_grad = True
@@ -186,8 +195,8 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
 
     def validate(step):
         if frames_val is None:
-            return validation_frame(network, dataset_val, latent_codes, step, sample_seed), None
-        return resident_validation_frame(network, frames_val, latent_codes, step, sample_seed)
+            return validation_frame(network, dataset_val, latent_codes, step, sample_seed, flip=flip), None
+        return resident_validation_frame(network, frames_val, latent_codes, step, sample_seed, flip=flip)
 
     global_step = _run_epochs(
         args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step,
@@ -198,7 +207,7 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
         scalars_of=lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"],
                                      latent_code_loss=info["latent_code_loss"].item()),
         log_line=lambda sc: f"LatentLoss: {sc['latent_code_loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}",
-        validate=validate, checkpoint_name=lambda epoch: 'head.tar')
+        validate=validate, checkpoint_name=checkpoint_name)
     return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
 
 

@@ -33,8 +33,12 @@ for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 def parse(argv):
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--flow", choices=("head", "torso"), required=True)
-    flow = pre.parse_known_args(argv)[0].flow
-    if flow == "head":
+    pre.add_argument("--model", choices=("head", "agg"), default="head")
+    known = pre.parse_known_args(argv)[0]
+    flow = known.flow
+    if flow == "head" and known.model == "agg":
+        from idealnerf_amd.agg_aud_exp_nerf import config_parser   # the head stage's flags plus use_highlight
+    elif flow == "head":
         from idealnerf_amd.helper import config_parser
     else:
         from idealnerf_amd.train_torso import config_parser
@@ -47,6 +51,7 @@ def parse(argv):
     p.add_argument("--global-step", type=int, default=0)
     p.add_argument("--still-every", type=int, default=10)
     p.add_argument("--seed", type=int, default=None, help="per-frame draws seeded with seed + frame (perturb > 0)")
+    p.add_argument("--model", choices=("head", "agg"), default="head", help="--flow head: the run's model (agg: train_agg.train's)")
     return p.parse_args(argv)
 
 
@@ -67,7 +72,7 @@ def main(argv=None):
         common = dict(out=args.out, device=dev, codec=args.codec, still_every=args.still_every, seed=args.seed,
                       precision=args.precision)
         if args.flow == "head":
-            res = drive.drive_head(args, global_step=args.global_step, **common)
+            res = drive.drive_head(args, global_step=args.global_step, model=args.model, **common)
         else:
             res = drive.drive_torso(args, **common)
         if res is not None:
