@@ -346,6 +346,7 @@ struct MlpArgs {
 // the colour-gated fp32 rays kernel's arguments (the other kernels' stay as they are)
 struct MlpGateArgs : MlpArgs {
     unsigned long long* gate_counters;   // (tiles, skipped) this launch adds to, or null
+    int tile_step;                       // tile_order_step(grid) (tile_order.h): the kernel's loop divides nothing
 };
 
 // Raw inputs of one lane's point.  They are loaded one pass ahead (right after a slice opens in

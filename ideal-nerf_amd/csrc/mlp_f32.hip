@@ -13,8 +13,10 @@
 //     weight stream: global -> LDS by global_load_lds_dwordx4 into a 2 x 64 KiB ring, one
 //     barrier per 64 KiB slice (= 256 MFMAs per wave);
 //   * workgroups are persistent (one per CU) and walk the point tiles grid-stride, so the
-//     weight stream keeps flowing across tiles.
+//     weight stream keeps flowing across tiles (the colour-gated instantiation: in rounds of
+//     one tile per workgroup, rotated round by round -- tile_order.h).
 #include "mlp_f32_layers.h"
+#include "tile_order.h"
 
 namespace idn {
 
@@ -133,7 +135,17 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(std::conditional_t<GATE
     load_point<MODE>(a, blockIdx.x, wave, m, cur);
     if constexpr (GATE) load_gate_point(a, blockIdx.x, wave, m, cur);
     nxt = cur;
-    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    // GATE: rounds of gridDim.x tiles in the skewed order of tile_order.h (round 0 is the identity), so that the live tiles of
+    // a frame spread over the CUs; workgroup-uniform integers, scalar instructions only.  Otherwise plain grid-stride, spelled
+    // `tile += gridDim.x` as ever: moving that sum into the body re-allocates the other instantiations' registers.
+    [[maybe_unused]] long next_tile = 0, tile_base = 0;
+    [[maybe_unused]] int tile_off = blockIdx.x;
+    auto advance = [&](long& tile) {
+        if constexpr (GATE) tile = next_tile;
+        else tile += gridDim.x;
+    };
+    for (long tile = blockIdx.x; tile < ntiles; advance(tile)) {
+        if constexpr (GATE) next_tile = tile_order_next(&tile_base, &tile_off, (int)gridDim.x, a.tile_step);
         const long P = tile * 128 + wave * 32 + m;
         const bool valid = P < a.n_points;
         const long Pc = valid ? P : a.n_points - 1;
@@ -194,7 +206,7 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(std::conditional_t<GATE
             // as below, with the gate's inputs beside the point's; a point beyond n_points is dead
             const bool skipped = f32_inference_pass<true>(
                 pe, pd, bias_s, bias_h, ws, fr,
-                [&]() { load_point<MODE>(a, tile + gridDim.x, wave, m, nxt); load_gate_point(a, tile + gridDim.x, wave, m, nxt); },
+                [&]() { load_point<MODE>(a, next_tile, wave, m, nxt); load_gate_point(a, next_tile, wave, m, nxt); },
                 [&]() { touch_point(nxt); touch_gate_point(nxt); }, rgb, sigma,
                 [&](float sg) { return !valid || gate_point_dead(cur, sg); }, gate_words + gate_par, gate_words + (gate_par ^ 1));
             gate_par ^= 1;
@@ -406,6 +418,7 @@ int launch_mlp_f32(const float* packed, const float* folded, const float* x, con
         MlpGateArgs ga;
         static_cast<MlpArgs&>(ga) = a;
         ga.gate_counters = reinterpret_cast<unsigned long long*>(gate_counters);
+        ga.tile_step = tile_order_step(grid);
         hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, false, true>), dim3(grid), dim3(256), kMlpLdsGate, s, ga);
     }
     else
