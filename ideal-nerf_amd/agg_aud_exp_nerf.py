@@ -45,13 +45,17 @@ class Network(HeadNetwork):
         return expr
 
 
-HEAD_MODELS = ("head", "agg")
+HEAD_MODELS = ("head", "agg", "baseline")
 
 
 def head_network_class(model="head"):
-    """The renderer class of a head-stage model: "head" (audio_exp_nerf.Network) or "agg" (this module's)."""
+    """The renderer class of a head-stage model: "head" (audio_exp_nerf.Network), "agg" (this module's) or "baseline"
+    (head_baseline.Network: audio only, no expression and no latent code anywhere in its tuples)."""
     if model not in HEAD_MODELS:
         raise ValueError(f"model must be one of {HEAD_MODELS}, got {model!r}")
+    if model == "baseline":
+        from .head_baseline import Network as BaselineNetwork
+        return BaselineNetwork
     return HeadNetwork if model == "head" else Network
 
 

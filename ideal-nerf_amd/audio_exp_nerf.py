@@ -286,7 +286,8 @@ class Network(nn.Module):
             viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
             rec = torch.cat([rays_o, rays_d, near * torch.ones_like(rays_d[..., :1]),
                              far * torch.ones_like(rays_d[..., :1]), viewdirs], -1)
-            all_ret = self.batchify_rays(rec, bc_rgb, aud_para, poses=poses, latent_code=latent_code, expr=expr, chunk=chunk)
+            # (batchify_rays' body, called by that name: a variant's batchify_rays has upstream's signature of its own class)
+            all_ret = self._batchify(rec, bc_rgb, aud_para, latent_code, expr, self.face_nerf_coarse, self.face_nerf_fine, False, chunk)
         for k in all_ret:
             all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
         k_extract = ['rgb_map', 'disp_map', 'acc_map', 'last_weight']

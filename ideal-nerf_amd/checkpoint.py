@@ -2,7 +2,9 @@
 TorsoNeRF/train_torso.py:565-573): ``head.tar`` = {'global_step', 'model_state_dict',
 'optimizer', 'latent_codes'}, resume from the naturally-sorted last ``*.tar`` of the run
 directory, and warm start from AD-NeRF checkpoints (``ft_path``) whose first / skip / view layers
-have other input widths and are dropped.
+have other input widths and are dropped.  The AD-NeRF baseline (head_baseline.py:439-457,516-520; test_nerf.py:155-172) has
+two forms of its own: the run file ``{'global_step', 'model_state_dict', 'optimizer'}`` with upstream's ``module.`` keys, and
+AD-NeRF's four state dicts, read in full and strict (``load_adnerf``) and written (``save_adnerf``).
 """
 import os
 import re
@@ -39,6 +41,57 @@ def load_checkpoint(path: str, network, optimizer=None, map_location=None, stric
     if optimizer is not None and ckpt.get("optimizer") is not None:
         optimizer.load_state_dict(ckpt["optimizer"])
     return ckpt["global_step"], ckpt["latent_codes"]
+
+
+DATA_PARALLEL_PREFIX = "module."
+
+
+def save_baseline_checkpoint(path: str, network, optimizer, global_step: int):
+    """The AD-NeRF baseline's run file (head_baseline.py:516-520): {'global_step', 'model_state_dict', 'optimizer'}, no latent
+    codes.  Upstream wraps the network in ``nn.DataParallel`` on this path (:448), so its keys carry ``module.``: they are
+    written that way, and upstream's trainer and tester load the file as their own."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save({"global_step": global_step,
+                "model_state_dict": {DATA_PARALLEL_PREFIX + k: v for k, v in network.state_dict().items()},
+                "optimizer": optimizer.state_dict() if optimizer is not None else None}, path)
+
+
+def load_baseline_checkpoint(path: str, network, optimizer=None, map_location=None):
+    """-> global_step.  Strict, as upstream (head_baseline.py:455-457); the keys may carry upstream's ``module.`` prefix
+    (every one of them) or none."""
+    ckpt = torch.load(path, map_location=map_location, weights_only=False)
+    state = ckpt["model_state_dict"]
+    if state and all(k.startswith(DATA_PARALLEL_PREFIX) for k in state):
+        state = {k[len(DATA_PARALLEL_PREFIX):]: v for k, v in state.items()}
+    network.load_state_dict(state, strict=True)
+    if optimizer is not None and ckpt.get("optimizer") is not None:
+        optimizer.load_state_dict(ckpt["optimizer"])
+    return ckpt["global_step"]
+
+
+ADNERF_KEYS = (("network_fn_state_dict", "face_nerf_coarse"), ("network_fine_state_dict", "face_nerf_fine"),
+               ("network_audnet_state_dict", "aud_net"), ("network_audattnet_state_dict", "aud_att_net"))
+
+
+def load_adnerf(path_or_dict, network, map_location=None):
+    """An AD-NeRF checkpoint as what it is (head_baseline.py:439-446, test_nerf.py:155-163): the coarse / fine FaceNeRFs and
+    the two audio nets, each dict in full and strict -- a file of another model (other input widths, missing or extra keys)
+    raises.  ``network``: a ``head_baseline.Network``.  -> the file's ``global_step`` (None where it records none)."""
+    ckpt = path_or_dict if isinstance(path_or_dict, dict) else torch.load(path_or_dict, map_location=map_location,
+                                                                          weights_only=False)
+    missing = [k for k, _ in ADNERF_KEYS if k not in ckpt]
+    if missing:
+        raise KeyError(f"not an AD-NeRF checkpoint: no {missing} among {sorted(ckpt)}")
+    for key, name in ADNERF_KEYS:
+        getattr(network, name).load_state_dict(ckpt[key], strict=True)
+    return ckpt.get("global_step")
+
+
+def save_adnerf(path: str, network, global_step: int):
+    """``network`` (a ``head_baseline.Network``) in AD-NeRF's four-dict form: a valid ``--ft_path`` for upstream's baseline
+    trainer and tester and for AD-NeRF tooling, and what ``load_adnerf`` reads back unchanged."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(dict({key: getattr(network, name).state_dict() for key, name in ADNERF_KEYS}, global_step=global_step), path)
 
 
 ADNERF_DROP = ("pts_linears.0.weight", "pts_linears.5.weight", "views_linears.0.weight")

@@ -90,13 +90,23 @@ def _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, st
     return dict(done, seconds=seconds, frames_per_s=n / seconds if n else 0.0, world=world)
 
 
+def _forward_tuple(data, latent_code, model):
+    """A head-stage loader's item as ``Network.forward`` takes it: the latent code before the index -- the baseline's 7-tuple
+    (``model="baseline"``: no expression, no latent code) as it is."""
+    return tuple(data) if model == "baseline" else (*data[:7], latent_code, data[7])
+
+
 def render_head_clip(network, dataset, path, global_step, *, latent_code, frames=None, seed=None, fps=25, codec="MJPG",
-                     swap_rb=False, still_every=0, still_path=None, group=None):
+                     swap_rb=False, still_every=0, still_path=None, group=None, model="head", stills_as_rgb=False):
     """The head-only eval loop: every frame of ``frames`` (default: the whole ``dataset``, a ``dataset.GetData`` in
     val mode) through ``network([data, global_step, dataset.data_size])`` in eval mode under no_grad, converted on
     the device and written to the AVI at ``path`` in order; ``still_path="dir/name_{i}.jpg"`` with
     ``still_every=10`` adds the reference's stills ({i}: position in the clip).  This rank reads only its own frames,
     through a batch-1 in-process loader, so every field is collated as the reference's loader collates it.
+    ``model="baseline"``: a ``head_baseline.Network`` on a ``dataset.BaselineGetData`` (``latent_code`` is not read).
+    ``stills_as_rgb``: the stills are written the way ``imageio.imwrite`` writes the frame's bytes -- taken as RGB, quality 75
+    -- where the sink writes them as cv2 does (taken as BGR, quality 95): test_nerf.py:184-189 hands ONE array to both
+    writers.  Each still is then written by the rank that rendered the frame.
 
     Returns on rank 0 ``dict(n_frames, nonfinite_frames, seconds, frames_per_s, world)`` (seconds: first render to
     the file being closed), None on the other ranks.  A frame with a NaN/Inf is reported, not fatal."""
@@ -109,11 +119,18 @@ def render_head_clip(network, dataset, path, global_step, *, latent_code, frames
 
     def render_one(pos, frame):
         data = next(loader)
-        rgb = network([(*data[:7], latent_code, data[7]), global_step, dataset.data_size])[0]
+        rgb = network([_forward_tuple(data, latent_code, model), global_step, dataset.data_size])[0]
         flag = torch.zeros(1, dtype=torch.int32, device=device)
-        return ops.to8b(rgb, swap_rb, flag), flag
+        u8 = ops.to8b(rgb, swap_rb, flag)
+        if stills_as_rgb and still_every and pos % still_every == 0:
+            with open(still_path.format(i=pos), "wb") as f:
+                f.write(encode_jpeg(u8.cpu().numpy()[..., ::-1], quality=75))
+        return u8, flag
 
-    return _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, still_every, still_path, None)
+    if stills_as_rgb and still_every and not still_path:
+        raise ValueError("still_every needs still_path")
+    return _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, 0 if stills_as_rgb else still_every, still_path,
+                None)
 
 
 def _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose):
@@ -231,13 +248,16 @@ def _score(frames, score_one, network, path, group, seed, fps, codec, swap_rb, d
 
 
 def score_head_clip(network, frames, global_step, *, latent_code, frame_ids=None, path=None, seed=None, group=None, fps=25,
-                    codec="MJPG", swap_rb=False):
+                    codec="MJPG", swap_rb=False, model="head"):
     """``render_head_clip`` with the ground truth beside it.  ``frames`` is a val-mode ``dataset.ResidentFrames``: frame j of
     ``frame_ids`` (default: all of them) comes from ``frames.frame(j)`` -- no file read, no host meshgrid -- goes through
     ``network([data, global_step, frames.data_size])`` in eval mode under no_grad (the caller's mode is restored), and the float
     render is scored on the device against ``frames.imgs[j]`` per region of ``frames.maps[j]`` (``ops.frame_scores``).  No
     float frame leaves the device.  Frame-parallel like the render loops (``parallel.frames_of``; ``seed`` as there), with one
     collective at the end of the clip (``parallel.gather_frame_rows``).
+
+    ``model="baseline"``: a ``head_baseline.Network`` on a val-mode ``dataset.ResidentBaselineFrames`` (``latent_code`` is not
+    read; the torso group of its byte map is empty, so that row stays nan).
 
     ``path=None``: nothing is converted to bytes and nothing is written.  With ``path`` the clip is also written, through the
     same conversion, assembler and sink as ``render_head_clip``: the same file.
@@ -253,7 +273,7 @@ def score_head_clip(network, frames, global_step, *, latent_code, frame_ids=None
 
     def score_one(j, row, want_bytes):
         data = frames.frame(j)
-        rgb = network([(*data[:7], latent_code, data[7]), global_step, frames.data_size])[0]
+        rgb = network([_forward_tuple(data, latent_code, model), global_step, frames.data_size])[0]
         ops.frame_scores(rgb, frames.imgs[j], frames.maps[j], out=row, workspace=ws)
         if not want_bytes:
             return None, None

@@ -124,6 +124,29 @@ def torso_select_pixels(H, W, face_rect, landmark, n_rand, use_highlight, sample
     return np.concatenate([s_rect, s_norect, s_mouth], 0).astype(np.int64)
 
 
+def baseline_select_pixels(H, W, face_rect, landmark, n_rand, sample_rate):
+    """-> int64 [n_rand, 2] (row, col), head_baseline.py:124-160: ``int(n_rand * sample_rate)`` picks from the face rect minus
+    the mouth box, the rest from outside the rect, rows in that order, from the global numpy RNG exactly like upstream --
+    including its third draw (:158): ZERO picks over the mouth box's population.  It selects nothing, but a draw without
+    replacement permutes its whole population whatever its size, so it advances the generator and decides every later batch."""
+    coords, mouth_w, rect_w = _box_masks(H, W, face_rect, landmark)
+    c_rect, c_norect = coords[rect_w & ~mouth_w], coords[~rect_w]
+    rect_num = int(n_rand * sample_rate)
+    norect_num = n_rand - rect_num
+    s_rect = c_rect[np.random.choice(c_rect.shape[0], size=[rect_num], replace=False)]
+    s_norect = c_norect[np.random.choice(c_norect.shape[0], size=[norect_num], replace=False)]
+    np.random.choice(int(mouth_w.sum()), size=[0], replace=False)
+    return np.concatenate([s_rect, s_norect], 0).astype(np.int64)
+
+
+def baseline_region_byte_map(H, W, face_rect, landmark):
+    """uint8 [H, W] for the baseline: bits 0 and 1 as ``torso_region_byte_map`` (face rect minus mouth box; outside the face
+    rect) -- the two populations ``baseline_select_pixels`` picks from --, bit 2 the mouth box itself (nothing is drawn from it:
+    it is there for the per-region scores), bit 3 clear (an AD-NeRF dataset has no parsing)."""
+    _, mouth_w, rect_w = _box_masks(H, W, face_rect, landmark)
+    return ((rect_w & ~mouth_w).astype(np.uint8) | ((~rect_w).astype(np.uint8) << 1) | (mouth_w.astype(np.uint8) << 2)).reshape(H, W)
+
+
 def gather_selected(sel, poses, target, bc_img, H, W, focal, cx, cy, device):
     """Rays of the pixels `sel` (int64 [n, 2] (row, col), numpy) from each camera of `poses`, and their colours ->
     ([batch_rays [2, n, 3] per pose], target_s [n, 3], bc_rgb [n, 3]) on `device`: the device-side pinhole kernel on the whole
@@ -155,6 +178,13 @@ def torso_sample_rays(pose, pose_torso, face_rect, target, bc_img, landmark, H, 
     return batch_rays, batch_rays_torso, target_s, bc_rgb
 
 
+def baseline_sample_rays(pose, face_rect, target, bc_img, landmark, H, W, focal, cx, cy, n_rand, sample_rate, device):
+    """head_baseline.py:124-168 -> (batch_rays [2, n, 3], target_s [n, 3], bc_rgb [n, 3]) on `device`."""
+    sel = baseline_select_pixels(H, W, face_rect, landmark, n_rand, sample_rate)
+    (batch_rays,), target_s, bc_rgb = gather_selected(sel, [pose], target, bc_img, H, W, focal, cx, cy, device)
+    return batch_rays, target_s, bc_rgb
+
+
 class GetData(torch.utils.data.Dataset):
     """mode in {train, val, test}; ``args`` needs gt_dirs, testskip, N_rand, sample_rate, mouth_rays, torso_rays."""
 
@@ -171,18 +201,25 @@ class GetData(torch.utils.data.Dataset):
         self.all_poses, self.all_face_rects, self.all_exprs, auds = [], [], [], []
         for frame in self.meta["frames"][::skip]:
             fid = str(frame["img_id"])
-            self.all_imgs.append(os.path.join(data_dir, args.gt_dirs, fid + ".jpg"))
+            self.all_imgs.append(os.path.join(data_dir, self._image_dir(args), fid + ".jpg"))
             self.all_landmarks.append(os.path.join(data_dir, "ori_imgs", fid + ".lms"))
             self.all_parse_imgs.append(os.path.join(data_dir, "parsing", fid + ".png"))
             self.all_poses.append(np.array(frame["transform_matrix"]))
             auds.append(self.aud_features[min(frame["aud_id"], self.aud_features.shape[0] - 1)])
             self.all_face_rects.append(np.array(frame["face_rect"], dtype=np.int32))
-            self.all_exprs.append(frame["exp"])
+            self.all_exprs.append(self._frame_expr(frame))
         self.data_size = len(self.all_imgs)
         self.auds = torch.tensor(np.asarray(auds), dtype=torch.float)
 
     def __len__(self):
         return self.data_size
+
+    # ---- what the baseline's loader (BaselineGetData) replaces
+    def _image_dir(self, args):
+        return args.gt_dirs
+
+    def _frame_expr(self, frame):
+        return frame["exp"]
 
     def _read_image(self, index):
         return _imread(self.all_imgs[index])[..., ::-1].copy()  # upstream reads with cv2: BGR
@@ -246,6 +283,41 @@ class AggGetData(TorsoGetData):
         return batch_rays, target_s, bc_rgb
 
 
+class BaselineGetData(GetData):
+    """The AD-NeRF baseline's host-side loader (``GetData`` of NeRFs/HeadNeRF/train/head_baseline.py:47-168): the images come
+    from ``head_imgs/`` whatever ``gt_dirs`` says and are RGB (upstream reads them with imageio), the landmarks from
+    ``ori_imgs/<id>.lms``; neither ``exp`` nor ``parsing/`` is read -- an AD-NeRF dataset has neither --; the pixel selection is
+    ``baseline_select_pixels`` (upstream's numpy draw sequence, its zero-size third draw included).  ``__getitem__`` returns the
+    reference's 7-tuple (batch_rays, target_s, bc_rgb, auds, raw_img, pose, index); outside train mode ``bc_rgb`` is the whole
+    background.  ``args`` needs testskip, N_rand, sample_rate."""
+
+    def _image_dir(self, args):
+        return "head_imgs"
+
+    def _frame_expr(self, frame):
+        return None
+
+    def _read_image(self, index):
+        return _imread(self.all_imgs[index])
+
+    def _sample(self, index, target, pose):
+        a = self.args
+        landmark = np.loadtxt(self.all_landmarks[index])
+        return baseline_sample_rays(pose, self.all_face_rects[index], target, self.background_img, landmark, self.H, self.W,
+                                    self.focal, self.cx, self.cy, a.N_rand, a.sample_rate, self.device)
+
+    def __getitem__(self, index):
+        if index is None:
+            index = np.random.choice(self.data_size)
+        raw_img = torch.tensor(np.array(self._read_image(index)))
+        self.H, self.W = raw_img.shape[0], raw_img.shape[1]
+        target = raw_img.to(self.device).float() / 255.0
+        pose = self.all_poses[index][:3, :4]
+        batch_rays, target_s, bc_rgb = self._sample(index, target, pose)
+        bc_rgb = bc_rgb if self.mode == "train" else self.background_img
+        return batch_rays, target_s, bc_rgb, self.auds, raw_img, pose, index
+
+
 class ResidentFrames:
     """The training clip resident on the device, drawn from by the device-side sampler: the opt-in second data path beside
     ``GetData`` (which stays the reference's host-side loader, numpy draw sequence included).
@@ -291,7 +363,7 @@ class ResidentFrames:
         self.populations = np.zeros((n, 4), np.int64)
         for i, frame in enumerate(frames):
             fid = str(frame["img_id"])
-            img_paths.append(os.path.join(data_dir, args.gt_dirs, fid + ".jpg"))
+            img_paths.append(os.path.join(data_dir, self._image_dir(args), fid + ".jpg"))
             m = self._region_map(fid, np.array(frame["face_rect"], dtype=np.int32))
             self.populations[i] = [int(((m >> g) & 1).sum()) for g in range(4)]
             for g in range(4):
@@ -301,7 +373,7 @@ class ResidentFrames:
             maps.append(m)
             poses.append(np.array(frame["transform_matrix"])[:3, :4])
             auds.append(aud_features[min(frame["aud_id"], aud_features.shape[0] - 1)])
-            exprs.append(frame["exp"])
+            exprs.append(self._frame_expr(frame))
         self.all_poses = poses                                   # float64 [3, 4] each, as GetData keeps them
         self._cams = [ops.camera_floats(p) for p in poses]       # the same matrices as the 12 floats the kernels take
         # ---- upload
@@ -321,13 +393,15 @@ class ResidentFrames:
         self._no_rays = torch.empty(0, dtype=torch.float32, device=device)
         self.auds = torch.tensor(np.asarray(auds), dtype=torch.float).to(device)
         self.poses = torch.tensor(np.asarray(poses), dtype=torch.float32).to(device)
-        self.exprs = torch.tensor(np.asarray(exprs), dtype=torch.float32).to(device)
+        self.exprs = None if exprs and exprs[0] is None else torch.tensor(np.asarray(exprs), dtype=torch.float32).to(device)
         self._sel = torch.empty(sum(self.counts), dtype=torch.int64, device=device)
         self._ws = torch.zeros(4, dtype=torch.int32, device=device)
         if torch.device(device).type == "cuda":
             ops.byte_tables(device)                              # built here, so that batch() allocates nothing but its outputs
 
-    # ---- what the torso stage's loader (ResidentTorsoFrames) replaces
+    # ---- what the other stages' loaders (ResidentTorsoFrames, ResidentBaselineFrames) replace
+    _image_dir, _frame_expr = GetData._image_dir, GetData._frame_expr
+
     def _counts(self, args):
         """(rect, outside, mouth, torso) picks of one batch."""
         return ops.sample_counts(args.N_rand, args.mouth_rays, args.torso_rays, args.sample_rate)
@@ -424,6 +498,38 @@ class ResidentAggFrames(ResidentTorsoFrames):
     _gather = ResidentFrames._gather
 
 
+class ResidentBaselineFrames(ResidentFrames):
+    """``ResidentFrames`` for the AD-NeRF baseline: the resident counterpart of ``BaselineGetData``.  Same constructor arguments
+    (``args`` needs N_rand, sample_rate); what differs from the head stage's loader:
+
+    - the byte map is ``baseline_region_byte_map`` (no parsing image is read); counts ``ops.sample_counts(N_rand, 0, 0,
+      sample_rate)``: nothing is drawn from the mouth box, so a box of any size -- empty, or the whole rect -- leaves
+      construction alone (a rect it swallows still fails it, as upstream's first draw does).  The sampler and the gather are the
+      head stage's, unchanged;
+    - the images are RGB and come from ``head_imgs/``; no ``exp`` is read;
+    - ``batch`` returns the 7-tuple (batch_rays, target_s, bc_rgb, auds, raw_img, pose, index), ``frame`` the eval 7-tuple."""
+
+    _image_dir, _frame_expr = BaselineGetData._image_dir, BaselineGetData._frame_expr
+
+    def _counts(self, args):
+        return ops.sample_counts(args.N_rand, 0, 0, args.sample_rate)
+
+    def _region_map(self, fid, face_rect):
+        landmark = np.loadtxt(os.path.join(self.data_dir, "ori_imgs", fid + ".lms"))
+        return baseline_region_byte_map(self.H, self.W, face_rect, landmark)
+
+    def _read_image(self, path):
+        return np.array(_imread(path))
+
+    def frame(self, index):
+        index = int(index)
+        return (self._no_rays, self._no_rays, self.background_unit, self.auds, self.imgs[index], self._poses_host[index], index)
+
+    def batch(self, index, draw):
+        index = int(index)
+        return (*self._gather(index, self.select(index, draw)), self.auds, self.imgs[index], self.poses[index], index)
+
+
 # ---- test-time loaders: a trained model on a track that is not its training clip -----------------------------------------
 
 def load_test_data(datadir, aud_file, test_pose_file, testskip=1, test_size=-1, aud_start=0):
@@ -518,3 +624,44 @@ class DrivingFrames(torch.utils.data.Dataset):
         index = int(index)
         return (self._no_rays, self._no_rays, self.background_img, self.auds, self._raw_img, self.all_poses[index][:3, :4],
                 self._exprs[index], index)
+
+
+class BaselineTestFrames(torch.utils.data.Dataset):
+    """The baseline tester's loader (``GetData``, NeRFs/HeadNeRF/test/test_nerf.py:27-82): the poses and the intrinsics of
+    ``<data_dir>/transforms_exp_{mode}.json`` (``frames[::skip]``; H, W = int(2 cy), int(2 cx)) with the audio rows taken BY
+    POSITION -- frame i of the loader gets ``aud_features[i]``, whatever its ``aud_id`` says (:51-53).
+
+    ``__getitem__(j)`` is the 7-tuple ``head_baseline.Network.forward`` reads in eval mode: (empty batch_rays, empty target_s,
+    the background in [0, 1], the audio rows 0 .. n-1, a zero uint8 image of the frame's shape -- only its shape is read --,
+    the pose [3, 4], j).  No image or landmark file is opened.  ``clip.render_head_clip(model="baseline")`` takes it.
+
+    Where upstream fails at the first missing row, this raises ``ValueError`` at construction: fewer audio rows than frames, a
+    ``bc.jpg`` of another shape than (H, W)."""
+
+    def __init__(self, data_dir, aud_file, mode, args, skip=1, device="cuda"):
+        self.data_dir, self.aud_file, self.mode, self.args, self.device = data_dir, aud_file, mode, args, device
+        with open(os.path.join(data_dir, f"transforms_exp_{mode}.json")) as fp:
+            self.meta = json.load(fp)
+        self.focal, self.cx, self.cy = float(self.meta["focal_len"]), float(self.meta["cx"]), float(self.meta["cy"])
+        self.H, self.W = int(self.cy * 2), int(self.cx * 2)
+        self.skip = skip
+        self.all_poses = [np.array(f["transform_matrix"]) for f in self.meta["frames"][::skip]]
+        self.data_size = n = len(self.all_poses)
+        self.aud_features = np.load(os.path.join(data_dir, aud_file))
+        if self.aud_features.shape[0] < n:
+            raise ValueError(f"{os.path.join(data_dir, aud_file)} holds {self.aud_features.shape[0]} audio rows, the clip has {n} "
+                             "frames and takes them by position")
+        background = np.array(_imread(os.path.join(data_dir, "bc.jpg")))
+        if background.shape != (self.H, self.W, 3):
+            raise ValueError(f"{os.path.join(data_dir, 'bc.jpg')} is {background.shape}, the clip's cx / cy say {(self.H, self.W, 3)}")
+        self.background_img = torch.tensor(background / 255.0).to(device)
+        self.auds = torch.tensor(np.asarray(self.aud_features[:n]), dtype=torch.float)
+        self._raw_img = torch.zeros((self.H, self.W, 3), dtype=torch.uint8)
+        self._no_rays = torch.empty(0, dtype=torch.float32)
+
+    def __len__(self):
+        return self.data_size
+
+    def __getitem__(self, index):
+        index = int(index)
+        return (self._no_rays, self._no_rays, self.background_img, self.auds, self._raw_img, self.all_poses[index][:3, :4], index)

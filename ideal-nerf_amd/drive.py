@@ -120,3 +120,44 @@ def drive_torso(args, *, out=None, device="cuda", codec="MJPG", still_every=10, 
                                  aud_ids=aud_ids, seed=seed, codec=codec, swap_rb=True, still_every=still_every,
                                  still_path=args.save_path, group=group)
     return None if res is None else dict(res, path=out)
+
+
+def baseline_names(args):
+    """test_nerf.py:179,187 -> (the clip's file name, the stills' name pattern with ``{i}`` for the frame's position)."""
+    name = f"{args.datadir[8:].lstrip(os.sep)}_{args.aud_file[:-4]}"
+    return f"V_{name}_N_baseline.avi", name + "_ADNeRF_{i}.jpg"
+
+
+def drive_baseline(args, *, out=None, device="cuda", codec="MJPG", still_every=10, seed=None, group=None, precision=None):
+    """The baseline tester's ``test()`` (NeRFs/HeadNeRF/test/test_nerf.py:140-190) on the flags ``args``
+    (``helper.config_parser().parse_args()``): ``BaselineTestFrames(args.datadir, args.aud_file, "val", args,
+    skip=args.testskip)`` -- the val poses, frame i with audio row i --, a ``head_baseline.Network`` with
+    ``to_render_config(args)``, the weights of ``args.ft_path`` (an AD-NeRF four-dict file, ``checkpoint.load_adnerf``) -- else
+    of the newest ``*tar`` of ``basedir/expname`` (``checkpoint.load_baseline_checkpoint``; none: the network as initialised,
+    as upstream) --, every frame through ``clip.render_head_clip(model="baseline")`` at ``global_step = 0`` (:174: always the
+    unsmoothed audio branch).
+
+    ``out`` defaults to upstream's ``V_{datadir[8:]}_{aud_file[:-4]}_N_baseline.avi`` under ``args.save_path``; every
+    ``still_every``-th frame is also written there as ``{datadir[8:]}_{aud_file[:-4]}_ADNeRF_{i}.jpg``.  Channels as upstream
+    (:184-189): the red/blue-swapped bytes go to BOTH writers, the clip's (which takes them as BGR) and the stills' (which
+    takes them as RGB).  Frame-parallel inside a process group like ``drive_head``.
+    -> ``render_head_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
+    from .agg_aud_exp_nerf import build_head_network
+    frames = dataset.BaselineTestFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device)
+    network = _same_on_every_rank(lambda: build_head_network(args, frames.H, frames.W, frames.focal, "baseline")).to(device)
+    if not _unset(args.ft_path):
+        checkpoint.load_adnerf(args.ft_path, network, map_location=device)
+    else:
+        path = checkpoint.latest_checkpoint(os.path.join(args.basedir, args.expname), contains="tar")
+        if path is not None:
+            checkpoint.load_baseline_checkpoint(path, network, map_location=device)
+    if precision is not None:
+        set_render_precision(network, precision)
+    clip_name, still_name = baseline_names(args)
+    out = os.path.join(args.save_path, clip_name) if out is None else out
+    stills = os.path.join(args.save_path, still_name) if still_every else None
+    for d in {os.path.dirname(os.path.abspath(p)) for p in (out, stills) if p}:
+        os.makedirs(d, exist_ok=True)
+    res = clip.render_head_clip(network, frames, out, 0, latent_code=None, seed=seed, codec=codec, swap_rb=True,
+                                still_every=still_every, still_path=stills, group=group, model="baseline", stills_as_rgb=True)
+    return None if res is None else dict(res, path=out)

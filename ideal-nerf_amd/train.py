@@ -45,6 +45,23 @@ def train_step(network, optimizer, data, latent_codes, global_step, dataset_size
     return dict(loss=loss.detach(), psnr=psnr, latent_code_loss=latent_code_loss.detach(), lr=new_lrate)
 
 
+def baseline_train_step(network, optimizer, data, global_step, dataset_size, lrate=5e-4, lrate_decay=500):
+    """One iteration of the AD-NeRF baseline's loop (NeRFs/HeadNeRF/train/head_baseline.py:466-491) on ``head_baseline.Network``:
+    ``data`` is the baseline loader's 7-tuple (batch_rays, target_s, bg_img, auds, raw_img, pose, index); the loss is
+    mse(rgb, target) + mse(rgb0, target) (:475-481) -- there is no latent code and so no latent term."""
+    target_s = data[1]
+    rgb, _, _, _, extras = network([data, global_step, dataset_size])
+    target = target_s.reshape(-1, 3).to(rgb.device, torch.float32)
+    optimizer.zero_grad()
+    img_loss = img2mse(rgb, target)
+    loss = img_loss
+    psnr = mse2psnr(img_loss.detach())
+    if 'rgb0' in extras:
+        loss = loss + img2mse(extras['rgb0'], target)
+    new_lrate = _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay)
+    return dict(loss=loss.detach(), psnr=psnr, lr=new_lrate)
+
+
 def _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay):
     """The tail both stages' steps share: backward, the gradient all-reduce inside a process group, the Adam step and the
     decayed learning rate for the next one -> that rate."""
@@ -88,9 +105,12 @@ def draw_index(global_step, rank=0, world=1):
     return int(global_step) * int(world) + int(rank)
 
 
-def _as_loader_item(item):
-    """What the reference's DataLoader makes of a GetData item (either stage's: the tuples end in raw_img, pose, expr, index), as
-    far as Network.forward reads it: the pose as a tensor."""
+def _as_loader_item(item, with_expr=True):
+    """What the reference's DataLoader makes of a GetData item (either stage's: the tuples end in raw_img, pose, expr, index; the
+    baseline's, with_expr=False, in raw_img, pose, index), as far as Network.forward reads it: the pose as a tensor."""
+    if not with_expr:
+        *head, pose, index = item
+        return (*head, torch.as_tensor(pose, dtype=torch.float32), index)
     *head, pose, expr, index = item
     return (*head, torch.as_tensor(pose, dtype=torch.float32), expr, index)
 
@@ -139,9 +159,12 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
 
 
 def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name, flip, *, loader, sample_seed, device, steps,
-                      on_log, on_step, max_bytes, val):
+                      on_log, on_step, max_bytes, val, with_codes=True):
     """The body of ``train`` for a head-stage model (``agg_aud_exp_nerf.HEAD_MODELS``): its two loader classes, its checkpoint
-    name per epoch, and whether the validation image is channel-flipped (the loader reads BGR)."""
+    name per epoch, and whether the validation image is channel-flipped (the loader reads BGR).  with_codes=False (the AD-NeRF
+    baseline): no per-frame latent codes exist -- Adam runs over the network alone, the step is ``baseline_train_step`` on the
+    loaders' 7-tuples, ``ft_path`` is read in full (``checkpoint.load_adnerf``) and the run file is
+    ``checkpoint.save_baseline_checkpoint``'s; the returned ``latent_codes`` is None."""
     import numpy as np
     from . import checkpoint
     from .agg_aud_exp_nerf import build_head_network
@@ -175,21 +198,27 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
         write_config(args)
 
     network = build_head_network(args, H, W, focal, model, intrinsic).to(device)
-    latent_codes = torch.ones(data_size, 32, dtype=torch.float32, device=device)
+    latent_codes = torch.ones(data_size, 32, dtype=torch.float32, device=device) if with_codes else None
     network.apply(init_weights)
-    latent_codes.requires_grad = True
-    optimizer = make_optimizer(network, latent_codes, args.lrate)
+    if with_codes:
+        latent_codes.requires_grad = True
+        optimizer = make_optimizer(network, latent_codes, args.lrate)
+    else:   # head_baseline.py:460
+        optimizer = torch.optim.Adam(list(network.parameters()), lr=args.lrate, betas=(0.9, 0.999))
 
     global_step = 0
     if args.ft_path is not None and args.ft_path != 'None':
         logger.info(f'Found ckpts:{[args.ft_path]}')
-        checkpoint.load_adnerf_finetune(args.ft_path, network, map_location=device)
+        (checkpoint.load_adnerf_finetune if with_codes else checkpoint.load_adnerf)(args.ft_path, network, map_location=device)
     else:
         ckpt_path = checkpoint.latest_checkpoint(run_dir)
         if ckpt_path is not None:
             logger.info(f'Found ckpts:{ckpt_path}')
-            global_step, saved_codes = checkpoint.load_checkpoint(ckpt_path, network, optimizer, map_location=device)
-            latent_codes.data = saved_codes.to(device)
+            if with_codes:
+                global_step, saved_codes = checkpoint.load_checkpoint(ckpt_path, network, optimizer, map_location=device)
+                latent_codes.data = saved_codes.to(device)
+            else:
+                global_step = checkpoint.load_baseline_checkpoint(ckpt_path, network, optimizer, map_location=device)
 
     network.train()
 
@@ -198,25 +227,34 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
             return validation_frame(network, dataset_val, latent_codes, step, sample_seed, flip=flip), None
         return resident_validation_frame(network, frames_val, latent_codes, step, sample_seed, flip=flip)
 
+    if with_codes:
+        step_fn = lambda data, step: train_step(network, optimizer, data, latent_codes, step, data_size, lrate=args.lrate,
+                                                lrate_decay=args.lrate_decay)
+        scalars_of = lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"],
+                                       latent_code_loss=info["latent_code_loss"].item())
+        log_line = lambda sc: f"LatentLoss: {sc['latent_code_loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}"
+        save = checkpoint.save_checkpoint
+    else:
+        step_fn = lambda data, step: baseline_train_step(network, optimizer, data, step, data_size, lrate=args.lrate,
+                                                         lrate_decay=args.lrate_decay)
+        scalars_of = lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"])
+        log_line = lambda sc: f"Loss: {sc['loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}"
+        save = lambda path, net, opt, codes, step: checkpoint.save_baseline_checkpoint(path, net, opt, step)
     global_step = _run_epochs(
         args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step,
         batch=lambda it, step: (dataset_train.batch(it, draw_index(step, rank, world)) if loader == "resident"
-                                else _as_loader_item(dataset_train[it])),
-        step_fn=lambda data, step: train_step(network, optimizer, data, latent_codes, step, data_size, lrate=args.lrate,
-                                              lrate_decay=args.lrate_decay),
-        scalars_of=lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"],
-                                     latent_code_loss=info["latent_code_loss"].item()),
-        log_line=lambda sc: f"LatentLoss: {sc['latent_code_loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}",
-        validate=validate, checkpoint_name=checkpoint_name)
+                                else _as_loader_item(dataset_train[it], with_codes)),
+        step_fn=step_fn, scalars_of=scalars_of, log_line=log_line, validate=validate, checkpoint_name=checkpoint_name, save=save)
     return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
 
 
 def _run_epochs(args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step, *, batch, step_fn,
-                scalars_of, log_line, validate, checkpoint_name):
+                scalars_of, log_line, validate, checkpoint_name, save=None):
     """The skeleton both stages' ``train`` share (audio_exp_nerf.py:527-593, train_torso.py:509-574): epochs over the frames
     in order from ``global_step`` on, and per step ``step_fn(batch(it, global_step), global_step)``, the log line every
     ``i_print`` steps, ``validate(global_step) -> (image, scores or None)`` every ``100 * i_print`` and the checkpoint
-    ``checkpoint_name(epoch)`` every ``i_weights`` -- recording the COMPLETED steps; a resumed run enters its first epoch at
+    ``checkpoint_name(epoch)`` every ``i_weights`` -- recording the COMPLETED steps (through ``save(path, network, optimizer,
+    latent_codes, steps)``, default ``checkpoint.save_checkpoint``); a resumed run enters its first epoch at
     frame ``global_step % data_size``.  Rank 0 alone logs, validates and saves.  -> the global step reached."""
     from . import checkpoint
     run_dir = os.path.join(args.basedir, args.expname)
@@ -256,7 +294,7 @@ def _run_epochs(args, network, optimizer, latent_codes, data_size, global_step, 
 
                 if global_step % args.i_weights == 0 and rank == 0:
                     path = os.path.join(run_dir, checkpoint_name(epoch))
-                    checkpoint.save_checkpoint(path, network, optimizer, latent_codes, global_step + 1)
+                    (save or checkpoint.save_checkpoint)(path, network, optimizer, latent_codes, global_step + 1)
                     logger.info(f'Saved checkpoints at {path} and start to test with network')
                 global_step += 1
                 done += 1
@@ -285,12 +323,22 @@ def validation_frame(network, dataset_val, latent_codes, global_step, sample_see
     val_i = _validation_index(len(dataset_val), global_step, sample_seed)
     network.eval()
     try:
-        item = _as_loader_item(dataset_val[val_i])
+        item = _as_loader_item(dataset_val[val_i], latent_codes is not None)
         with torch.no_grad():
-            rgb = network([(*item[:-1], latent_codes[0], item[-1]), global_step, dataset_val.data_size])[0]
+            rgb = network([_eval_tuple(item, latent_codes), global_step, dataset_val.data_size])[0]
     finally:
         network.train()
-    return _pred_over_label(rgb, item[-4], flip)
+    return _pred_over_label(rgb, _raw_img(item, latent_codes), flip)
+
+
+def _eval_tuple(item, latent_codes):
+    """A loader's item as the eval forward takes it: latent code row 0 before the index (audio_exp_nerf.py:571) -- or the item
+    as it is for a model without latent codes (latent_codes None: the baseline's 7-tuple)."""
+    return item if latent_codes is None else (*item[:-1], latent_codes[0], item[-1])
+
+
+def _raw_img(item, latent_codes):
+    return item[-3] if latent_codes is None else item[-4]
 
 
 def _pred_over_label(rgb, raw_img, flip):
@@ -311,9 +359,9 @@ def resident_validation_frame(network, frames_val, latent_codes, global_step, sa
     try:
         data = frames_val.frame(val_i)
         with torch.no_grad():
-            rgb = network([(*data[:-1], latent_codes[0], data[-1]), global_step, frames_val.data_size])[0]
+            rgb = network([_eval_tuple(data, latent_codes), global_step, frames_val.data_size])[0]
             table = ops.frame_scores(rgb, frames_val.imgs[val_i], frames_val.maps[val_i])
     finally:
         network.train()
     scores = {k: [float(x) for x in v] for k, v in ops.summarise_scores(table).items()}
-    return _pred_over_label(rgb, data[-4], flip), dict(scores, frame=val_i, groups=list(ops.SCORE_GROUPS))
+    return _pred_over_label(rgb, _raw_img(data, latent_codes), flip), dict(scores, frame=val_i, groups=list(ops.SCORE_GROUPS))

@@ -4,6 +4,7 @@
 
     python tools/drive_clip.py --flow head  --config <file> [--gpus N] [--precision P] [--out PATH] [--codec raw] [--global-step S]
     python tools/drive_clip.py --flow torso --config <file> [--gpus N] [--precision P] [--out PATH] [--codec raw]
+    python tools/drive_clip.py --flow head --model baseline --config <adnerf_baseline.txt> [--gpus N] ...
 
 --flow head is ``drive.drive_head`` (the reference's eval script): the flags of the head stage's config file -- ``datadir``,
 ``aud_file``, ``evalExpr_path``, ``testskip``, ``basedir`` / ``expname`` or ``ft_path``, ``save_path`` --, the identity's val poses,
@@ -11,7 +12,9 @@ the audio from the start of the file, expressions and focal length of ``evalExpr
 directory (tools/train_head.py's ``head.tar``).  --flow torso is ``drive.drive_torso`` (the reference's ``test_torso.py
 --with_test``): the torso stage's flags -- ``test_pose_file``, ``test_size``, ``aud_start``, ``evalExpr_path`` --, the ``head.tar``
 / ``*_torso.tar`` pair tools/train_torso.py leaves in the run directory.  Every other flag of the two parsers may follow on
-the command line and ranks above the file, as in the reference.
+the command line and ranks above the file, as in the reference.  --flow head --model baseline is ``drive.drive_baseline`` (the
+reference's ``test/test_nerf.py``): the val poses with the audio rows by position, ``ft_path`` (an AD-NeRF checkpoint) or the
+newest ``*tar`` of the run directory (tools/train_head.py --model baseline), always at global step 0.
 
 --gpus N starts N ranks as fresh child processes exactly as tools/render_clip.py does; this parent never opens the GPU
 (IDN_DIST_BACKEND=gloo IDN_FORCE_DEVICE=0 rehearses N > 1 on one GPU).  --global-step (head): the step ``Network.forward`` sees,
@@ -33,7 +36,7 @@ for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 def parse(argv):
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--flow", choices=("head", "torso"), required=True)
-    pre.add_argument("--model", choices=("head", "agg"), default="head")
+    pre.add_argument("--model", choices=("head", "agg", "baseline"), default="head")
     known = pre.parse_known_args(argv)[0]
     flow = known.flow
     if flow == "head" and known.model == "agg":
@@ -51,7 +54,8 @@ def parse(argv):
     p.add_argument("--global-step", type=int, default=0)
     p.add_argument("--still-every", type=int, default=10)
     p.add_argument("--seed", type=int, default=None, help="per-frame draws seeded with seed + frame (perturb > 0)")
-    p.add_argument("--model", choices=("head", "agg"), default="head", help="--flow head: the run's model (agg: train_agg.train's)")
+    p.add_argument("--model", choices=("head", "agg", "baseline"), default="head",
+                   help="--flow head: the run's model (agg: train_agg.train's; baseline: train_baseline.train's or an AD-NeRF ft_path)")
     return p.parse_args(argv)
 
 
@@ -71,7 +75,9 @@ def main(argv=None):
         from idealnerf_amd import drive
         common = dict(out=args.out, device=dev, codec=args.codec, still_every=args.still_every, seed=args.seed,
                       precision=args.precision)
-        if args.flow == "head":
+        if args.flow == "head" and args.model == "baseline":
+            res = drive.drive_baseline(args, **common)
+        elif args.flow == "head":
             res = drive.drive_head(args, global_step=args.global_step, model=args.model, **common)
         else:
             res = drive.drive_torso(args, **common)

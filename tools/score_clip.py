@@ -36,7 +36,7 @@ for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 def parse(argv):
     import argparse
     pre = argparse.ArgumentParser(add_help=False)
-    pre.add_argument("--model", choices=("head", "agg"), default="head")
+    pre.add_argument("--model", choices=("head", "agg", "baseline"), default="head")
     if pre.parse_known_args(argv)[0].model == "agg":
         from idealnerf_amd.agg_aud_exp_nerf import config_parser   # the head stage's flags plus use_highlight
     else:
@@ -52,7 +52,9 @@ def parse(argv):
     p.add_argument("--global-step", type=int, default=None, help="default: the checkpoint's, else nosmo_iters")
     p.add_argument("--generated", action="store_true", help="(set by the parent) --datadir is a generated clip")
     p.add_argument("--timing-json", default=None)
-    p.add_argument("--model", choices=("head", "agg"), default="head", help="agg: the feature-aggregation network and its loader")
+    p.add_argument("--model", choices=("head", "agg", "baseline"), default="head",
+                   help="agg: the feature-aggregation network and its loader; baseline: the AD-NeRF baseline and its loader "
+                        "(--ckpt: a {epoch:06d}_head.tar of train_baseline.train or an AD-NeRF four-dict file)")
     return p.parse_args(argv)
 
 
@@ -85,12 +87,19 @@ def build(args, dev):
     import torch
     from idealnerf_amd import checkpoint, dataset, synthetic
     from idealnerf_amd.agg_aud_exp_nerf import build_head_network
-    resident = dataset.ResidentAggFrames if args.model == "agg" else dataset.ResidentFrames
+    resident = {"agg": dataset.ResidentAggFrames, "baseline": dataset.ResidentBaselineFrames}.get(args.model, dataset.ResidentFrames)
     frames = resident(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=dev)
     torch.manual_seed(0)   # the audio nets: every rank builds the same network
     net = build_head_network(args, frames.H, frames.W, frames.focal, args.model)
     step, latent = net.args.nosmo_iters, torch.ones(32)
-    if args.ckpt:
+    if args.ckpt and args.model == "baseline":
+        ckpt = torch.load(args.ckpt, map_location="cpu", weights_only=False)
+        if "model_state_dict" in ckpt:
+            step = checkpoint.load_baseline_checkpoint(args.ckpt, net, map_location="cpu")
+        else:
+            step = checkpoint.load_adnerf(ckpt, net) or step
+        latent = None
+    elif args.ckpt:
         step, codes = checkpoint.load_checkpoint(args.ckpt, net, map_location="cpu")
         latent = codes[0]
     else:
@@ -110,7 +119,7 @@ def score(args, dev, world):
         idealnerf_amd.set_render_precision(net, prec)
         path = None if args.avi is None else "{0}.{2}{1}".format(*os.path.splitext(args.avi), prec)
         res = clip.score_head_clip(net, frames, step, latent_code=latent, frame_ids=ids, path=path, seed=0 if args.perturb else None,
-                                   codec="MJPG")
+                                   codec="MJPG", model=args.model)
         if res is None:
             continue
         first = res if first is None else first
