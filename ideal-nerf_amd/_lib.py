@@ -133,6 +133,8 @@ PROTOTYPES = {
     "idealnerf_pass_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "idealnerf_pass_bwd": (C.c_int, [C.POINTER(FaceNerfParams), C.POINTER(FaceNerfGrads), fp, fp, fp, fp, fp, fp, fp,
                                      fp, C.c_int64, C.c_int, fp, fp, fp, fp, fp, fp, fp, C.c_size_t, fp]),
+    "idealnerf_pass_bwd_rays": (C.c_int, [C.POINTER(FaceNerfParams), C.POINTER(FaceNerfGrads), fp, fp, fp, fp, fp, fp, fp,
+                                          fp, C.c_int64, C.c_int, fp, fp, fp, fp, fp, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_pass_bwd_cond": (C.c_int, [C.POINTER(FaceNerfParams), fp, fp, fp, fp, fp, fp, fp, fp, C.c_int64, C.c_int, fp, fp, fp,
                                           fp, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_facenerf_train_fwd": (C.c_int, [fp, fp, C.c_int, fp, C.c_int64, fp, fp, fp]),

@@ -5,7 +5,8 @@ One ``torch.autograd.Function`` per render: forward runs the HIP stages with the
 activation-saving MLP variant, backward is two C calls (fine pass, coarse pass), each
 compositing-backward + 11 layers of MFMA GEMMs + the conditioning fold.  Gradients reach
 every FaceNeRF parameter of both networks, ``aud_para`` (and through it the audio nets,
-which stay ordinary autograd modules) and ``latent_code``.  Sampled depths are detached
+which stay ordinary autograd modules), ``latent_code`` and -- only when ``rays`` require one (pose refinement,
+pose_refine.py) -- the ray records: origins, directions and view directions, summed over the two passes.  Sampled depths are detached
 exactly as upstream (:345); ``expr`` is data.  A FaceNeRFAgg pair (agg_aud_exp_nerf.Network) goes through the same function:
 each network's fused feature is its conditioning vector, its columns of ``views_linears.0`` are a bias term
 (``_pass_bwd``), and torch carries the feature's gradient into ``agg_linears`` and the audio nets.
@@ -42,15 +43,23 @@ def _train_query(net, folded, rays, z):
     return ops.query_rays_train_fwd(net.packed_weights(prec_name), folded, rays, z, code)
 
 
-def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, frozen=False):
+def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, frozen=False,
+              d_rays=None):
     """One pass's backward -> its 24 parameter gradients by PARAM_KEYS.  frozen = (need_aud, need_latent) for a network none of
     whose parameters needs a gradient: the conditioning-only plan -- d_aud / d_latent alone, each only if needed (neither: no
     launch at all), and None for every parameter.
 
     A network whose ``bias_columns()`` is a block E of ``views_linears.0.weight`` (FaceNeRFAgg: E @ aud is part of that layer's
     bias) gets, from the layer's bias gradient b: dE = outer(b, aud) appended to the kernels' weight gradient, and
-    d_aud += E^T b (frozen: b alone, from the conditioning-only plan's deltas)."""
+    d_aud += E^T b (frozen: b alone, from the conditioning-only plan's deltas).
+
+    d_rays [n, 11] (pose refinement): OVERWRITTEN with the pass's gradient of the ray records, by the entry that also runs
+    the input-row gradient and its per-ray reduction (ops.pass_bwd_rays); None: that entry is never reached.  The frozen
+    plan has no ray gradient."""
     ext = net.bias_columns()
+    if frozen and d_rays is not None:
+        raise _lib.IdealNerfError("rays require a gradient but the network is frozen: the conditioning-only backward "
+                                  "(idealnerf_pass_bwd_cond) returns no ray gradient")
     if frozen:
         d_aud, d_latent = (d if want else None for d, want in zip((d_aud, d_latent), frozen))
         if d_aud is not None or d_latent is not None:
@@ -65,7 +74,11 @@ def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw,
     sd = net.kernel_tensors()
     # (no column stays uninitialised: the fold kernel writes all conditioning columns, the GEMM reductions all others)
     grads = {k: torch.empty_like(sd[k]) for k in PARAM_KEYS}
-    ops.pass_bwd(net.kernel_params(), grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+    args = (net.kernel_params(), grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+    if d_rays is None:
+        ops.pass_bwd(*args)
+    else:
+        ops.pass_bwd_rays(*args, d_rays)
     if ext is not None:
         b = grads["views_linears.0.bias"]
         if d_aud is not None:
@@ -107,6 +120,12 @@ class RenderRaysFn(torch.autograd.Function):
         # (need d aud of the coarse pass, of the fine pass -- one and the same where the vector is shared --, need d latent)
         ctx.needs = (need_aud, need_aud if aud_fine is None else aud_fine.requires_grad, latent is not None and latent.requires_grad)
         ctx.shared_aud = aud_fine is None
+        if ctx.needs_input_grad[5]:   # rays (pose refinement): both passes run the full backward, or none can return d rays
+            n_keys = len(PARAM_KEYS)
+            trained = [any(t.requires_grad for t in params[i * n_keys:(i + 1) * n_keys]) for i in range(2 if Ni > 0 else 1)]
+            if not all(trained):
+                raise _lib.IdealNerfError("rays require a gradient but a network of the pair is frozen (none of its parameters "
+                                          "requires one): the conditioning-only backward returns no ray gradient")
         if Ni == 0:
             ctx.saved = (rays, bc, raw_c, z_c, acts_c)
             outs = [comp_c["rgb_map"], comp_c["disp_map"], comp_c["acc_map"]]
@@ -144,20 +163,30 @@ class RenderRaysFn(torch.autograd.Function):
             d_aud = torch.zeros_like(aud) if need_aud or not frozen_c else None
             d_aud_f = torch.zeros_like(aud_f) if Ni > 0 and (need_aud_f or not frozen_f) else None
         c = lambda t: None if t is None else t.contiguous()
+        # d rays: one buffer per pass (each entry overwrites its own), only when rays require a gradient -- otherwise nothing
+        # new is allocated or launched and the step is what it was
+        need_rays = ctx.needs_input_grad[5]
+        new_d_rays = lambda: torch.empty_like(ctx.saved[0]) if need_rays else None
         if Ni == 0:
             rays, bc, raw_c, z_c, acts_c = ctx.saved
+            d_rays = new_d_rays()
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[0]), c(g[3]) if with_fg else None,
-                           None, c(g[2]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat))
+                           None, c(g[2]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat), d_rays=d_rays)
             gf = {k: None for k in PARAM_KEYS}
         else:
             rays, bc, raw_c, z_c, acts_c, raw_f, z_f, acts_f = ctx.saved
+            d_rays_f, d_rays = new_d_rays(), new_d_rays()
             gf = _pass_bwd(fine, aud_f, expr, lat, acts_f, raw_f, z_f, rays, bc, c(g[0]), c(g[8]) if with_fg else None,
-                           c(g[7]), c(g[2]), d_aud_f, d_lat, frozen=frozen_f and (need_aud_f, need_lat))
+                           c(g[7]), c(g[2]), d_aud_f, d_lat, frozen=frozen_f and (need_aud_f, need_lat), d_rays=d_rays_f)
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[3]), c(g[9]) if with_fg else None,
-                           c(g[10]) if with_fg else None, c(g[5]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat))
+                           c(g[10]) if with_fg else None, c(g[5]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat),
+                           d_rays=d_rays)
+            if need_rays:
+                d_rays += d_rays_f   # coarse + fine, one fp32 addition per element
         ctx.saved = None
         param_grads = [gc[k] for k in PARAM_KEYS] + [gf[k] for k in PARAM_KEYS]
         fixed = [None] * RenderRaysFn.N_FIXED
+        fixed[5] = d_rays
         fixed[10] = d_aud if need_aud else None
         fixed[11] = d_aud_f if need_aud_f and not ctx.shared_aud else None
         fixed[12] = d_lat if need_lat else None
@@ -167,7 +196,9 @@ class RenderRaysFn(torch.autograd.Function):
 def render_rays_apply(network, coarse, fine, rays, bc_rgb, aud_para, latent_code, expr, perturb, pytest, with_fg=False,
                       lindisp=False):
     args = network.args
-    rays = rays.detach().to(torch.float32).contiguous()
+    if not rays.requires_grad:   # rays that require a gradient (pose refinement) keep their graph edge
+        rays = rays.detach()
+    rays = rays.to(torch.float32).contiguous()
     bc = bc_rgb.detach().to(torch.float32).contiguous()
     n, dev = rays.shape[0], rays.device
     S, Ni = args.N_samples, args.N_importance

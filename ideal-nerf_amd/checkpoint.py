@@ -25,12 +25,28 @@ def latest_checkpoint(run_dir: str, contains: str = ".tar"):
     return os.path.join(run_dir, names[-1]) if names else None
 
 
-def save_checkpoint(path: str, network, optimizer, latent_codes, global_step: int):
-    """audio_exp_nerf.py:586-591."""
+def _with_pose_deltas(ckpt: dict, pose_deltas):
+    """The file gains ``pose_deltas`` [n_frames, 6] only for a run that refines its cameras (pose_refine.PoseRefiner)."""
+    if pose_deltas is not None:
+        ckpt["pose_deltas"] = pose_deltas.detach().clone()
+    return ckpt
+
+
+def save_checkpoint(path: str, network, optimizer, latent_codes, global_step: int, pose_deltas=None):
+    """audio_exp_nerf.py:586-591.  pose_deltas (no counterpart upstream): see ``load_pose_deltas``; None: upstream's keys."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    torch.save({"global_step": global_step, "model_state_dict": network.state_dict(),
-                "optimizer": optimizer.state_dict() if optimizer is not None else None,
-                "latent_codes": latent_codes.data}, path)
+    torch.save(_with_pose_deltas({"global_step": global_step, "model_state_dict": network.state_dict(),
+                                  "optimizer": optimizer.state_dict() if optimizer is not None else None,
+                                  "latent_codes": latent_codes.data}, pose_deltas), path)
+
+
+def load_pose_deltas(path: str, map_location=None):
+    """-> the ``pose_deltas`` [n_frames, 6] a run with pose refinement saved.  A file without them raises: resuming such a run
+    from a checkpoint of a run without refinement would silently restart the cameras."""
+    ckpt = torch.load(path, map_location=map_location, weights_only=False)
+    if "pose_deltas" not in ckpt:
+        raise KeyError(f"{path} holds no pose_deltas: it was written by a run without pose refinement")
+    return ckpt["pose_deltas"]
 
 
 def load_checkpoint(path: str, network, optimizer=None, map_location=None, strict=True):
@@ -46,14 +62,14 @@ def load_checkpoint(path: str, network, optimizer=None, map_location=None, stric
 DATA_PARALLEL_PREFIX = "module."
 
 
-def save_baseline_checkpoint(path: str, network, optimizer, global_step: int):
+def save_baseline_checkpoint(path: str, network, optimizer, global_step: int, pose_deltas=None):
     """The AD-NeRF baseline's run file (head_baseline.py:516-520): {'global_step', 'model_state_dict', 'optimizer'}, no latent
     codes.  Upstream wraps the network in ``nn.DataParallel`` on this path (:448), so its keys carry ``module.``: they are
     written that way, and upstream's trainer and tester load the file as their own."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    torch.save({"global_step": global_step,
-                "model_state_dict": {DATA_PARALLEL_PREFIX + k: v for k, v in network.state_dict().items()},
-                "optimizer": optimizer.state_dict() if optimizer is not None else None}, path)
+    torch.save(_with_pose_deltas({"global_step": global_step,
+                                  "model_state_dict": {DATA_PARALLEL_PREFIX + k: v for k, v in network.state_dict().items()},
+                                  "optimizer": optimizer.state_dict() if optimizer is not None else None}, pose_deltas), path)
 
 
 def load_baseline_checkpoint(path: str, network, optimizer=None, map_location=None):

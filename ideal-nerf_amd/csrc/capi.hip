@@ -364,6 +364,24 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
                            (hipStream_t)stream);
 }
 
+int idealnerf_pass_bwd_rays(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
+                            const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
+                            const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
+                            const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
+                            float* d_latent, float* d_rays, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_grads(grads)) return e;
+    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
+        (p->dim_latent > 0) != (latent != nullptr))
+        return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
+    if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
+    if (n_rays == 0) return IDN_OK;
+    if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_pass_bwd(*p, grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
+                           g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
+                           (hipStream_t)stream, d_rays);
+}
+
 int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, const float* expr, const float* latent,
                             const float* acts, const float* raw, const float* z, const float* rays, const float* bc_rgb,
                             int64_t n_rays, int n_samples, const float* g_rgb_map, const float* g_rgb_fg,

@@ -277,7 +277,11 @@ int launch_composite(const float* raw, const float* z, const float* rays, const 
         case 1: hipLaunchKernelGGL(composite_kernel<1>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
         case 2: hipLaunchKernelGGL(composite_kernel<2>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
         case 3: hipLaunchKernelGGL(composite_kernel<3>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        default: hipLaunchKernelGGL(composite_kernel<4>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
+        case 4: hipLaunchKernelGGL(composite_kernel<4>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
+        case 5: hipLaunchKernelGGL(composite_kernel<5>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
+        case 6: hipLaunchKernelGGL(composite_kernel<6>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
+        case 7: hipLaunchKernelGGL(composite_kernel<7>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
+        default: hipLaunchKernelGGL(composite_kernel<8>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
     }
     IDN_HIP_CHECK(hipGetLastError());
     return IDN_OK;

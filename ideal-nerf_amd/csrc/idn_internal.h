@@ -322,7 +322,11 @@ size_t bwd_workspace_bytes(int64_t n_points);
 int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
-                    const float* g_acc, float* d_aud, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s);
+                    const float* g_acc, float* d_aud, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s,
+                    float* d_rays = nullptr);   // d_rays [n_rays, 11] != null: also the gradient of the ray records (overwritten)
+// ray_grad.hip: d_x [n_rays * S, 90] (the input-row gradient of the pass's points) -> d_rays [n_rays, 11]; column 6 of d_rays
+// holds dL / d |rays_d| on entry
+int launch_ray_grad(const float* d_x, const float* rays, const float* z, int64_t n_rays, int S, float* d_rays, hipStream_t s);
 // FaceNeRF.forward's backward on pre-embedded rows: head deltas from g_out [n, 4], the same tail as launch_pass_bwd, d expr
 // from the fold and (d_x != null) the input-row gradient d_x [n, 90]
 int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,

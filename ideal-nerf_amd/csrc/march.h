@@ -5,7 +5,7 @@
 
 namespace idn {
 
-constexpr int kMaxSpl = 4;  // samples per lane: S <= 256
+constexpr int kMaxSpl = 8;  // samples per lane: S <= 512 (a fine pass of 256 + 256; the march itself stops at kMaxBins)
 
 // Philox4x32-10 (Salmon et al., SC'11): ten rounds on the counter (c0..c3) under the key (k0, k1).  The one round function of
 // the library: the draw table below and the ray sampler's sort keys (sampler.hip) both come from it.

@@ -6,12 +6,15 @@
 //   delta chain       all delta_l = (delta_{l+1} . W_{l+1}) (.) [a_l > 0] in one fused kernel (mlp_f32_bwd.hip)
 //   dW products       dW_l = delta_l^T . a_{l-1} and db_l = sum_p delta_l: dw_gemm.hip, scheduled by DwPass (dw_gemm.h)
 //   fold_bwd          conditioning columns of W0 / W5 / Wv0 and d aud, d latent
+//   ray gradient      (idealnerf_pass_bwd_rays) after all of that: dx_kernel into the workspace, then ray_grad.hip; the compositing
+//                     backward's kNorm variant supplies dL / d |rays_d|
 //   frozen network    (no gradient tensors: idealnerf_pass_bwd_cond) instead of the dW products, colsum_rows / colsum_finish on
 //                     dA[0] and dA[5], and the d cond range of fold_bwd alone
 //
 // Activations come from the training variant of the MLP kernel as row-major matrices
 // (idn_internal.h, "activation slab").  Everything is deterministic: no float atomics.
 #include "dw_gemm.h"
+#include "march.h"
 #include <cstdlib>
 
 namespace idn {
@@ -42,9 +45,12 @@ struct CompBwdArgs {
     float* d_rgb; int ld_rgb;    // row p = ray*S+s: d raw_rgb at d_rgb[p*ld_rgb + 0..2]
     float* d_sig; int ld_sig;    // d raw_sigma at d_sig[p*ld_sig]
     long n_rays; int S;
+    float* d_norm; int ld_norm;  // kNorm kernels only: dL / d |rays_d| = sum_{s < S-1} (dL / d dist_s) (z_{s+1} - z_s) at d_norm[ray*ld_norm]
 };
 
-template <int SPL>
+// kNorm: also the per-ray gradient of dists = dz * |rays_d| with respect to the norm (baseline.py:341-343; the ray's last
+// sample is left out: across its 1e10 spacing alpha is saturated).  The other outputs are the same instructions either way.
+template <int SPL, bool kNorm = false>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const long ray = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -126,6 +132,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) total += shfl_xor_dd(total, m);
     double before = pin - lsum;  // sum over earlier lanes
+    double nsum = 0.0;           // kNorm: this lane's share of dL / d |rays_d|
 #pragma unroll
     for (int i = 0; i < SPL; ++i) {
         const int s = lane * SPL + i;
@@ -134,6 +141,10 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
             const double suffix = total - before;            // sum_{t > s} dw_t w_t
             const float dalpha = dw[i] * T[i] - (float)(suffix / (double)tf[i]);
             const float dsig = (rw[i].w > 0.f) ? dalpha * ex[i] * dist[i] : 0.f;
+            if constexpr (kNorm) {
+                if (s < S - 1)
+                    nsum += (double)dalpha * (double)ex[i] * (double)(fmaxf(rw[i].w, 0.0f) + 1e-6f) * (double)(zs[i + 1] - zs[i]);
+            }
             const long p = ray * S + s;
             a.d_sig[p * a.ld_sig] = dsig;
             float d0 = 0.f, d1 = 0.f, d2 = 0.f;
@@ -146,6 +157,11 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
             a.d_rgb[p * a.ld_rgb + 1] = d1;
             a.d_rgb[p * a.ld_rgb + 2] = d2;
         }
+    }
+    if constexpr (kNorm) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) nsum += shfl_xor_dd(nsum, m);
+        if (lane == 0) a.d_norm[ray * a.ld_norm] = (float)nsum;
     }
 }
 
@@ -397,13 +413,36 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
     return IDN_OK;
 }
 
+// d_x [n, 90] = dL / d (input rows) from the deltas of pts_linears.0 / .5 and views_linears.0 a backward has left in `w`
+// (dx_kernel, below)
+static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, int64_t Pp, float* d_x, hipStream_t s);
+
+template <bool kNorm>
+static void launch_composite_bwd(const CompBwdArgs& a, int64_t n_rays, int S, hipStream_t s) {
+    const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
+    switch ((S + 63) / 64) {
+        case 1: hipLaunchKernelGGL((composite_bwd_kernel<1, kNorm>), grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((composite_bwd_kernel<2, kNorm>), grid, block, 0, s, a); break;
+        case 3: hipLaunchKernelGGL((composite_bwd_kernel<3, kNorm>), grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((composite_bwd_kernel<4, kNorm>), grid, block, 0, s, a); break;
+        case 5: hipLaunchKernelGGL((composite_bwd_kernel<5, kNorm>), grid, block, 0, s, a); break;
+        case 6: hipLaunchKernelGGL((composite_bwd_kernel<6, kNorm>), grid, block, 0, s, a); break;
+        case 7: hipLaunchKernelGGL((composite_bwd_kernel<7, kNorm>), grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((composite_bwd_kernel<8, kNorm>), grid, block, 0, s, a); break;
+    }
+}
+
+// d_rays != nullptr (idealnerf_pass_bwd_rays): after the backward, the input-row gradient of the pass's points (into the
+// workspace: the delta matrix of pts_linears.1 is free once the weight gradients are reduced, and p_pad x 256 floats hold
+// n x 90) and its reduction to the ray records (ray_grad.hip).  The compositing backward leaves dL / d |rays_d| in column 6
+// of d_rays, which the reduction reads before it writes that column's zero.
 int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
-                    const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s) {
+                    const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s, float* d_rays) {
     const int64_t P = n_rays * S;
     const int64_t Pp = (P + 127) / 128 * 128;
-    if (S < 2 || S > 256) return fail(IDN_EUNSUPPORTED, "pass_bwd: n_samples %d outside [2, 256]", S);
+    if (S < 2 || S > 64 * kMaxSpl) return fail(IDN_EUNSUPPORTED, "pass_bwd: n_samples %d outside [2, %d]", S, 64 * kMaxSpl);
     const BwdWs w = carve_bwd(reinterpret_cast<char*>(ws_), Pp);
     if (!ws_ || ws_bytes < w.bytes) return fail(IDN_EWORKSPACE, "backward workspace %zu < %zu", ws_bytes, w.bytes);
 
@@ -417,17 +456,19 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, 
     if (Pp > P) IDN_HIP_CHECK(hipMemsetAsync(w.dV0 + (size_t)P * 256, 0, (size_t)(Pp - P) * 256 * 4, s));
     {
         CompBwdArgs a{reinterpret_cast<const float4*>(raw), z, rays, bc, g_rgb, g_fg, g_lw, g_acc,
-                      w.dRGB, 64, w.dV0 + kSigmaChannel, 256, (long)n_rays, S};
-        const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-        switch ((S + 63) / 64) {
-            case 1: hipLaunchKernelGGL(composite_bwd_kernel<1>, grid, block, 0, s, a); break;
-            case 2: hipLaunchKernelGGL(composite_bwd_kernel<2>, grid, block, 0, s, a); break;
-            case 3: hipLaunchKernelGGL(composite_bwd_kernel<3>, grid, block, 0, s, a); break;
-            default: hipLaunchKernelGGL(composite_bwd_kernel<4>, grid, block, 0, s, a); break;
-        }
+                      w.dRGB, 64, w.dV0 + kSigmaChannel, 256, (long)n_rays, S, d_rays ? d_rays + 6 : nullptr, IDN_RAY_FLOATS};
+        if (d_rays) launch_composite_bwd<true>(a, n_rays, S, s);
+        else launch_composite_bwd<false>(a, n_rays, S, s);
         IDN_HIP_CHECK(hipGetLastError());
     }
-    return bwd_tail(p, gr, aud, expr, latent, acts, Pp, w, d_aud, nullptr, d_latent, s);
+    if (int e = bwd_tail(p, gr, aud, expr, latent, acts, Pp, w, d_aud, nullptr, d_latent, s)) return e;
+    if (d_rays) {
+        float* d_x = w.dA[1];
+        static_assert(IDN_PTS_CH + IDN_VIEWS_CH <= 256, "the input-row gradient fits a delta matrix");
+        if (int e = launch_dx(p, w, P, Pp, d_x, s)) return e;
+        return launch_ray_grad(d_x, rays, z, n_rays, S, d_rays, s);
+    }
+    return IDN_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -543,6 +584,24 @@ __global__ __launch_bounds__(64 * kDxWaves, 1) void dx_kernel(DxArgs a) {
     }
 }
 
+static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, int64_t Pp, float* d_x, hipStream_t s) {
+    static LaunchSetup setup;
+    int num_cu = 0;
+    if (int e = setup.get([]() -> int {
+            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDxLds));
+            return IDN_OK;
+        }, &num_cu))
+        return e;
+    const int C = p.dim_aud + p.dim_expr + p.dim_latent;
+    const DxArgs da{p.pts_w[0], IDN_PTS_CH + C, p.pts_w[5], IDN_PTS_CH + C + IDN_W, p.views_w[0], IDN_W + IDN_VIEWS_CH + p.dim_expr,
+                    w.dA[0], w.dA[5], w.dV0, (long)n, (long)Pp, d_x};
+    const int64_t groups = (Pp / 32 + kDxWaves - 1) / kDxWaves;
+    const int grid = (int)(groups < num_cu ? groups : num_cu);
+    hipLaunchKernelGGL(dx_kernel, dim3(grid), dim3(64 * kDxWaves), kDxLds, s, da);
+    IDN_HIP_CHECK(hipGetLastError());
+    return IDN_OK;
+}
+
 int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
                         const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
                         float* d_expr, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s) {
@@ -556,22 +615,7 @@ int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& 
         IDN_HIP_CHECK(hipGetLastError());
     }
     if (int e = bwd_tail(p, &gr, aud, expr, latent, acts, Pp, w, d_aud, d_expr, d_latent, s)) return e;
-    if (d_x) {
-        static LaunchSetup setup;
-        int num_cu = 0;
-        if (int e = setup.get([]() -> int {
-                IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDxLds));
-                return IDN_OK;
-            }, &num_cu))
-            return e;
-        const int C = p.dim_aud + p.dim_expr + p.dim_latent;
-        const DxArgs da{p.pts_w[0], IDN_PTS_CH + C, p.pts_w[5], IDN_PTS_CH + C + IDN_W, p.views_w[0], IDN_W + IDN_VIEWS_CH + p.dim_expr,
-                        w.dA[0], w.dA[5], w.dV0, (long)n, (long)Pp, d_x};
-        const int64_t groups = (Pp / 32 + kDxWaves - 1) / kDxWaves;
-        const int grid = (int)(groups < num_cu ? groups : num_cu);
-        hipLaunchKernelGGL(dx_kernel, dim3(grid), dim3(64 * kDxWaves), kDxLds, s, da);
-        IDN_HIP_CHECK(hipGetLastError());
-    }
+    if (d_x) return launch_dx(p, w, n, Pp, d_x, s);
     return IDN_OK;
 }
 

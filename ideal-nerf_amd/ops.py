@@ -217,21 +217,25 @@ def query_rays_train_fwd(packed, folded, rays, z, precision=_lib.IDN_PREC_BF16X6
     return raw, acts
 
 
-def _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias=None):
-    """The checks and the call behind `pass_bwd` (grads: a dict) and `pass_bwd_cond` (grads: None)."""
+def _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias=None,
+              d_rays=None, with_rays=False):
+    """The checks and the call behind `pass_bwd` (grads: a dict), `pass_bwd_rays` (with_rays) and `pass_bwd_cond` (grads: None)."""
     lib = _lib.load()
     if grads is None:
         grads = {}
     n, S = z.shape
     for t, name, shape in ((raw, "raw", (n, S, 4)), (rays, "rays", (n, RAY_FLOATS)), (bc, "bc_rgb", (n, 3)),
                            (g_rgb, "g_rgb_map", (n, 3)), (g_fg, "g_rgb_fg", (n, 3)), (g_lw, "g_last_weight", (n,)),
-                           (g_acc, "g_acc", (n,))):
+                           (g_acc, "g_acc", (n,)), (d_rays, "d_rays", (n, RAY_FLOATS))):
         _shape(t, name, *shape)
     tensors = (aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
-    with _Launch(*tensors, *grads.values()) as L:
+    with _Launch(*tensors, d_rays, *grads.values()) as L:
         ws = _workspace(lib.idealnerf_pass_bwd_workspace_bytes(n, S), z.device, L.stream)   # scratch of this (device, stream): two streams training on one GPU do not share it
         ptrs = [_ptr(t) for t in tensors]
-        if grads:
+        if with_rays:
+            check(lib.idealnerf_pass_bwd_rays(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], _ptr(d_rays, "d_rays"),
+                                              ws.data_ptr(), ws.numel(), L.stream))
+        elif grads:
             check(lib.idealnerf_pass_bwd(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
         else:
             check(lib.idealnerf_pass_bwd_cond(C.byref(p), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
@@ -250,6 +254,13 @@ def pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g
     """Backward of one render pass (idealnerf_pass_bwd) from the slab of query_rays_train_fwd.  grads: as facenerf_bwd,
     OVERWRITTEN; g_* = dL/d (rgb_map, rgb_fg, last_weight, acc_map), each may be None; d_aud / d_latent: accumulated."""
     return _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
+
+
+def pass_bwd_rays(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_rays):
+    """`pass_bwd` that also returns the gradient of the ray records (idealnerf_pass_bwd_rays): d_rays [n, 11], OVERWRITTEN --
+    columns 0:3 d rays_o, 3:6 d rays_d, 8:11 d viewdirs, 6:8 zeros.  d_rays None: the entry behaves as `pass_bwd`."""
+    return _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent,
+                     d_rays=d_rays, with_rays=True)
 
 
 def pass_bwd_cond(p, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias=None):

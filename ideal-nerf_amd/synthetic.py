@@ -98,3 +98,32 @@ def write_clip_directory(d, size, n_frames, seed=0, flat=False, N_rand=64, mouth
             json.dump(meta, f)
     return SimpleNamespace(gt_dirs="head_imgs", testskip=1, N_rand=N_rand, sample_rate=sample_rate, mouth_rays=mouth_rays,
                            torso_rays=torso_rays), meta
+
+
+def perturb_train_poses(d, degrees, length, seed=0):
+    """Seeded noise on the TRAINING cameras of a generated directory (tools/train_head.py --pose_noise): each frame's c2w becomes
+    [R(w) R | t + e] with w uniform on the sphere of radius ``degrees`` (as an angle) and e on the sphere of radius ``length``.
+    The clean file is kept beside it as transforms_exp_train_clean.json: the ground truth a pose-refinement run is scored
+    against.  Validation poses stay clean.  -> (noisy c2w [n, 4, 4], clean c2w [n, 4, 4])."""
+    import json
+    import os
+    from .pose_refine import rotation
+    path = os.path.join(d, "transforms_exp_train.json")
+    with open(path) as f:
+        meta = json.load(f)
+    with open(os.path.join(d, "transforms_exp_train_clean.json"), "w") as f:
+        json.dump(meta, f)
+    rs = np.random.RandomState(seed + 4242)
+    unit = lambda v: v / np.linalg.norm(v, axis=-1, keepdims=True)
+    n = len(meta["frames"])
+    w = torch.from_numpy(unit(rs.standard_normal((n, 3))) * math.radians(degrees))
+    e = torch.from_numpy(unit(rs.standard_normal((n, 3))) * length)
+    clean = torch.tensor([fr["transform_matrix"] for fr in meta["frames"]], dtype=torch.float64)
+    noisy = clean.clone()
+    noisy[:, :3, :3] = rotation(w) @ clean[:, :3, :3]
+    noisy[:, :3, 3] = clean[:, :3, 3] + e
+    for fr, m in zip(meta["frames"], noisy):
+        fr["transform_matrix"] = m.tolist()
+    with open(path, "w") as f:
+        json.dump(meta, f)
+    return noisy, clean

@@ -72,7 +72,8 @@ def _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay):
     optimizer.step()
     new_lrate = decayed_lr(lrate, lrate_decay, global_step)
     for group in optimizer.param_groups:
-        group['lr'] = new_lrate
+        # (a group with a rate of its own -- the pose deltas -- follows the same schedule at its own scale)
+        group['lr'] = new_lrate * group['lr_scale'] if 'lr_scale' in group else new_lrate
     return new_lrate
 
 
@@ -124,7 +125,7 @@ def _summary_writer(logdir):
 
 
 def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30,
-          val="reference"):
+          val="reference", refine_poses=False, pose_lrate=None):
     """The reference's ``train()`` (audio_exp_nerf.py:451-593) on the flags ``args`` (``helper.config_parser().parse_args()``):
     write_config, the train and validation datasets, ``Network`` + ``init_weights``, ``latent_codes = ones[n_frames, 32]``, Adam,
     warm start from ``ft_path`` or resume from the newest ``*.tar`` of ``basedir/expname``, then epochs over the frames in
@@ -151,20 +152,28 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     ("val", step, image [3, 2 H, W] RGB: prediction over ground truth) and, with val = "resident", ("val_scores", step,
     {frame, groups, mse, psnr, ssim: one value per ops.SCORE_GROUPS}); ``on_step(global_step, info)`` runs after every step.
     Inside a process group every rank trains (``train_step`` all-reduces the gradients); rank 0 alone logs and saves.
-    -> dict(network, optimizer, latent_codes, global_step, data_size)."""
+
+    refine_poses (no counterpart upstream; off: nothing below exists and the run is what it was): the training cameras are
+    refined jointly with the model (``pose_refine.PoseRefiner``: one (omega, tau) per training frame, zero at the start).  Each
+    step's ray batch goes through the frame's correction before the network sees it, and the render backward returns the
+    gradient of the rays.  The deltas are a third parameter set of the same Adam, in a group of their own whose rate is
+    ``pose_lrate`` (default 0.1 * lrate: a starting point nobody has tuned) and decays by the same schedule; inside a process
+    group the gradient all-reduce covers them.  The checkpoint gains ``pose_deltas`` and a resumed run restores them.  Validation
+    frames are rendered from their own poses.
+    -> dict(network, optimizer, latent_codes, global_step, data_size[, pose_refiner])."""
     from . import dataset
     return _train_head_model(args, "head", dataset.ResidentFrames, dataset.GetData, lambda epoch: 'head.tar', True, loader=loader,
                              sample_seed=sample_seed, device=device, steps=steps, on_log=on_log, on_step=on_step,
-                             max_bytes=max_bytes, val=val)
+                             max_bytes=max_bytes, val=val, refine_poses=refine_poses, pose_lrate=pose_lrate)
 
 
 def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name, flip, *, loader, sample_seed, device, steps,
-                      on_log, on_step, max_bytes, val, with_codes=True):
+                      on_log, on_step, max_bytes, val, with_codes=True, refine_poses=False, pose_lrate=None):
     """The body of ``train`` for a head-stage model (``agg_aud_exp_nerf.HEAD_MODELS``): its two loader classes, its checkpoint
     name per epoch, and whether the validation image is channel-flipped (the loader reads BGR).  with_codes=False (the AD-NeRF
     baseline): no per-frame latent codes exist -- Adam runs over the network alone, the step is ``baseline_train_step`` on the
     loaders' 7-tuples, ``ft_path`` is read in full (``checkpoint.load_adnerf``) and the run file is
-    ``checkpoint.save_baseline_checkpoint``'s; the returned ``latent_codes`` is None."""
+    ``checkpoint.save_baseline_checkpoint``'s; the returned ``latent_codes`` is None.  refine_poses / pose_lrate: as ``train``."""
     import numpy as np
     from . import checkpoint
     from .agg_aud_exp_nerf import build_head_network
@@ -205,6 +214,12 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
         optimizer = make_optimizer(network, latent_codes, args.lrate)
     else:   # head_baseline.py:460
         optimizer = torch.optim.Adam(list(network.parameters()), lr=args.lrate, betas=(0.9, 0.999))
+    refiner = None
+    if refine_poses:
+        from .pose_refine import PoseRefiner
+        refiner = PoseRefiner(data_size).to(device)
+        pose_lrate = 0.1 * args.lrate if pose_lrate is None else float(pose_lrate)
+        optimizer.add_param_group({'params': [refiner.deltas], 'lr': pose_lrate, 'lr_scale': pose_lrate / args.lrate})
 
     global_step = 0
     if args.ft_path is not None and args.ft_path != 'None':
@@ -219,6 +234,8 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
                 latent_codes.data = saved_codes.to(device)
             else:
                 global_step = checkpoint.load_baseline_checkpoint(ckpt_path, network, optimizer, map_location=device)
+            if refiner is not None:
+                refiner.deltas.data.copy_(checkpoint.load_pose_deltas(ckpt_path, map_location=device))
 
     network.train()
 
@@ -240,12 +257,26 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
         scalars_of = lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"])
         log_line = lambda sc: f"Loss: {sc['loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}"
         save = lambda path, net, opt, codes, step: checkpoint.save_baseline_checkpoint(path, net, opt, step)
+    if refiner is not None:
+        # the frame's correction on the step's ray batch (the tuples begin with batch_rays and end with the frame index), and
+        # the deltas beside everything else in the checkpoint
+        plain_step = step_fn
+        step_fn = lambda data, step: plain_step((refiner(int(data[-1]), data[0]), *data[1:]), step)
+        if with_codes:
+            save = lambda path, net, opt, codes, step: checkpoint.save_checkpoint(path, net, opt, codes, step,
+                                                                                  pose_deltas=refiner.deltas)
+        else:
+            save = lambda path, net, opt, codes, step: checkpoint.save_baseline_checkpoint(path, net, opt, step,
+                                                                                           pose_deltas=refiner.deltas)
     global_step = _run_epochs(
         args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step,
         batch=lambda it, step: (dataset_train.batch(it, draw_index(step, rank, world)) if loader == "resident"
                                 else _as_loader_item(dataset_train[it], with_codes)),
         step_fn=step_fn, scalars_of=scalars_of, log_line=log_line, validate=validate, checkpoint_name=checkpoint_name, save=save)
-    return dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
+    out = dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
+    if refiner is not None:
+        out["pose_refiner"] = refiner
+    return out
 
 
 def _run_epochs(args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step, *, batch, step_fn,

@@ -452,6 +452,29 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
                        float* d_latent, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * idealnerf_pass_bwd that also returns the gradient of the pass's ray records (joint camera-pose refinement): the
+ * arguments of idealnerf_pass_bwd plus d_rays [n_rays, IDN_RAY_FLOATS], OVERWRITTEN, in the layout of the record --
+ * columns 0:3 d rays_o, 3:6 d rays_d, 8:11 d viewdirs, columns 6 and 7 (near, far) are written as 0.  It runs the same
+ * backward (every other output is bit for bit idealnerf_pass_bwd's), then the input-row gradient of the pass's points
+ * (into the workspace: the size idealnerf_pass_bwd_workspace_bytes names is enough) and its reduction per ray:
+ *   encoding backward (helper.py:174-224, audio_exp_nerf.py:331,380): d pts[a] = dx[a] + sum_k 2^k (cos(2^k p_a) dx_sin[k, a]
+ *     - sin(2^k p_a) dx_cos[k, a]) over the 10 bands, the same over 4 bands for the view direction; points recomputed from
+ *     rays and z as the forward does;  d rays_o = sum_s d pts_s, d rays_d = sum_s z_s d pts_s, d viewdirs = sum_s d dir_s;
+ *   raw2outputs' dists = dz * |rays_d| (baseline.py:341-343): d rays_d += (sum_{s < S-1} dL/d dist_s dz_s) rays_d / |rays_d|
+ *     (the last sample's 1e10 spacing saturates alpha and is left out).
+ * Depths carry no gradient (coarse depths depend on near / far alone; fine depths are detached upstream, :345); the
+ * background, the expression and near / far get none here.  Fixed summation order, no float atomics: a ray's gradient is a
+ * function of the inputs alone, wherever the ray stands in the batch.  d_rays == NULL: exactly idealnerf_pass_bwd.
+ * Argument errors return IDN_EINVAL, a short workspace IDN_EWORKSPACE, before any HIP call.  The frozen plan
+ * (idealnerf_pass_bwd_cond) has no such variant.  Additive entry: the ABI version is unchanged.
+ */
+int idealnerf_pass_bwd_rays(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
+                            const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
+                            const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
+                            const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
+                            float* d_latent, float* d_rays, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * idealnerf_pass_bwd for a FROZEN network (the head pair of the torso stage, train_torso.py:476-479): none of its parameters
  * takes a gradient, but the conditioning it was given does.  The arguments of idealnerf_pass_bwd without `grads`, the same
  * workspace size; d_aud / d_latent are ACCUMULATED (+=) exactly as idealnerf_pass_bwd documents, and nothing else is written.

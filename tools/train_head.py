@@ -4,10 +4,13 @@
 
     python tools/train_head.py --config <file> [upstream's flags] [--loader resident|reference] [--steps N] [--sample-seed S]
     python tools/train_head.py --model agg --config <feat_agg.txt> ...      # the feature-aggregation model: train_agg.train
+    python tools/train_head.py --config <file> --refine_poses [--pose_lrate R]   # refine the training cameras with the model
+    python tools/train_head.py --config <file> --generate 300 --pose_noise 1.0,0.01 --refine_poses   # on noised generated cameras
     python tools/train_head.py --timing-json profiles/train_loop.json [--generate 300] [--steps 60]
     python tools/train_head.py --model agg --timing-json profiles/agg_train_loop.json --generate 300
     python tools/train_head.py --model baseline --config <adnerf_baseline.txt> ...   # the AD-NeRF baseline: train_baseline.train
     python tools/train_head.py --model baseline --timing-json profiles/baseline_train_loop.json --generate 300
+    python tools/train_head.py --refine_poses --timing-json profiles/pose_refine.json --generate 300   # the option's cost per step
 
 ``--model agg`` trains ``agg_aud_exp_nerf.Network`` (NeRFs/HeadNeRF/train/agg_aud_exp_nerf.py) with its own loaders, flags
 (the head stage's plus ``use_highlight``) and ``{epoch:06d}_head.tar`` checkpoints.  Its ``--timing-json`` measures what the
@@ -59,7 +62,13 @@ def parse(argv):
     p.add_argument("--steps", type=int, default=None, help="stop after this many steps (timing: steps per window, default 60)")
     p.add_argument("--sample-seed", type=int, default=0)
     p.add_argument("--timing-json", type=str, default=None)
-    p.add_argument("--generate", type=int, default=0, help="frames of the generated 450 x 450 directory (timing)")
+    p.add_argument("--generate", type=int, default=0, help="frames of the generated 450 x 450 directory (timing, or a training run on a directory that does not exist yet)")
+    p.add_argument("--refine_poses", action="store_true",
+                   help="refine the training cameras jointly with the model (pose_refine.PoseRefiner); head.tar gains pose_deltas")
+    p.add_argument("--pose_lrate", type=float, default=None, help="Adam rate of the pose deltas (default 0.1 * lrate, untuned)")
+    p.add_argument("--pose_noise", type=str, default=None, metavar="DEG,LEN",
+                   help="with --generate: seeded noise of this size (degrees, scene units) on the generated TRAINING cameras; "
+                        "the clean poses are kept as transforms_exp_train_clean.json")
     return p.parse_args(argv)
 
 
@@ -283,6 +292,74 @@ def baseline_timing(args):
     }}
 
 
+def pose_timing(args):
+    """What --refine_poses costs per step: the head model's bare train_step on prepared batches, without and with the frame's
+    pose correction (pose_refine.PoseRefiner, its deltas a parameter group of the same Adam), the two arms alternating window
+    by window in one process from equal initial weights, each window warmed and ended by one synchronise."""
+    import torch
+    from idealnerf_amd import dataset, synthetic, train as T_
+    from idealnerf_amd.agg_aud_exp_nerf import build_head_network, init_weights
+    from idealnerf_amd.pose_refine import PoseRefiner
+    if not torch.cuda.is_available():
+        raise SystemExit("--timing-json measures on a GPU; none is visible")
+    dev = torch.device("cuda", 0)
+    if args.generate and not os.path.isdir(args.datadir):
+        os.makedirs(args.datadir)
+        synthetic.write_clip_directory(args.datadir, SIZE, args.generate, seed=0)
+    steps = args.steps or 60
+    frames = dataset.ResidentFrames(args.datadir, args.aud_file, "train", args, device=dev, seed=args.sample_seed)
+    n = len(frames)
+    pose_lrate = 0.1 * args.lrate if args.pose_lrate is None else args.pose_lrate
+    arms = {}
+    for arm in ("plain", "refine"):
+        torch.manual_seed(0)
+        net = build_head_network(args, frames.H, frames.W, frames.focal, "head").to(dev)
+        lat = torch.ones(n, 32, dtype=torch.float32, device=dev)
+        net.apply(init_weights)
+        lat.requires_grad = True
+        net.train()
+        opt = T_.make_optimizer(net, lat, args.lrate)
+        refiner = None
+        if arm == "refine":
+            refiner = PoseRefiner(n).to(dev)
+            opt.add_param_group({"params": [refiner.deltas], "lr": pose_lrate, "lr_scale": pose_lrate / args.lrate})
+        arms[arm] = (net, opt, lat, refiner)
+    prepared = []
+    for i in range(16):                          # one set of batches for both arms
+        b = frames.batch(i % n, i)
+        prepared.append(tuple(t.clone() for t in b[:3]) + b[3:])
+    step = {k: 0 for k in arms}
+
+    def window(arm, count):
+        net, opt, lat, refiner = arms[arm]
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(count):
+            data = prepared[step[arm] % len(prepared)]
+            if refiner is not None:
+                data = (refiner(int(data[-1]), data[0]), *data[1:])
+            T_.train_step(net, opt, data, lat, step[arm], n, lrate=args.lrate, lrate_decay=args.lrate_decay)
+            step[arm] += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / count * 1e3
+
+    per_round = {k: [] for k in arms}
+    for _ in range(ROUNDS):
+        for arm in arms:                         # the same order in every round: plain, refine
+            window(arm, WARMUP)
+            per_round[arm].append(window(arm, steps))
+    med = lambda v: float(statistics.median(v))
+    return {"step_cost": {
+        "device": torch.cuda.get_device_name(0), "size": [frames.H, frames.W], "frames": n, "N_rand": args.N_rand,
+        "mouth_rays": args.mouth_rays, "N_samples": args.N_samples, "N_importance": args.N_importance, "perturb": args.perturb,
+        "steps_per_window": steps, "warmup_steps": WARMUP, "rounds": ROUNDS, "pose_lrate": pose_lrate,
+        "step_ms_plain": per_round["plain"], "step_ms_refine": per_round["refine"],
+        "step_ms_plain_median": med(per_round["plain"]), "step_ms_refine_median": med(per_round["refine"]),
+        "refine_minus_plain_ms": med(per_round["refine"]) - med(per_round["plain"]),
+        "refine_over_plain": med(per_round["refine"]) / med(per_round["plain"]),
+    }}
+
+
 def main(argv=None):
     args = parse(argv)
     if args.timing_json is not None:
@@ -292,7 +369,9 @@ def main(argv=None):
             args.N_rand, args.dim_aud, args.dim_expr = 2048, 64, 76
         elif args.generate:                      # the reference's size and split on the generated directory
             args.N_rand, args.mouth_rays, args.dim_aud, args.dim_expr = 3072, 256, 64, 76
-        out = {"agg": agg_timing, "baseline": baseline_timing}.get(args.model, timing)(args)
+        if args.refine_poses and args.model != "head":
+            raise SystemExit("--timing-json --refine_poses measures the head model")
+        out = pose_timing(args) if args.refine_poses else {"agg": agg_timing, "baseline": baseline_timing}.get(args.model, timing)(args)
         if args.timing_json not in ("", "-"):
             old = json.load(open(args.timing_json)) if os.path.exists(args.timing_json) else {}
             old.update(out)
@@ -302,17 +381,37 @@ def main(argv=None):
         return out
     import torch
     from idealnerf_amd import train as T_
+    clean = None
+    if args.generate and not os.path.isdir(args.datadir):
+        from idealnerf_amd import synthetic
+        os.makedirs(args.datadir)
+        synthetic.write_clip_directory(args.datadir, SIZE, args.generate, seed=0, dim_expr=79 if args.model == "agg" else 76)
+        if args.pose_noise:
+            deg, length = (float(v) for v in args.pose_noise.split(","))
+            clean = synthetic.perturb_train_poses(args.datadir, deg, length, seed=0)
+    elif args.pose_noise:
+        raise SystemExit("--pose_noise perturbs a directory --generate writes; this one exists or --generate is missing")
     t0 = time.perf_counter()
+    pose = dict(refine_poses=args.refine_poses, pose_lrate=args.pose_lrate)
     if args.model == "agg":
         from idealnerf_amd import train_agg
-        run = train_agg.train(args, loader=args.loader, sample_seed=args.sample_seed, steps=args.steps)
+        run = train_agg.train(args, loader=args.loader, sample_seed=args.sample_seed, steps=args.steps, **pose)
     elif args.model == "baseline":
         from idealnerf_amd import train_baseline
-        run = train_baseline.train(args, loader=args.loader, sample_seed=args.sample_seed, steps=args.steps)
+        run = train_baseline.train(args, loader=args.loader, sample_seed=args.sample_seed, steps=args.steps, **pose)
     else:
-        run = T_.train(args, loader=args.loader, sample_seed=args.sample_seed, steps=args.steps)
+        run = T_.train(args, loader=args.loader, sample_seed=args.sample_seed, steps=args.steps, **pose)
     torch.cuda.synchronize()
     out = {"model": args.model, "loader": args.loader, "global_step": run["global_step"], "frames": run["data_size"], "seconds": time.perf_counter() - t0}
+    if clean is not None:   # camera error against the clean poses, before and after (degrees, scene units; mean over the frames)
+        from idealnerf_amd.pose_refine import pose_errors, refined_c2w
+        noisy, truth = clean
+        before = pose_errors(noisy, truth)
+        out["pose_error_before"] = [float(before[0].mean()), float(before[1].mean())]
+        if "pose_refiner" in run:
+            deltas = run["pose_refiner"].deltas.detach().double().cpu()
+            after = pose_errors(torch.stack([refined_c2w(dl, m) for dl, m in zip(deltas, noisy)]), truth)
+            out["pose_error_after"] = [float(after[0].mean()), float(after[1].mean())]
     print(json.dumps(out))
     return out
 
