@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("IDN_LIB") or os.path.join(HERE, "libidealnerf.so")
 
 IDN_PREC_F32, IDN_PREC_BF16X3, IDN_PREC_BF16, IDN_PREC_FP16X3, IDN_PREC_BF16X6 = 0, 1, 2, 3, 4
 RAY_FLOATS = 11
+MAX_MULTIRES, MAX_MULTIRES_VIEWS = 10, 4   # IDN_MAX_MULTIRES / IDN_MAX_MULTIRES_VIEWS: the compiled 64- / 32-column input tiles
 SAMPLE_MAX_REGION = 4096   # IDN_SAMPLE_MAX_REGION
 SCORE_TILE = 32            # IDN_SCORE_TILE
 PROF_KINDS = ("mlp_fwd", "mlp_fwd_save", "delta_chain", "dw_gemm", "dw_gemm_x6", "mlp_fwd_save_x6", "delta_chain_x6")   # IDN_PROF_* of include/idealnerf.h
@@ -23,7 +24,9 @@ fp = C.c_void_p  # device pointers travel as integers
 class FaceNerfParams(C.Structure):
     _fields_ = [("pts_w", fp * 8), ("pts_b", fp * 8), ("views_w", fp * 3), ("views_b", fp * 3),
                 ("alpha_w", fp), ("alpha_b", fp), ("rgb_w", fp), ("rgb_b", fp),
-                ("dim_aud", C.c_int), ("dim_expr", C.c_int), ("dim_latent", C.c_int)]
+                ("dim_aud", C.c_int), ("dim_expr", C.c_int), ("dim_latent", C.c_int),
+                # the encoding widths as multires + 1 / multires_views + 1; 0 (a zero-initialised struct) = the default 10 / 4
+                ("multires_plus1", C.c_int), ("multires_views_plus1", C.c_int)]
 
 
 class FaceNerfGrads(C.Structure):
@@ -95,6 +98,9 @@ PROTOTYPES = {
     "idealnerf_pack_weights": (C.c_int, [C.POINTER(FaceNerfParams), C.c_int, fp, fp]),
     "idealnerf_fold_conditioning": (C.c_int, [C.POINTER(FaceNerfParams), fp, fp, fp, fp, fp]),
     "idealnerf_facenerf_fwd": (C.c_int, [fp, fp, C.c_int, fp, C.c_int64, fp, fp]),
+    "idealnerf_facenerf_fwd_ch": (C.c_int, [fp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int64, fp, fp]),
+    "idealnerf_params_pts_ch": (C.c_int, [C.POINTER(FaceNerfParams)]),
+    "idealnerf_params_views_ch": (C.c_int, [C.POINTER(FaceNerfParams)]),
     "idealnerf_query_rays_fwd": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int64, C.c_int, fp, fp]),
     "idealnerf_query_points_fwd": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int64, C.c_int, fp, fp]),
     "idealnerf_frame_rays": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
@@ -138,6 +144,7 @@ PROTOTYPES = {
     "idealnerf_pass_bwd_cond": (C.c_int, [C.POINTER(FaceNerfParams), fp, fp, fp, fp, fp, fp, fp, fp, C.c_int64, C.c_int, fp, fp, fp,
                                           fp, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_facenerf_train_fwd": (C.c_int, [fp, fp, C.c_int, fp, C.c_int64, fp, fp, fp]),
+    "idealnerf_facenerf_train_fwd_ch": (C.c_int, [fp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int64, fp, fp, fp]),
     "idealnerf_facenerf_bwd_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "idealnerf_facenerf_bwd": (C.c_int, [C.POINTER(FaceNerfParams), C.POINTER(FaceNerfGrads), fp, fp, fp, fp, C.c_int64, fp,
                                          fp, fp, fp, fp, fp, C.c_size_t, fp]),

@@ -15,6 +15,7 @@ Training: ``render_rays`` under autograd hands each network's fused feature ``g 
 entry and raises under autograd.
 """
 from .audio_exp_nerf import Network as HeadNetwork, init_weights  # noqa: F401  (init_weights: the trainer applies it)
+from .helper import input_channels
 from .models.face_nerf_agg import FaceNeRFAgg
 
 DIM_EXPR, DIM_AGG, DIM_LATENT = 79, 64, 32   # agg_aud_exp_nerf.py:190-199
@@ -32,8 +33,9 @@ class Network(HeadNetwork):
 
     def make_nerf(self):
         args = self.args
-        return FaceNeRFAgg(D=args.netdepth, W=args.netwidth, input_ch=63, dim_aud=args.dim_aud, dim_latent=DIM_LATENT,
-                           dim_expr=DIM_EXPR, dim_agg=DIM_AGG, output_ch=4, skips=self.skips, input_ch_views=27,
+        input_ch, input_ch_views = input_channels(args)   # agg_aud_exp_nerf.py:33-34
+        return FaceNeRFAgg(D=args.netdepth, W=args.netwidth, input_ch=input_ch, dim_aud=args.dim_aud, dim_latent=DIM_LATENT,
+                           dim_expr=DIM_EXPR, dim_agg=DIM_AGG, output_ch=4, skips=self.skips, input_ch_views=input_ch_views,
                            use_viewdirs=args.use_viewdirs)
 
     def audio_feature(self, auds, index, global_step, dataset_size):

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .helper import RenderConfig, linspace01
+from .helper import RenderConfig, input_channels, linspace01
 from .models.audio_net import AudioAttNet, AudioNet, DeepSpeechAudNet
 from .models.face_nerf import FaceNeRF
 
@@ -63,9 +63,10 @@ class Network(nn.Module):
     def make_nerf(self):
         """One network of the coarse / fine pair."""
         args = self.args
-        return FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=63, dim_aud=args.dim_aud, output_ch=4,
+        input_ch, input_ch_views = input_channels(args)   # get_embedder(args.multires / multires_views, args.i_embed), :35-36
+        return FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=input_ch, dim_aud=args.dim_aud, output_ch=4,
                         skips=self.skips, dim_latent=args.dim_latent, dim_expr=args.dim_expr,
-                        input_ch_views=27, use_viewdirs=args.use_viewdirs)
+                        input_ch_views=input_ch_views, use_viewdirs=args.use_viewdirs)
 
     def audio_feature(self, auds, index, global_step, dataset_size):
         """audio_exp_nerf.py:236-262: the frame's audio feature from the clip's DeepSpeech windows."""

@@ -238,7 +238,8 @@ class FaceNeRFFn(torch.autograd.Function):
         f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
         aud_d, expr_d, lat_d = f32(aud), f32(expr), f32(latent)
         folded = module.folded_bias(aud_d, expr_d, lat_d)
-        out, acts = ops.facenerf_train_fwd(module.packed_weights(prec_name), folded, f32(x), code)
+        out, acts = ops.facenerf_train_fwd(module.packed_weights(prec_name), folded, f32(x), code, module.input_xyz_ch,
+                                           module.input_views_ch)
         ctx.module, ctx.acts, ctx.cond = module, acts, (aud_d, expr_d, lat_d)
         ctx.like = [None if t is None else (t.dtype, t.shape) for t in (x, aud, expr, latent)]   # gradients come back alike
         return out
@@ -260,7 +261,7 @@ def _facenerf_backward(ctx, g_out):
     n = g_out.shape[0]
     zeros = lambda t, want: torch.zeros(t.shape, dtype=torch.float32, device=dev) if want and t is not None else None
     d_aud, d_expr, d_lat = zeros(aud, need[2]), zeros(expr, need[3]), zeros(lat, need[4])
-    d_x = torch.empty((n, ops.PTS_CH + ops.VIEWS_CH), dtype=torch.float32, device=dev) if need[1] else None
+    d_x = torch.empty((n, module.input_xyz_ch + module.input_views_ch), dtype=torch.float32, device=dev) if need[1] else None
     grads = {k: (torch.empty_like if n else torch.zeros_like)(sd[k]) for k in PARAM_KEYS}
     if n:
         ops.facenerf_bwd(module.kernel_params(), grads, aud, expr, lat, acts, g_out.detach().to(torch.float32).contiguous(),

@@ -148,7 +148,8 @@ def to_render_config(ns, dim_latent: int = 32) -> RenderConfig:
                         nosmo_iters=getattr(ns, "nosmo_iters", 300000),
                         N_samples=ns.N_samples, N_importance=ns.N_importance, perturb=ns.perturb, chunk=ns.chunk,
                         netchunk=ns.netchunk, multires=ns.multires, multires_views=ns.multires_views,
-                        use_viewdirs=ns.use_viewdirs, near=ns.near, far=ns.far, lc_weight=ns.lc_weight)
+                        use_viewdirs=ns.use_viewdirs, near=ns.near, far=ns.far, lc_weight=ns.lc_weight,
+                        i_embed=getattr(ns, "i_embed", 0))
 
 
 # ---- the process's flags: what the reference keeps in its import-time `args` global ------------------------------

@@ -28,18 +28,19 @@ static int check_precision_train(int precision) {
 
 int launch_mlp(int precision, const float* packed, const float* folded, const float* x, const float* rays,
                const float* z, const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw,
-               hipStream_t s, int gate, int64_t* gate_counters) {
+               hipStream_t s, int gate, int64_t* gate_counters, int pts_ch, int views_ch) {
     if (n_points > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "n_points %lld exceeds 2^31-1 per launch", (long long)n_points);
     if ((rays || pts) && n_samples < 1) return fail(IDN_EINVAL, "n_samples < 1");
     if (precision == IDN_PREC_BF16X3)
-        return launch_mlp_bf16x3(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s);
+        return launch_mlp_bf16x3(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, pts_ch, views_ch);
     if (precision == IDN_PREC_BF16)
-        return launch_mlp_bf16(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s);
+        return launch_mlp_bf16(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, pts_ch, views_ch);
     if (precision == IDN_PREC_FP16X3)
-        return launch_mlp_fp16x3(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s);
+        return launch_mlp_fp16x3(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, pts_ch, views_ch);
     if (precision == IDN_PREC_BF16X6)
-        return launch_mlp_bf16x6(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s);
-    return launch_mlp_f32(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, nullptr, 0, gate, gate_counters);
+        return launch_mlp_bf16x6(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, nullptr, 0, pts_ch, views_ch);
+    return launch_mlp_f32(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, nullptr, 0, gate, gate_counters, pts_ch,
+                          views_ch);
 }
 
 static int check_params(const idn_facenerf_params* p) {
@@ -50,6 +51,22 @@ static int check_params(const idn_facenerf_params* p) {
         if (!p->views_w[i] || !p->views_b[i]) return fail(IDN_EINVAL, "views_linears.%d is NULL", i);
     if (!p->alpha_w || !p->alpha_b || !p->rgb_w || !p->rgb_b) return fail(IDN_EINVAL, "alpha/rgb head is NULL");
     if (p->dim_aud < 0 || p->dim_expr < 0 || p->dim_latent < 0) return fail(IDN_EINVAL, "negative conditioning width");
+    // the encoding widths, stored as the value + 1 (0: the default 10 / 4)
+    if (p->multires_plus1 < 0 || p->multires_plus1 > IDN_MAX_MULTIRES + 1)
+        return fail(IDN_EINVAL, "multires_plus1 = %d: multires must be in 0..%d (0 in the field = the default %d)", p->multires_plus1,
+                    IDN_MAX_MULTIRES, IDN_MAX_MULTIRES);
+    if (p->multires_views_plus1 < 0 || p->multires_views_plus1 > IDN_MAX_MULTIRES_VIEWS + 1)
+        return fail(IDN_EINVAL, "multires_views_plus1 = %d: multires_views must be in 0..%d (0 in the field = the default %d)",
+                    p->multires_views_plus1, IDN_MAX_MULTIRES_VIEWS, IDN_MAX_MULTIRES_VIEWS);
+    return IDN_OK;
+}
+// the row widths the x-mode entries are given: 3 + 6 L, L in 0..10 / 0..4
+static int check_widths(int pts_ch, int views_ch) {
+    if (pts_ch < 3 || pts_ch > IDN_PTS_CH || pts_ch % 6 != 3)
+        return fail(IDN_EINVAL, "pts_ch %d is not 3 + 6 multires with multires in 0..%d (3..%d)", pts_ch, IDN_MAX_MULTIRES, IDN_PTS_CH);
+    if (views_ch < 3 || views_ch > IDN_VIEWS_CH || views_ch % 6 != 3)
+        return fail(IDN_EINVAL, "views_ch %d is not 3 + 6 multires_views with multires_views in 0..%d (3..%d)", views_ch,
+                    IDN_MAX_MULTIRES_VIEWS, IDN_VIEWS_CH);
     return IDN_OK;
 }
 
@@ -120,13 +137,26 @@ int idealnerf_fold_conditioning(const idn_facenerf_params* p, const float* aud, 
     return launch_fold(*p, aud, expr, latent, folded, (hipStream_t)stream);
 }
 
-int idealnerf_facenerf_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
-                           float* out, void* stream) {
+int idealnerf_params_pts_ch(const idn_facenerf_params* p) {
+    return p && p->multires_plus1 >= 0 && p->multires_plus1 <= IDN_MAX_MULTIRES + 1 ? pts_ch_of(*p) : -1;
+}
+int idealnerf_params_views_ch(const idn_facenerf_params* p) {
+    return p && p->multires_views_plus1 >= 0 && p->multires_views_plus1 <= IDN_MAX_MULTIRES_VIEWS + 1 ? views_ch_of(*p) : -1;
+}
+
+int idealnerf_facenerf_fwd_ch(const float* packed, const float* folded, int precision, const float* x, int pts_ch, int views_ch,
+                              int64_t n, float* out, void* stream) {
     if (int e = check_precision(precision)) return e;
+    if (int e = check_widths(pts_ch, views_ch)) return e;
     if (n < 0) return fail(IDN_EINVAL, "n < 0");
     if (n == 0) return IDN_OK;
     if (!packed || !folded || !x || !out) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_mlp(precision, packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream);
+    return launch_mlp(precision, packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, 0, nullptr,
+                      pts_ch, views_ch);
+}
+int idealnerf_facenerf_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
+                           float* out, void* stream) {
+    return idealnerf_facenerf_fwd_ch(packed, folded, precision, x, IDN_PTS_CH, IDN_VIEWS_CH, n, out, stream);
 }
 
 int idealnerf_query_rays_fwd(const float* packed, const float* folded, int precision, const float* rays,
@@ -401,15 +431,22 @@ int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, cons
 
 int idealnerf_facenerf_train_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
                                  float* out, float* acts, void* stream) {
+    return idealnerf_facenerf_train_fwd_ch(packed, folded, precision, x, IDN_PTS_CH, IDN_VIEWS_CH, n, out, acts, stream);
+}
+int idealnerf_facenerf_train_fwd_ch(const float* packed, const float* folded, int precision, const float* x, int pts_ch,
+                                    int views_ch, int64_t n, float* out, float* acts, void* stream) {
     if (int e = check_precision_train(precision)) return e;
+    if (int e = check_widths(pts_ch, views_ch)) return e;
     if (n < 0) return fail(IDN_EINVAL, "n < 0");
     if (n == 0) return IDN_OK;
     if (!packed || !folded || !x || !out || !acts) return fail(IDN_EINVAL, "NULL pointer");
     if (n > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "n %lld exceeds 2^31-1 per launch", (long long)n);
     const int64_t p_pad = (n + 127) / 128 * 128;
     if (precision == IDN_PREC_BF16X6)
-        return launch_mlp_bf16x6(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad);
-    return launch_mlp_f32(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad);
+        return launch_mlp_bf16x6(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad,
+                                 pts_ch, views_ch);
+    return launch_mlp_f32(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad, 0,
+                          nullptr, pts_ch, views_ch);
 }
 
 size_t idealnerf_facenerf_bwd_workspace_bytes(int64_t n) {

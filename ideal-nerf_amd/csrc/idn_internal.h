@@ -29,6 +29,20 @@ namespace idn {
 // direction PE (27 -> 4 groups).  The conditioning columns are not in the stream; they
 // are folded into the per-frame bias block (idealnerf_fold_conditioning).
 // ---------------------------------------------------------------------------
+// Encoding widths of a network (include/idealnerf.h: the params struct stores multires + 1, 0 = the default): the number
+// of input columns that exist, 3 + 6 multires.  gamma_L is a prefix of gamma_10, the stream's K tiles are padded to 64 / 32
+// columns whatever the width, and the packers zero every column the network does not have.
+__host__ __device__ inline int pts_ch_of(const idn_facenerf_params& p) {
+    return p.multires_plus1 ? 6 * p.multires_plus1 - 3 : IDN_PTS_CH;
+}
+__host__ __device__ inline int views_ch_of(const idn_facenerf_params& p) {
+    return p.multires_views_plus1 ? 6 * p.multires_views_plus1 - 3 : IDN_VIEWS_CH;
+}
+// the two widths as the x-mode entries take them: 3 + 6 L with L in range
+inline bool widths_ok(int pts_ch, int views_ch) {
+    return pts_ch >= 3 && pts_ch <= IDN_PTS_CH && pts_ch % 6 == 3 && views_ch >= 3 && views_ch <= IDN_VIEWS_CH && views_ch % 6 == 3;
+}
+
 constexpr int kFragBytes = 1024;
 constexpr int kFragFloats = 256;
 // Ring geometry.  Measured on the bf16x3 kernel (512^2 frame): 2 x 64 KiB 4.12e8 samples/s,
@@ -193,27 +207,33 @@ int launch_pack_bf16x3(const idn_facenerf_params& p, float* packed, hipStream_t 
 int launch_pack_bf16x6(const idn_facenerf_params& p, float* packed, hipStream_t s);
 int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                       const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                      float* acts = nullptr, int64_t p_pad = 0);   // acts != null: the training forward (saves activations + ReLU masks)
+                      float* acts = nullptr, int64_t p_pad = 0,    // acts != null: the training forward (saves activations + ReLU masks)
+                      int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);   // x != null: the widths of its rows
 int launch_pack_bf16(const idn_facenerf_params& p, float* packed, hipStream_t s);
 int launch_mlp_bf16(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s);
+                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
+                    int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
 int launch_mlp_bf16x3(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s);
+                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
+                      int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
 int launch_mlp_fp16x3(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s);
+                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
+                      int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
 // precision dispatch for the inference forward
 // gate (fp32 rays mode only; ignored by the other arithmetics): the colour-gated kernel; gate_counters: device int64 [2]
 // (tiles, skipped) it adds to, or null
 int launch_mlp(int precision, const float* packed, const float* folded, const float* x, const float* rays,
                const float* z, const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw,
-               hipStream_t s, int gate = 0, int64_t* gate_counters = nullptr);
+               hipStream_t s, int gate = 0, int64_t* gate_counters = nullptr, int pts_ch = IDN_PTS_CH,
+               int views_ch = IDN_VIEWS_CH);   // x != null: the widths of its rows [n_points, pts_ch + views_ch]
 int launch_fold(const idn_facenerf_params& p, const float* aud, const float* expr, const float* latent,
                 float* folded, hipStream_t s);
-// x != nullptr: pre-embedded rows [n_points, 90]; pts != nullptr: raw points [n_points,3] +
+// x != nullptr: pre-embedded rows [n_points, pts_ch + views_ch]; pts != nullptr: raw points [n_points,3] +
 // dirs[n_points/S, 3]; else rays[n_rays,11] + z[n_rays,S]
 int launch_mlp_f32(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                   float* acts = nullptr, int64_t p_pad = 0, int gate = 0, int64_t* gate_counters = nullptr);
+                   float* acts = nullptr, int64_t p_pad = 0, int gate = 0, int64_t* gate_counters = nullptr,
+                   int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
 
 int launch_frame_rays(const float* c2w, int H, int W, float focal, float cx, float cy, float near_, float far_,
                       int row0, int nrows, float* rays_out, hipStream_t s);
@@ -324,11 +344,12 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, 
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
                     const float* g_acc, float* d_aud, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s,
                     float* d_rays = nullptr);   // d_rays [n_rays, 11] != null: also the gradient of the ray records (overwritten)
-// ray_grad.hip: d_x [n_rays * S, 90] (the input-row gradient of the pass's points) -> d_rays [n_rays, 11]; column 6 of d_rays
-// holds dL / d |rays_d| on entry
-int launch_ray_grad(const float* d_x, const float* rays, const float* z, int64_t n_rays, int S, float* d_rays, hipStream_t s);
+// ray_grad.hip: d_x [n_rays * S, pts_ch + views_ch] (the input-row gradient of the pass's points) -> d_rays [n_rays, 11];
+// column 6 of d_rays holds dL / d |rays_d| on entry
+int launch_ray_grad(const float* d_x, int pts_ch, int views_ch, const float* rays, const float* z, int64_t n_rays, int S,
+                    float* d_rays, hipStream_t s);
 // FaceNeRF.forward's backward on pre-embedded rows: head deltas from g_out [n, 4], the same tail as launch_pass_bwd, d expr
-// from the fold and (d_x != null) the input-row gradient d_x [n, 90]
+// from the fold and (d_x != null) the input-row gradient d_x [n, pts_ch + views_ch]
 int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
                         const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
                         float* d_expr, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s);

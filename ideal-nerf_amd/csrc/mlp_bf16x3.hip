@@ -545,9 +545,11 @@ __global__ __launch_bounds__(64 * kPlainWaves, 1) void mlp_bf16_kernel(MlpArgs a
 }
 
 int launch_mlp_bf16(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s) {
+                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
+                    int pts_ch, int views_ch) {
     constexpr int NW = kPlainWaves, PT = kPlainSets;
     if (n_points <= 0) return IDN_OK;
+    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
     static LaunchSetup setup;
     int num_cu = 0;
     if (int e = setup.get([]() -> int {
@@ -562,7 +564,7 @@ int launch_mlp_bf16(const float* packed, const float* folded, const float* x, co
         return e;
     const int64_t ntiles = (n_points + 32 * NW * PT - 1) / (32 * NW * PT);
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, nullptr, 0};
+    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, nullptr, 0, pts_ch, views_ch};
     ProfScope prof(s, n_points);
     if (x)
         hipLaunchKernelGGL((mlp_bf16_kernel<kModeX>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
@@ -577,8 +579,10 @@ int launch_mlp_bf16(const float* packed, const float* folded, const float* x, co
 #endif  // IDN_X3_FP16
 
 int X3_LAUNCH(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s) {
+                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
+                      int pts_ch, int views_ch) {
     if (n_points <= 0) return IDN_OK;
+    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
     static LaunchSetup setup;
     int num_cu = 0;
     if (int e = setup.get([]() -> int {
@@ -593,7 +597,7 @@ int X3_LAUNCH(const float* packed, const float* folded, const float* x, const fl
         return e;
     const int64_t ntiles = (n_points + 127) / 128;
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, nullptr, 0};
+    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, nullptr, 0, pts_ch, views_ch};
     ProfScope prof(s, n_points);
     if (x)
         hipLaunchKernelGGL((X3_KERNEL<kModeX>), dim3(grid), dim3(256), kMlpLds, s, a);

@@ -325,8 +325,9 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x6_kernel(MlpArgs a) {
 
 int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                       const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                      float* acts, int64_t p_pad) {
+                      float* acts, int64_t p_pad, int pts_ch, int views_ch) {
     if (n_points <= 0) return IDN_OK;
+    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
     if (acts && pts) return fail(IDN_EUNSUPPORTED, "the activation-saving forward takes rays or pre-embedded rows");
     static LaunchSetup setup;
     int num_cu = 0;
@@ -348,7 +349,7 @@ int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, 
         return e;
     const int64_t ntiles = (n_points + 127) / 128;
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad};
+    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad, pts_ch, views_ch};
     ProfScope prof(s, n_points, acts ? IDN_PROF_MLP_FWD_SAVE_X6 : IDN_PROF_MLP_FWD);
     if (x && acts)   // FaceNeRF.forward with gradients: the same instruction sequence as the line below plus the slab stores
         hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModeX, true>), dim3(grid), dim3(256), kLdsTrain, s, a);

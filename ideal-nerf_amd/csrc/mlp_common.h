@@ -332,7 +332,7 @@ enum { kModeRays = 0, kModeX = 1, kModePts = 2 };
 struct MlpArgs {
     const float* wstream;
     const float* bias;
-    const float* x;     // kModeX:    [n_points, 90] pre-embedded rows
+    const float* x;     // kModeX:    [n_points, x_pts_ch + x_views_ch] pre-embedded rows
     const float* rays;  // kModeRays: [n_rays, 11]
     const float* z;     // kModeRays: [n_rays, S]
     const float* pts;   // kModePts:  [n_points, 3]
@@ -342,6 +342,7 @@ struct MlpArgs {
     float* raw;         // [n_points, 4]
     float* acts;        // training only: activation slab (act_off() matrices of p_pad rows), else null
     long p_pad;
+    int x_pts_ch, x_views_ch;   // kModeX: the network's encoding widths (3..63, 3..27); the other modes do not read them
 };
 // the colour-gated fp32 rays kernel's arguments (the other kernels' stay as they are)
 struct MlpGateArgs : MlpArgs {
@@ -423,14 +424,16 @@ __device__ __forceinline__ void point_of(const PointIn& in, float (&p)[3], float
 }
 
 // This lane's input features: calls use(fpt, fdir) with two providers, fpt(ic<K0>) / fdir(ic<K0>) =
-// feature K0 + 4h of gamma_10(point) / gamma_4(view direction) (zero beyond 63 / 27).
+// feature K0 + 4h of gamma_10(point) / gamma_4(view direction) (zero beyond 63 / 27; kModeX: beyond the rows' own widths,
+// wave-uniform run-time values).
 template <int MODE, class Use>
 __device__ __forceinline__ void input_features(const MlpArgs& a, long Pc, int h, const PeLane& pln, const PointIn& in,
                                                Use&& use) {
     if constexpr (MODE == kModeX) {
-        const float* xr = a.x + Pc * (IDN_PTS_CH + IDN_VIEWS_CH) + 4 * h;
-        use([&](auto K) { constexpr int k = decltype(K)::value; return (k + 4 * h < IDN_PTS_CH) ? xr[k] : 0.0f; },
-            [&](auto K) { constexpr int k = decltype(K)::value; return (k + 4 * h < IDN_VIEWS_CH) ? xr[IDN_PTS_CH + k] : 0.0f; });
+        const int pc = a.x_pts_ch, vc = a.x_views_ch;
+        const float* xr = a.x + Pc * (pc + vc) + 4 * h;
+        use([&](auto K) { constexpr int k = decltype(K)::value; return (k + 4 * h < pc) ? xr[k] : 0.0f; },
+            [&](auto K) { constexpr int k = decltype(K)::value; return (k + 4 * h < vc) ? xr[pc + k] : 0.0f; });
     } else {
         float p[3], v[3];
         point_of<MODE>(in, p, v);

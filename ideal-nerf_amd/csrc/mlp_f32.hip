@@ -153,19 +153,20 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(std::conditional_t<GATE
         // ---- inputs: this lane's half of the 64 point features and 32 direction features
         float pe[8][4], pd[4][4];
         if constexpr (MODE == kModeX) {
-            const float* xr = a.x + Pc * (IDN_PTS_CH + IDN_VIEWS_CH);
+            const int pc = a.x_pts_ch, vc = a.x_views_ch;   // the rows' widths: wave-uniform
+            const float* xr = a.x + Pc * (pc + vc);
             static_for<8>([&](auto G) {
                 static_for<4>([&](auto J) {
                     constexpr int g = decltype(G)::value, j = decltype(J)::value;
                     const int k = 8 * g + 4 * h + j;
-                    pe[g][j] = (k < IDN_PTS_CH) ? xr[k] : 0.0f;
+                    pe[g][j] = (k < pc) ? xr[k] : 0.0f;
                 });
             });
             static_for<4>([&](auto G) {
                 static_for<4>([&](auto J) {
                     constexpr int g = decltype(G)::value, j = decltype(J)::value;
                     const int k = 8 * g + 4 * h + j;
-                    pd[g][j] = (k < IDN_VIEWS_CH) ? xr[IDN_PTS_CH + k] : 0.0f;
+                    pd[g][j] = (k < vc) ? xr[pc + k] : 0.0f;
                 });
             });
         } else {
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(std::conditional_t<GATE
 
 int launch_mlp_f32(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                   float* acts, int64_t p_pad, int gate, int64_t* gate_counters) {
+                   float* acts, int64_t p_pad, int gate, int64_t* gate_counters, int pts_ch, int views_ch) {
     if (n_points <= 0) return IDN_OK;
     static LaunchSetup setup;
     int num_cu = 0;
@@ -402,7 +403,8 @@ int launch_mlp_f32(const float* packed, const float* folded, const float* x, con
     const int64_t ntiles = (n_points + 127) / 128;
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
     if (gate && (acts || x || pts)) return fail(IDN_EUNSUPPORTED, "the colour gate is built for the rays-mode inference launch");
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad};
+    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
+    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad, pts_ch, views_ch};
     ProfScope prof(s, n_points, acts ? IDN_PROF_MLP_FWD_SAVE : IDN_PROF_MLP_FWD);
     if (acts) {
         if (pts) return fail(IDN_EUNSUPPORTED, "activation saving is built for the rays+z and the pre-embedded-row input modes");

@@ -58,10 +58,10 @@ static void fill_bwd_desc(const idn_facenerf_params& p, BwdPackDesc& d) {
     d.st[0] = {p.rgb_w, nullptr, IDN_W / 2, 0, 3, IDN_W / 2, -1};
     d.st[1] = {p.views_w[2], nullptr, IDN_W / 2, 0, IDN_W / 2, IDN_W / 2, -1};
     d.st[2] = {p.views_w[1], nullptr, IDN_W / 2, 0, IDN_W / 2, IDN_W / 2, -1};
-    d.st[3] = {p.views_w[0], p.alpha_w, IDN_W + IDN_VIEWS_CH + p.dim_expr, 0, IDN_W / 2, IDN_W, kSigmaChannel};
+    d.st[3] = {p.views_w[0], p.alpha_w, IDN_W + views_ch_of(p) + p.dim_expr, 0, IDN_W / 2, IDN_W, kSigmaChannel};
     for (int l = 7; l >= 1; --l) {
         BwdPackStage& S = d.st[4 + (7 - l)];
-        S = {p.pts_w[l], nullptr, l == 5 ? IDN_PTS_CH + C + IDN_W : IDN_W, l == 5 ? IDN_PTS_CH + C : 0, IDN_W, IDN_W, -1};
+        S = {p.pts_w[l], nullptr, l == 5 ? pts_ch_of(p) + C + IDN_W : IDN_W, l == 5 ? pts_ch_of(p) + C : 0, IDN_W, IDN_W, -1};
     }
 }
 

@@ -202,6 +202,9 @@ int launch_pack_f32(const idn_facenerf_params& p, float* packed, hipStream_t s) 
 
 static void fill_pack_desc(const idn_facenerf_params& p, PackDesc& d) {
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
+    // the network's own encoding widths: the columns from there up to 63 / 27 do not exist in its tensors and are packed as
+    // zeros (kvalid), so the features the ray / point kernels still evaluate for them multiply exact zeros
+    const int PC = pts_ch_of(p), VC = views_ch_of(p);
     for (int l = 0; l < kNumLayers; ++l) {
         PackLayer& L = d.L[l];
         L.w_extra = nullptr;
@@ -212,16 +215,16 @@ static void fill_pack_desc(const idn_facenerf_params& p, PackDesc& d) {
         L.kg0 = L.kg;
         L.col0[0] = L.col0[1] = 0;
         L.kvalid[0] = L.kvalid[1] = 0;
-        if (l == 0) {  // [PE(63) | cond(C)] -> 256 ; cond folded
-            L.w = p.pts_w[0]; L.ld = IDN_PTS_CH + C; L.rows = IDN_W; L.kvalid[0] = IDN_PTS_CH;
-        } else if (l == 5) {  // [PE(63) | cond(C) | h(256)] -> 256
-            L.w = p.pts_w[5]; L.ld = IDN_PTS_CH + C + IDN_W; L.rows = IDN_W; L.kg0 = 8;
-            L.kvalid[0] = IDN_PTS_CH; L.col0[1] = IDN_PTS_CH + C; L.kvalid[1] = IDN_W;
+        if (l == 0) {  // [PE(PC) | cond(C)] -> 256 ; cond folded
+            L.w = p.pts_w[0]; L.ld = PC + C; L.rows = IDN_W; L.kvalid[0] = PC;
+        } else if (l == 5) {  // [PE(PC) | cond(C) | h(256)] -> 256
+            L.w = p.pts_w[5]; L.ld = PC + C + IDN_W; L.rows = IDN_W; L.kg0 = 8;
+            L.kvalid[0] = PC; L.col0[1] = PC + C; L.kvalid[1] = IDN_W;
         } else if (l < 8) {
             L.w = p.pts_w[l]; L.ld = IDN_W; L.rows = IDN_W; L.kvalid[0] = IDN_W;
-        } else if (l == 8) {  // [h(256) | dirPE(27) | expr] -> 128, plus alpha_linear as channel 128
-            L.w = p.views_w[0]; L.ld = IDN_W + IDN_VIEWS_CH + p.dim_expr; L.rows = IDN_W / 2; L.kg0 = 32;
-            L.kvalid[0] = IDN_W; L.col0[1] = IDN_W; L.kvalid[1] = IDN_VIEWS_CH;
+        } else if (l == 8) {  // [h(256) | dirPE(VC) | expr] -> 128, plus alpha_linear as channel 128
+            L.w = p.views_w[0]; L.ld = IDN_W + VC + p.dim_expr; L.rows = IDN_W / 2; L.kg0 = 32;
+            L.kvalid[0] = IDN_W; L.col0[1] = IDN_W; L.kvalid[1] = VC;
             L.w_extra = p.alpha_w; L.extra_at = kSigmaChannel;
         } else if (l < 11) {
             L.w = p.views_w[l - 8]; L.ld = IDN_W / 2; L.rows = IDN_W / 2; L.kvalid[0] = IDN_W / 2;
@@ -238,7 +241,7 @@ struct FoldDesc {
     const float* latent;
 };
 
-// cond[c] of the reference's `initial[:, 63:]` (face_nerf.py:45-55): aud | expr*1/3 | latent
+// cond[c] of the reference's `initial[:, 63:]` (face_nerf.py:45-55; 63 = the point encoding's width): aud | expr*1/3 | latent
 __device__ __forceinline__ float cond_at(const FoldDesc& d, int c) {
     if (c < d.p.dim_aud) return d.aud[c];
     c -= d.p.dim_aud;
@@ -266,20 +269,21 @@ __global__ __launch_bounds__(256) void fold_kernel(FoldDesc d, float* out) {
         else { l = 11; n = r - 416; }
     }
     const int C = d.p.dim_aud + d.p.dim_expr + d.p.dim_latent;
+    const int PC = pts_ch_of(d.p), VC = views_ch_of(d.p);   // the conditioning columns stand behind the network's encoding columns
     float b = 0.f, dot = 0.f;
     if (l < 8) {
         b = d.p.pts_b[l][n];
         if (l == 0 || l == 5) {
-            const int ld = IDN_PTS_CH + C + (l == 5 ? IDN_W : 0);
-            const float* row = d.p.pts_w[l] + (long)n * ld + IDN_PTS_CH;
+            const int ld = PC + C + (l == 5 ? IDN_W : 0);
+            const float* row = d.p.pts_w[l] + (long)n * ld + PC;
             for (int c = lane; c < C; c += 64) dot = fmaf(row[c], cond_at(d, c), dot);
         }
     } else if (l == 8) {
         if (n < IDN_W / 2) {
             b = d.p.views_b[0][n];
             if (d.expr) {
-                const int ld = IDN_W + IDN_VIEWS_CH + d.p.dim_expr;
-                const float* row = d.p.views_w[0] + (long)n * ld + IDN_W + IDN_VIEWS_CH;
+                const int ld = IDN_W + VC + d.p.dim_expr;
+                const float* row = d.p.views_w[0] + (long)n * ld + IDN_W + VC;
                 for (int e = lane; e < d.p.dim_expr; e += 64) dot = fmaf(row[e], d.expr[e] * 1.0f / 3.0f, dot);
             }
         } else if (n == kSigmaChannel) {

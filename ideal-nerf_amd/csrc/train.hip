@@ -170,6 +170,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
 //   dW0[:, 63+c] = db0'[n] cond[c];  dW5[:, 63+c] = db5'[n] cond[c];  dWv0[:, 283+e] = dbv'[n] expr3[e]
 //   d cond[c] = sum_n W0[n][63+c] db0'[n] + W5[n][63+c] db5'[n]   -> d aud, d latent (accumulated)
 //   d expr[e] = (d cond[dim_aud+e] + sum_n Wv0[n][283+e] dbv'[n]) / 3   (expr * 1 / 3 enters all three layers, face_nerf.py:49)
+// (63 and 283 at the default widths: the network's pts_ch and 256 + views_ch, idn_internal.h)
 // ---------------------------------------------------------------------------
 struct FoldBwdArgs {
     idn_facenerf_params p;
@@ -191,17 +192,18 @@ __device__ __forceinline__ float cond_val(const FoldBwdArgs& d, int c) {
 template <bool kCondOnly>
 __global__ void fold_bwd_kernel(FoldBwdArgs d) {
     const int C = d.p.dim_aud + d.p.dim_expr + d.p.dim_latent;
-    const int ld0 = IDN_PTS_CH + C, ld5 = IDN_PTS_CH + C + IDN_W, ldv = IDN_W + IDN_VIEWS_CH + d.p.dim_expr;
+    const int PC = pts_ch_of(d.p), VC = views_ch_of(d.p);
+    const int ld0 = PC + C, ld5 = PC + C + IDN_W, ldv = IDN_W + VC + d.p.dim_expr;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x + (kCondOnly ? IDN_W * C + (IDN_W / 2) * d.p.dim_expr : 0);
     const int n_outer = IDN_W * C;
     if (!kCondOnly && idx < n_outer) {
         const int n = idx / C, c = idx % C;
         const float cv = cond_val(d, c);
-        d.gW0[(long)n * ld0 + IDN_PTS_CH + c] = d.db0[n] * cv;
-        d.gW5[(long)n * ld5 + IDN_PTS_CH + c] = d.db5[n] * cv;
+        d.gW0[(long)n * ld0 + PC + c] = d.db0[n] * cv;
+        d.gW5[(long)n * ld5 + PC + c] = d.db5[n] * cv;
     } else if (!kCondOnly && idx < n_outer + (IDN_W / 2) * d.p.dim_expr) {
         const int k = idx - n_outer, n = k / d.p.dim_expr, e = k % d.p.dim_expr;
-        d.gWv0[(long)n * ldv + IDN_W + IDN_VIEWS_CH + e] = d.dbv[n] * (d.expr[e] * 1.0f / 3.0f);
+        d.gWv0[(long)n * ldv + IDN_W + VC + e] = d.dbv[n] * (d.expr[e] * 1.0f / 3.0f);
     } else {
         // d cond[c]: one wavefront per conditioning column, the lanes split the 256 rows (a thread per column
         // walked them as one chain of dependent strided loads: 65 us)
@@ -210,8 +212,8 @@ __global__ void fold_bwd_kernel(FoldBwdArgs d) {
         if (c >= C) return;
         double s = 0.0;
         for (int n = lane; n < IDN_W; n += 64)
-            s += (double)d.p.pts_w[0][(long)n * ld0 + IDN_PTS_CH + c] * (double)d.db0[n] +
-                 (double)d.p.pts_w[5][(long)n * ld5 + IDN_PTS_CH + c] * (double)d.db5[n];
+            s += (double)d.p.pts_w[0][(long)n * ld0 + PC + c] * (double)d.db0[n] +
+                 (double)d.p.pts_w[5][(long)n * ld5 + PC + c] * (double)d.db5[n];
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) s += shfl_xor_dd(s, m);
         // an expr column also feeds views_linears.0 (wave-uniform branch; never taken when d_expr is NULL)
@@ -220,7 +222,7 @@ __global__ void fold_bwd_kernel(FoldBwdArgs d) {
         double sv = 0.0;
         if (want_expr) {
             for (int n = lane; n < IDN_W / 2; n += 64)
-                sv += (double)d.p.views_w[0][(long)n * ldv + IDN_W + IDN_VIEWS_CH + e] * (double)d.dbv[n];
+                sv += (double)d.p.views_w[0][(long)n * ldv + IDN_W + VC + e] * (double)d.dbv[n];
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) sv += shfl_xor_dd(sv, m);
         }
@@ -319,7 +321,10 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
                     const float* latent, const float* acts, int64_t Pp, const BwdWs& w, float* d_aud, float* d_expr,
                     float* d_latent, hipStream_t s) {
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
-    const int ld0 = IDN_PTS_CH + C, ld5 = IDN_PTS_CH + C + IDN_W, ldv = IDN_W + IDN_VIEWS_CH + p.dim_expr;
+    // the network's encoding widths: the leading dimensions of its three mixed-input tensors and the columns the narrow
+    // takes keep of the 64-column products (the slab's x0 / dir matrices are 64 wide whatever the width)
+    const int PC = pts_ch_of(p), VC = views_ch_of(p);
+    const int ld0 = PC + C, ld5 = PC + C + IDN_W, ldv = IDN_W + VC + p.dim_expr;
     auto act = [&](int i) { return acts + (size_t)act_off(i) * Pp; };
     auto a_l = [&](int l) { return act(kActA1 + l - 1); };  // post-ReLU output of pts_linears.(l-1), l = 1..8
     auto v_l = [&](int l) { return act(kActV1 + l - 1); };  // post-ReLU output of views_linears.(l-1), l = 1..3
@@ -386,19 +391,19 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
     TRY(q.take(h, 0, 0, 128, 256, gr.views_w[0], ldv));
     TRY(q.take(h, kSigmaChannel, 0, 1, 256, gr.alpha_w, 256));
     TRY(q.product(w.dV0, 256, 128, act(kActDir), 64, 64, false, &h));
-    TRY(q.take(h, 0, 0, 128, IDN_VIEWS_CH, gr.views_w[0] + IDN_W, ldv));
+    TRY(q.take(h, 0, 0, 128, VC, gr.views_w[0] + IDN_W, ldv));
     for (int l = 7; l >= 1; --l) {   // pts_linears.l; the skip layer's input is [encoding | conditioning | a5]: two products
         TRY(q.product(w.dA[l], 256, 256, a_l(l), 256, 256, true, &h));
         TRY(q.take_colsum(h, 0, 256, gr.pts_b[l]));
-        TRY(q.take(h, 0, 0, 256, 256, l == 5 ? gr.pts_w[5] + IDN_PTS_CH + C : gr.pts_w[l], l == 5 ? ld5 : 256));
+        TRY(q.take(h, 0, 0, 256, 256, l == 5 ? gr.pts_w[5] + PC + C : gr.pts_w[l], l == 5 ? ld5 : 256));
         if (l == 5) {
             TRY(q.product(w.dA[5], 256, 256, act(kActX0), 64, 64, false, &h));
-            TRY(q.take(h, 0, 0, 256, IDN_PTS_CH, gr.pts_w[5], ld5));
+            TRY(q.take(h, 0, 0, 256, PC, gr.pts_w[5], ld5));
         }
     }
     TRY(q.product(w.dA[0], 256, 256, act(kActX0), 64, 64, true, &h));
     TRY(q.take_colsum(h, 0, 256, gr.pts_b[0]));
-    TRY(q.take(h, 0, 0, 256, IDN_PTS_CH, gr.pts_w[0], ld0));
+    TRY(q.take(h, 0, 0, 256, PC, gr.pts_w[0], ld0));
     TRY(q.finish());
 #undef TRY
     {
@@ -413,7 +418,7 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
     return IDN_OK;
 }
 
-// d_x [n, 90] = dL / d (input rows) from the deltas of pts_linears.0 / .5 and views_linears.0 a backward has left in `w`
+// d_x [n, pts_ch + views_ch] = dL / d (input rows) from the deltas of pts_linears.0 / .5 and views_linears.0 a backward has left in `w`
 // (dx_kernel, below)
 static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, int64_t Pp, float* d_x, hipStream_t s);
 
@@ -434,7 +439,7 @@ static void launch_composite_bwd(const CompBwdArgs& a, int64_t n_rays, int S, hi
 
 // d_rays != nullptr (idealnerf_pass_bwd_rays): after the backward, the input-row gradient of the pass's points (into the
 // workspace: the delta matrix of pts_linears.1 is free once the weight gradients are reduced, and p_pad x 256 floats hold
-// n x 90) and its reduction to the ray records (ray_grad.hip).  The compositing backward leaves dL / d |rays_d| in column 6
+// n x (pts_ch + views_ch <= 90)) and its reduction to the ray records (ray_grad.hip).  The compositing backward leaves dL / d |rays_d| in column 6
 // of d_rays, which the reduction reads before it writes that column's zero.
 int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
@@ -466,7 +471,7 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, 
         float* d_x = w.dA[1];
         static_assert(IDN_PTS_CH + IDN_VIEWS_CH <= 256, "the input-row gradient fits a delta matrix");
         if (int e = launch_dx(p, w, P, Pp, d_x, s)) return e;
-        return launch_ray_grad(d_x, rays, z, n_rays, S, d_rays, s);
+        return launch_ray_grad(d_x, pts_ch_of(p), views_ch_of(p), rays, z, n_rays, S, d_rays, s);
     }
     return IDN_OK;
 }
@@ -492,6 +497,8 @@ __global__ __launch_bounds__(256) void head_seed_kernel(const float* g_out, long
 // Gradient with respect to the input rows x [n, 90] (rays never need it: their encoding is not a leaf):
 //   d_x[:, 0:63]  = dA0 . W0[:, 0:63] + dA5 . W5[:, 0:63]     (pts_linears.0 and the skip layer, K = 512)
 //   d_x[:, 63:90] = dV0[:, 0:128] . Wv0[:, 256:283]           (views_linears.0's direction columns, K = 128)
+// (at the default widths; a narrower network has pts_ch / views_ch columns in place of 63 / 27 -- block-uniform run-time
+// values: the fragments of the columns it does not have are zero, and the stores stop at its widths and use its row pitch)
 // Row-major "NN" products, contraction over the layers' OUTPUT channels, on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32,
 // fp32 operands, fp32 accumulate).  One wave = 32 points: C[col][point] = W^T (A operand, from LDS) x delta^T (B operand,
 // straight from the delta rows: lane (point j, half hh) loads the float4 of channels 8 g + 4 hh .. + 3 of its row and feeds
@@ -512,7 +519,8 @@ struct DxArgs {
     const float* wv; int ldv;    // views_linears.0.weight
     const float* dA0; const float* dA5; const float* dV0;   // [p_pad, 256] deltas
     long n, p_pad;
-    float* d_x;                  // [n, 90]
+    float* d_x;                  // [n, pts_ch + views_ch]
+    int pts_ch, views_ch;        // the network's encoding widths (3..63, 3..27)
 };
 __global__ __launch_bounds__(64 * kDxWaves, 1) void dx_kernel(DxArgs a) {
     extern __shared__ __attribute__((aligned(16))) f32x4 dx_frag[];   // [kDxFrags][64 lanes]
@@ -526,10 +534,10 @@ __global__ __launch_bounds__(64 * kDxWaves, 1) void dx_kernel(DxArgs a) {
             if (f < 128) {
                 const int g = f >> 1, col = 32 * (f & 1) + i, k = 8 * g + 4 * h + t;
                 const float* row = k < IDN_W ? a.w0 + (long)k * a.ld0 : a.w5 + (long)(k - IDN_W) * a.ld5;
-                v[t] = col < IDN_PTS_CH ? row[col] : 0.f;
+                v[t] = col < a.pts_ch ? row[col] : 0.f;
             } else {
                 const int k = 8 * (f - 128) + 4 * h + t;
-                v[t] = i < IDN_VIEWS_CH ? a.wv[(long)k * a.ldv + IDN_W + i] : 0.f;
+                v[t] = i < a.views_ch ? a.wv[(long)k * a.ldv + IDN_W + i] : 0.f;
             }
         }
         dx_frag[e] = f32x4{v[0], v[1], v[2], v[3]};
@@ -572,13 +580,13 @@ __global__ __launch_bounds__(64 * kDxWaves, 1) void dx_kernel(DxArgs a) {
         }
         // lane (j, hh), register r: column d_row(r, hh) of point p (+ 32 for the second pts tile, + 63 for the direction block)
         if (p < a.n) {
-            float* o = a.d_x + p * (IDN_PTS_CH + IDN_VIEWS_CH);
+            float* o = a.d_x + p * (a.pts_ch + a.views_ch);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int col = d_row(r, hh);
-                o[col] = acc0[r];
-                if (col < IDN_PTS_CH - 32) o[32 + col] = acc1[r];
-                if (col < IDN_VIEWS_CH) o[IDN_PTS_CH + col] = accv[r];
+                if (col < a.pts_ch) o[col] = acc0[r];   // (a network of fewer than 32 point columns ends inside the first tile)
+                if (col < a.pts_ch - 32) o[32 + col] = acc1[r];
+                if (col < a.views_ch) o[a.pts_ch + col] = accv[r];
             }
         }
     }
@@ -593,8 +601,9 @@ static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, in
         }, &num_cu))
         return e;
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
-    const DxArgs da{p.pts_w[0], IDN_PTS_CH + C, p.pts_w[5], IDN_PTS_CH + C + IDN_W, p.views_w[0], IDN_W + IDN_VIEWS_CH + p.dim_expr,
-                    w.dA[0], w.dA[5], w.dV0, (long)n, (long)Pp, d_x};
+    const int PC = pts_ch_of(p), VC = views_ch_of(p);
+    const DxArgs da{p.pts_w[0], PC + C, p.pts_w[5], PC + C + IDN_W, p.views_w[0], IDN_W + VC + p.dim_expr,
+                    w.dA[0], w.dA[5], w.dV0, (long)n, (long)Pp, d_x, PC, VC};
     const int64_t groups = (Pp / 32 + kDxWaves - 1) / kDxWaves;
     const int grid = (int)(groups < num_cu ? groups : num_cu);
     hipLaunchKernelGGL(dx_kernel, dim3(grid), dim3(64 * kDxWaves), kDxLds, s, da);

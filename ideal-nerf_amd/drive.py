@@ -16,6 +16,7 @@ import torch
 
 from . import checkpoint, clip, dataset
 from .config import to_render_config
+from .helper import input_channels
 from .models.face_nerf import set_render_precision
 
 
@@ -71,15 +72,15 @@ def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", st
     return None if res is None else dict(res, path=out)
 
 
-def head_expr_width(run_dir):
+def head_expr_width(run_dir, input_ch_views=27):
     """The expression width of the head pair that the torso stage's checkpoints in ``run_dir`` hold: the input width of
-    ``face_nerf_coarse.views_linears.0`` (27 view columns + 256 features + the expression) in the newest ``*head.tar*``, else in
-    the newest ``*torso.tar*``.  FileNotFoundError without either."""
+    ``face_nerf_coarse.views_linears.0`` (``input_ch_views`` view columns -- 27 at ``multires_views = 4`` -- + 256 features +
+    the expression) in the newest ``*head.tar*``, else in the newest ``*torso.tar*``.  FileNotFoundError without either."""
     path = checkpoint.latest_checkpoint(run_dir, contains="head.tar") or checkpoint.latest_checkpoint(run_dir, contains="torso.tar")
     if path is None:
         raise FileNotFoundError(f"no *head.tar* and no *torso.tar* in {run_dir}")
     state = torch.load(path, map_location="cpu", weights_only=False)["model_state_dict"]
-    return int(state["face_nerf_coarse.views_linears.0.weight"].shape[1]) - 27 - 256
+    return int(state["face_nerf_coarse.views_linears.0.weight"].shape[1]) - input_ch_views - 256
 
 
 def drive_torso(args, *, out=None, device="cuda", codec="MJPG", still_every=10, seed=None, group=None, precision=None):
@@ -97,7 +98,7 @@ def drive_torso(args, *, out=None, device="cuda", codec="MJPG", still_every=10, 
     poses, auds, bc_img, (H, W, focal, _, _), aud_ids, torso_pose = dataset.load_test_data(
         args.datadir, args.aud_file, args.test_pose_file, args.testskip, args.test_size, args.aud_start)
     run_dir = os.path.join(args.basedir, args.expname)
-    dim_expr_head = head_expr_width(run_dir)
+    dim_expr_head = head_expr_width(run_dir, input_channels(args)[1])
     track = None
     if dim_expr_head > 0:
         expr_path = args.test_pose_file if _unset(args.evalExpr_path) else args.evalExpr_path

@@ -13,6 +13,7 @@ inherited, and training goes through ``autograd.RenderRaysFn`` unchanged (no lat
 import torch
 
 from .audio_exp_nerf import Network as HeadNetwork, init_weights  # noqa: F401  (init_weights: the trainer applies it)
+from .helper import input_channels
 from .models.face_nerf import FaceNeRF
 
 
@@ -28,8 +29,9 @@ class Network(HeadNetwork):
 
     def make_nerf(self):
         args = self.args
-        return FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=63, dim_aud=args.dim_aud, dim_latent=0, dim_expr=0,
-                        output_ch=4, skips=self.skips, input_ch_views=27, use_viewdirs=args.use_viewdirs)
+        input_ch, input_ch_views = input_channels(args)   # head_baseline.py:37-38
+        return FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=input_ch, dim_aud=args.dim_aud, dim_latent=0, dim_expr=0,
+                        output_ch=4, skips=self.skips, input_ch_views=input_ch_views, use_viewdirs=args.use_viewdirs)
 
     def audio_feature(self, auds, index, global_step, dataset_size):
         if global_step >= self.args.nosmo_iters:

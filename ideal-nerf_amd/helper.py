@@ -42,6 +42,7 @@ class RenderConfig:
     near: float = 0.3
     far: float = 0.9
     lc_weight: float = 0.0005
+    i_embed: int = 0              # -1: the identity embedder (helper.py:207-209), 3 + 3 input channels
 
 
 def config_parser():
@@ -118,8 +119,9 @@ def linspace01(n: int, device) -> torch.Tensor:
 
 def get_embedder(multires, i=0, input_dims=3):
     """helper.py:207-224.  The per-point encodings are fused into the MLP kernel; this
-    standalone embedder only serves per-frame vectors (torso pose signal,
-    train_torso.py:238-240) and is plain tensor math on whatever device x lives on."""
+    standalone embedder serves per-frame vectors (torso pose signal,
+    train_torso.py:238-240), gives the Network classes their FaceNeRFs' input widths
+    (``input_channels``) and is plain tensor math on whatever device x lives on."""
     if i == -1:
         return torch.nn.Identity(), input_dims
     out_dim = input_dims * (1 + 2 * multires)
@@ -132,6 +134,17 @@ def get_embedder(multires, i=0, input_dims=3):
         return torch.cat(feats, -1)
 
     return embed, out_dim
+
+
+def input_channels(args):
+    """(input_ch, input_ch_views) of the FaceNeRFs a Network builds from its flags, as every trainer and tester upstream
+    takes them: ``get_embedder(args.multires, args.i_embed)`` and ``get_embedder(args.multires_views, args.i_embed)``
+    (audio_exp_nerf.py:35-36).  ``i_embed = -1`` is the identity embedder: 3 / 3, the network of 0 / 0 octaves.  More
+    octaves than the kernels' input tiles hold (10 / 4) raise NotImplementedError naming the flag."""
+    i_embed = getattr(args, "i_embed", 0)
+    if i_embed != -1:   # (the identity embedder does not read the octave counts)
+        ops.embed_channels(args.multires), ops.embed_channels(args.multires_views, views=True)
+    return get_embedder(args.multires, i_embed)[1], get_embedder(args.multires_views, i_embed)[1]
 
 
 def get_rays(H, W, focal, c2w, cx=None, cy=None, near=0.0, far=1.0, row0=0, nrows=None, device="cuda"):

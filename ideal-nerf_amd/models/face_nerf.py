@@ -72,10 +72,12 @@ class FaceNeRF(nn.Module):
         self.input_xyz_ch, self.input_views_ch = input_ch, input_ch_views
         self.dim_aud, self.dim_expr, self.dim_latent = dim_aud, dim_expr, dim_latent
         self.skips, self.use_viewdirs = skips, use_viewdirs
-        if (D, W, list(skips), input_ch, input_ch_views, bool(use_viewdirs)) != (8, 256, [4], 63, 27, True):
+        if (D, W, list(skips), bool(use_viewdirs)) != (8, 256, [4], True):
             raise NotImplementedError(
                 "libidealnerf is compiled for the reference's fixed architecture D=8, W=256, skips=[4], "
-                "input_ch=63, input_ch_views=27, use_viewdirs=True (audio_exp_nerf.py:213-224)")
+                "use_viewdirs=True (audio_exp_nerf.py:213-224)")
+        # the encoding widths are the network's own: 3 + 6 multires in 3..63, 3 + 6 multires_views in 3..27 (helper.get_embedder)
+        ops.check_input_channels(input_ch, input_ch_views)
         c_all = input_ch + dim_aud + dim_expr + dim_latent
         self.pts_linears = nn.ModuleList(
             [nn.Linear(c_all, W)] + [nn.Linear(W, W) if i not in skips else nn.Linear(W + c_all, W) for i in range(D - 1)])
@@ -116,7 +118,8 @@ class FaceNeRF(nn.Module):
 
     def kernel_params(self):
         sd = {k: v for k, v in self.named_parameters()}
-        return ops.params_struct(sd, self.dim_aud, self.dim_expr, self.dim_latent)
+        return ops.params_struct(sd, self.dim_aud, self.dim_expr, self.dim_latent, pts_ch=self.input_xyz_ch,
+                                 views_ch=self.input_views_ch)
 
     # -- what autograd.RenderRaysFn asks of a model class (FaceNeRFAgg answers the same questions with its fused feature)
     def kernel_tensors(self):
@@ -174,4 +177,4 @@ class FaceNeRF(nn.Module):
         with torch.no_grad():
             folded = self.folded_bias(aud, expr, latent_code)
             return ops.facenerf_fwd(self.packed_weights(), folded, x.detach().to(torch.float32).contiguous(),
-                                    self.prec_code)
+                                    self.prec_code, self.input_xyz_ch, self.input_views_ch)

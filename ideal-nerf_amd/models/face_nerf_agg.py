@@ -25,9 +25,9 @@ class FaceNeRFAgg(nn.Module):
         super().__init__()
         if skips is None:
             skips = [4]
-        if (D, W, list(skips), input_ch, input_ch_views, bool(use_viewdirs)) != (8, 256, [4], 63, 27, True):
-            raise NotImplementedError("libidealnerf is compiled for D=8, W=256, skips=[4], input_ch=63, "
-                                      "input_ch_views=27, use_viewdirs=True")
+        if (D, W, list(skips), bool(use_viewdirs)) != (8, 256, [4], True):
+            raise NotImplementedError("libidealnerf is compiled for D=8, W=256, skips=[4], use_viewdirs=True")
+        ops.check_input_channels(input_ch, input_ch_views)   # 3 + 6 multires in 3..63, 3 + 6 multires_views in 3..27
         self.D, self.W, self.skips, self.use_viewdirs = D, W, skips, use_viewdirs
         self.input_xyz_ch, self.input_views_ch = input_ch, input_ch_views
         self.dim_latent, self.dim_agg, self.dim_aud, self.dim_expr = dim_latent, dim_agg, dim_aud, dim_expr
@@ -105,7 +105,8 @@ class FaceNeRFAgg(nn.Module):
         sd["views_linears.0.weight"] = self._views0[1]
         if views0_bias is not None:
             sd["views_linears.0.bias"] = views0_bias
-        return ops.params_struct(sd, self.dim_agg, 0, self.dim_latent), sd
+        return ops.params_struct(sd, self.dim_agg, 0, self.dim_latent, pts_ch=self.input_xyz_ch,
+                                 views_ch=self.input_views_ch), sd
 
     def packed_weights(self, precision: str = None) -> torch.Tensor:
         precision = precision or self.precision
@@ -144,4 +145,5 @@ class FaceNeRFAgg(nn.Module):
             raise NotImplementedError("FaceNeRFAgg runs on the HIP path for inference only; wrap the call in torch.no_grad()")
         with torch.no_grad():
             return ops.facenerf_fwd(self.packed_weights(), self.folded_bias(aud, expr, latent_code),
-                                    x.detach().to(torch.float32).contiguous(), self.prec_code)
+                                    x.detach().to(torch.float32).contiguous(), self.prec_code, self.input_xyz_ch,
+                                    self.input_views_ch)

@@ -16,7 +16,33 @@ import torch
 from . import _lib
 from ._lib import IDN_PREC_F32, RAY_FLOATS, IdealNerfError, check
 
-PTS_CH, VIEWS_CH, W_HID = 63, 27, 256
+PTS_CH, VIEWS_CH, W_HID = 63, 27, 256   # the widest encodings (multires 10 / multires_views 4): the defaults
+
+
+def embed_channels(multires: int, views: bool = False) -> int:
+    """Input channels of an encoding of `multires` octaves: 3 + 6 multires, helper.get_embedder's out_dim.  Raises
+    NotImplementedError naming the flag outside 0..10 (points) / 0..4 (view directions), the compiled input tiles."""
+    limit = _lib.MAX_MULTIRES_VIEWS if views else _lib.MAX_MULTIRES
+    name = "multires_views" if views else "multires"
+    if not 0 <= int(multires) <= limit:
+        raise NotImplementedError(f"{name}={multires}: libidealnerf is compiled for {name} in 0..{limit} "
+                                  f"({3 + 6 * limit} input channels at the most)")
+    return 3 + 6 * int(multires)
+
+
+def check_input_channels(input_ch: int, input_ch_views: int):
+    """The widths a FaceNeRF / FaceNeRFAgg may have: 3 + 6 L with L in 0..10 (points) and 0..4 (view directions)."""
+    for ch, name, flag, limit in ((input_ch, "input_ch", "multires", _lib.MAX_MULTIRES),
+                                  (input_ch_views, "input_ch_views", "multires_views", _lib.MAX_MULTIRES_VIEWS)):
+        if ch != int(ch) or ch < 3 or (ch - 3) % 6 or (ch - 3) // 6 > limit:
+            raise NotImplementedError(f"{name}={ch}: libidealnerf is compiled for {name} = 3 + 6 {flag} with {flag} in "
+                                      f"0..{limit} (at most {3 + 6 * limit})")
+
+
+def widths(p):
+    """(pts_ch, views_ch) of an idn_facenerf_params struct; 63 / 27 for one that leaves the two fields zero."""
+    m, v = p.multires_plus1, p.multires_views_plus1
+    return (6 * m - 3 if m else PTS_CH), (6 * v - 3 if v else VIEWS_CH)
 
 
 def _ptr(t: Optional[torch.Tensor], name="tensor", dtype=torch.float32):
@@ -85,23 +111,26 @@ def _net_buffers(lib, packed, folded, precision, which=""):
         _shape(folded, f"folded{which}", lib.idealnerf_folded_bias_floats())
 
 
-def params_struct(sd: Dict[str, torch.Tensor], dim_aud: int, dim_expr: int, dim_latent: int, prefix: str = ""):
-    """state_dict-keyed tensors (models/face_nerf.py:27-37 names) -> idn_facenerf_params."""
+def params_struct(sd: Dict[str, torch.Tensor], dim_aud: int, dim_expr: int, dim_latent: int, prefix: str = "",
+                  pts_ch: int = PTS_CH, views_ch: int = VIEWS_CH):
+    """state_dict-keyed tensors (models/face_nerf.py:27-37 names) -> idn_facenerf_params.  pts_ch / views_ch: the
+    network's input widths (FaceNeRF's input_ch / input_ch_views), 3 + 6 multires each."""
+    check_input_channels(pts_ch, views_ch)
     p = _lib.FaceNerfParams()
-    C_all = PTS_CH + dim_aud + dim_expr + dim_latent
+    C_all = pts_ch + dim_aud + dim_expr + dim_latent
 
     def get(key, shape):
         t = sd[prefix + key]
         if tuple(t.shape) != shape:
-            raise IdealNerfError(f"{key}: shape {tuple(t.shape)} != {shape} "
-                                 "(only D=8, W=256, skips=[4], multires=10/4 is compiled)")
+            raise IdealNerfError(f"{key}: shape {tuple(t.shape)} != {shape} (D=8, W=256, skips=[4] with "
+                                 f"{pts_ch} point and {views_ch} direction channels)")
         return _ptr(t, key)
 
     for i in range(8):
         fan_in = C_all if i == 0 else (W_HID + C_all if i == 5 else W_HID)
         p.pts_w[i] = get(f"pts_linears.{i}.weight", (W_HID, fan_in))
         p.pts_b[i] = get(f"pts_linears.{i}.bias", (W_HID,))
-    p.views_w[0] = get("views_linears.0.weight", (W_HID // 2, W_HID + VIEWS_CH + dim_expr))
+    p.views_w[0] = get("views_linears.0.weight", (W_HID // 2, W_HID + views_ch + dim_expr))
     p.views_b[0] = get("views_linears.0.bias", (W_HID // 2,))
     for i in (1, 2):
         p.views_w[i] = get(f"views_linears.{i}.weight", (W_HID // 2, W_HID // 2))
@@ -111,6 +140,7 @@ def params_struct(sd: Dict[str, torch.Tensor], dim_aud: int, dim_expr: int, dim_
     p.rgb_w = get("rgb_linear.weight", (3, W_HID // 2))
     p.rgb_b = get("rgb_linear.bias", (3,))
     p.dim_aud, p.dim_expr, p.dim_latent = dim_aud, dim_expr, dim_latent
+    p.multires_plus1, p.multires_views_plus1 = (pts_ch - 3) // 6 + 1, (views_ch - 3) // 6 + 1
     return p
 
 
@@ -137,22 +167,26 @@ def fold_conditioning(p, aud, expr, latent, device) -> torch.Tensor:
     return out
 
 
-def facenerf_fwd(packed, folded, x, precision=IDN_PREC_F32) -> torch.Tensor:
+def facenerf_fwd(packed, folded, x, precision=IDN_PREC_F32, pts_ch=PTS_CH, views_ch=VIEWS_CH) -> torch.Tensor:
+    """x [n, pts_ch + views_ch] -> [n, 4]; `packed` must be the stream of a network of those widths."""
     lib = _lib.load()
-    _shape(x, "x", None, PTS_CH + VIEWS_CH)
+    check_input_channels(pts_ch, views_ch)
+    _shape(x, "x", None, pts_ch + views_ch)
     _net_buffers(lib, packed, folded, precision)
     with _Launch(packed, folded, x) as L:
         out = torch.empty((x.shape[0], 4), dtype=torch.float32, device=x.device)
-        check(lib.idealnerf_facenerf_fwd(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(x, "x"),
-                                         x.shape[0], out.data_ptr(), L.stream))
+        check(lib.idealnerf_facenerf_fwd_ch(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(x, "x"),
+                                            pts_ch, views_ch, x.shape[0], out.data_ptr(), L.stream))
     return out
 
 
-def facenerf_train_fwd(packed, folded, x, precision=_lib.IDN_PREC_BF16X6):
-    """FaceNeRF.forward that also records the backward's activation slab (idealnerf_facenerf_train_fwd): x [n, 90] ->
-    (out [n, 4], acts [idealnerf_train_acts_floats(n)]).  precision: IDN_PREC_F32 or IDN_PREC_BF16X6 only."""
+def facenerf_train_fwd(packed, folded, x, precision=_lib.IDN_PREC_BF16X6, pts_ch=PTS_CH, views_ch=VIEWS_CH):
+    """FaceNeRF.forward that also records the backward's activation slab (idealnerf_facenerf_train_fwd_ch):
+    x [n, pts_ch + views_ch] -> (out [n, 4], acts [idealnerf_train_acts_floats(n)]).  precision: IDN_PREC_F32 or
+    IDN_PREC_BF16X6 only."""
     lib = _lib.load()
-    _shape(x, "x", None, PTS_CH + VIEWS_CH)
+    check_input_channels(pts_ch, views_ch)
+    _shape(x, "x", None, pts_ch + views_ch)
     if precision not in (_lib.IDN_PREC_F32, _lib.IDN_PREC_BF16X6):
         raise IdealNerfError(f"the training forward runs IDN_PREC_F32 or IDN_PREC_BF16X6 only (got {precision})")
     _net_buffers(lib, packed, folded, precision)
@@ -160,8 +194,8 @@ def facenerf_train_fwd(packed, folded, x, precision=_lib.IDN_PREC_BF16X6):
     with _Launch(packed, folded, x) as L:
         out = torch.empty((n, 4), dtype=torch.float32, device=x.device)
         acts = torch.empty(lib.idealnerf_train_acts_floats(n), dtype=torch.float32, device=x.device)
-        check(lib.idealnerf_facenerf_train_fwd(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(x, "x"), n,
-                                               out.data_ptr(), acts.data_ptr(), L.stream))
+        check(lib.idealnerf_facenerf_train_fwd_ch(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(x, "x"),
+                                                  pts_ch, views_ch, n, out.data_ptr(), acts.data_ptr(), L.stream))
     return out, acts
 
 
@@ -181,13 +215,13 @@ def grads_struct(grads: Dict[str, torch.Tensor]):
 
 def facenerf_bwd(p, grads, aud, expr, latent, acts, g_out, d_x=None, d_aud=None, d_expr=None, d_latent=None):
     """Backward of FaceNeRF.forward (idealnerf_facenerf_bwd) from the slab of facenerf_train_fwd.  p: params_struct of the
-    module; grads: state_dict-keyed tensors of the parameters' shapes, OVERWRITTEN; g_out [n, 4] = dL/d out; d_x [n, 90]
-    (overwritten) and d_aud / d_expr / d_latent (accumulated) may each be None."""
+    module; grads: state_dict-keyed tensors of the parameters' shapes, OVERWRITTEN; g_out [n, 4] = dL/d out;
+    d_x [n, pts_ch + views_ch] of the network `p` describes (overwritten) and d_aud / d_expr / d_latent (accumulated) may each be None."""
     lib = _lib.load()
     _shape(g_out, "g_out", None, 4)
     n = g_out.shape[0]
     _shape(acts, "acts", lib.idealnerf_train_acts_floats(n))
-    _shape(d_x, "d_x", n, PTS_CH + VIEWS_CH)
+    _shape(d_x, "d_x", n, sum(widths(p)))
     for t, name, dim in ((aud, "aud", p.dim_aud), (expr, "expr", p.dim_expr), (latent, "latent", p.dim_latent),
                          (d_aud, "d_aud", p.dim_aud), (d_expr, "d_expr", p.dim_expr), (d_latent, "d_latent", p.dim_latent)):
         _shape(t, name, dim)

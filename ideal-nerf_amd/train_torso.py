@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .audio_exp_nerf import Network as HeadNetwork
-from .helper import RenderConfig, get_embedder
+from .helper import RenderConfig, get_embedder, input_channels
 from .models.audio_net import AudioAttNet, AudioNet
 from .models.face_nerf import FaceNeRF
 
@@ -54,10 +54,11 @@ class Network(HeadNetwork):
         self.output_ch, self.skips = 4, [4]
         self.dim_aud_body = dim_aud_body
         self.embed_torso_aud_fn, ch = get_embedder(3, 0)  # 21 per 3-vector (:38)
-        head = lambda: FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=63, dim_aud=args.dim_aud, skips=self.skips,
-                                dim_latent=32, dim_expr=dim_expr_head, input_ch_views=27)
-        torso = lambda: FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=63, dim_aud=dim_aud_body + 2 * ch,
-                                 skips=self.skips, input_ch_views=27)
+        input_ch, input_ch_views = input_channels(args)   # all four networks: train_torso.py:36-37,200-221
+        head = lambda: FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=input_ch, dim_aud=args.dim_aud, skips=self.skips,
+                                dim_latent=32, dim_expr=dim_expr_head, input_ch_views=input_ch_views)
+        torso = lambda: FaceNeRF(D=args.netdepth, W=args.netwidth, input_ch=input_ch, dim_aud=dim_aud_body + 2 * ch,
+                                 skips=self.skips, input_ch_views=input_ch_views)
         self.face_nerf_coarse, self.face_nerf_fine = head(), head()
         self.aud_net = AudioNet(args.dim_aud, args.win_size)
         self.aud_att_net = AudioAttNet()

@@ -19,11 +19,15 @@
  *     (the reference's nn.DataParallel replicas call forward concurrently,
  *     NeRFs/HeadNeRF/test/eval_aud_exp_nerf.py:475).
  *
- * Network architecture is the reference's fixed one: D=8, W=256, skips=[4],
- * multires=10 (63 ch), multires_views=4 (27 ch), use_viewdirs=True
- * (NeRFs/HeadNeRF/train/audio_exp_nerf.py:213-224).  The conditioning widths
- * (dim_aud, dim_expr, dim_latent) are free: they only enter the per-frame folded
- * biases.  Other architectures are rejected with IDN_EUNSUPPORTED.
+ * Network architecture is the reference's: D=8, W=256, skips=[4], use_viewdirs=True
+ * (NeRFs/HeadNeRF/train/audio_exp_nerf.py:213-224).  The encoding widths are a property of
+ * the network: multires in 0..10 (3 + 6 multires point channels, 63 at the default 10) and
+ * multires_views in 0..4 (3 + 6 multires_views direction channels, 27 at the default 4), as
+ * helper.get_embedder gives them (helper.py:174-224; i_embed = -1 is 0 / 0).  gamma_L is a
+ * prefix of gamma_10: a narrower network's weight stream holds zeros in the columns it does
+ * not have, and the ray / point kernels evaluate the full encoding against them.  The
+ * conditioning widths (dim_aud, dim_expr, dim_latent) are free: they only enter the
+ * per-frame folded biases.  Other architectures are rejected with IDN_EUNSUPPORTED.
  */
 #ifndef IDEALNERF_H
 #define IDEALNERF_H
@@ -44,8 +48,10 @@ extern "C" {
 /* Fixed architecture constants (models/face_nerf.py:9-37 at the reference's flags). */
 #define IDN_W 256
 #define IDN_D 8
-#define IDN_PTS_CH 63
-#define IDN_VIEWS_CH 27
+#define IDN_PTS_CH 63   /* the widest point encoding (multires 10): the compiled 64-column input tile */
+#define IDN_VIEWS_CH 27 /* the widest direction encoding (multires_views 4): the compiled 32-column input tile */
+#define IDN_MAX_MULTIRES 10
+#define IDN_MAX_MULTIRES_VIEWS 4
 #define IDN_RAY_FLOATS 11 /* o(3) d(3) near far viewdir(3): audio_exp_nerf.py:412-427 */
 
 /* Arithmetic of the MLP contraction. */
@@ -84,7 +90,17 @@ typedef struct idn_facenerf_params {
     const float* rgb_w;
     const float* rgb_b;
     int dim_aud, dim_expr, dim_latent; /* widths of the per-frame conditioning vectors */
+    /* Encoding widths, stored as the value + 1 so that a zero-initialised struct means the defaults:
+     * 0 = multires 10 / multires_views 4; otherwise multires + 1 in 1..11, multires_views + 1 in 1..5.
+     * pts_linears.0 / .5 then have 3 + 6 multires encoding columns in front of the conditioning columns and
+     * views_linears.0 has 3 + 6 multires_views direction columns behind its 256 trunk columns; every gradient
+     * tensor has its parameter's (narrower) shape.  Anything else returns IDN_EINVAL. */
+    int multires_plus1, multires_views_plus1;
 } idn_facenerf_params;
+
+/* The widths a params struct names (63 / 27 for a zero-initialised one), or -1 for a value out of range. */
+int idealnerf_params_pts_ch(const idn_facenerf_params* p);
+int idealnerf_params_views_ch(const idn_facenerf_params* p);
 
 /*
  * Re-lay the per-point part of the weights into MFMA-fragment order
@@ -100,6 +116,7 @@ int idealnerf_pack_weights(const idn_facenerf_params* p, int precision, float* p
  *   b0' = b0 + W0[:, 63:]  . [aud | expr/3 | latent]        (face_nerf.py:45-55,58)
  *   b5' = b5 + W5[:, 63:63+C] . [aud | expr/3 | latent]     (face_nerf.py:61)
  *   bv' = bv + Wv0[:, 283:] . expr/3                        (face_nerf.py:68-70)
+ * (63 and 283 = 256 + 27 at the default widths; pts_ch and 256 + views_ch of the network otherwise)
  * aud / expr / latent may be NULL exactly when their width is 0 (or, for expr and
  * latent, when the caller passes None as the reference allows).  Run once per frame.
  */
@@ -112,6 +129,12 @@ int idealnerf_fold_conditioning(const idn_facenerf_params* p, const float* aud, 
  */
 int idealnerf_facenerf_fwd(const float* packed, const float* folded, int precision, const float* x,
                            int64_t n, float* out, void* stream);
+/* The same for a network of other encoding widths: x[n, pts_ch + views_ch], pts_ch = 3 + 6 multires (3..63),
+ * views_ch = 3 + 6 multires_views (3..27); `packed` must come from a params struct of those widths.  The entry above
+ * is this one at 63 / 27.  A width outside the range returns IDN_EINVAL before any launch.  Additive entry: the ABI
+ * version is unchanged. */
+int idealnerf_facenerf_fwd_ch(const float* packed, const float* folded, int precision, const float* x, int pts_ch,
+                              int views_ch, int64_t n, float* out, void* stream);
 
 /*
  * Network.run_network with the embedders fused (audio_exp_nerf.py:376-394 +
@@ -458,8 +481,8 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
  * backward (every other output is bit for bit idealnerf_pass_bwd's), then the input-row gradient of the pass's points
  * (into the workspace: the size idealnerf_pass_bwd_workspace_bytes names is enough) and its reduction per ray:
  *   encoding backward (helper.py:174-224, audio_exp_nerf.py:331,380): d pts[a] = dx[a] + sum_k 2^k (cos(2^k p_a) dx_sin[k, a]
- *     - sin(2^k p_a) dx_cos[k, a]) over the 10 bands, the same over 4 bands for the view direction; points recomputed from
- *     rays and z as the forward does;  d rays_o = sum_s d pts_s, d rays_d = sum_s z_s d pts_s, d viewdirs = sum_s d dir_s;
+ *     - sin(2^k p_a) dx_cos[k, a]) over the network's multires bands (10 by default), the same over its multires_views bands
+ *     (4) for the view direction -- with no band, d pts = dx; points recomputed from rays and z as the forward does;  d rays_o = sum_s d pts_s, d rays_d = sum_s z_s d pts_s, d viewdirs = sum_s d dir_s;
  *   raw2outputs' dists = dz * |rays_d| (baseline.py:341-343): d rays_d += (sum_{s < S-1} dL/d dist_s dz_s) rays_d / |rays_d|
  *     (the last sample's 1e10 spacing saturates alpha and is left out).
  * Depths carry no gradient (coarse depths depend on near / far alone; fine depths are detached upstream, :345); the
@@ -502,6 +525,10 @@ int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, cons
  */
 int idealnerf_facenerf_train_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
                                  float* out, float* acts, void* stream);
+/* The same for x[n, pts_ch + views_ch] (widths as idealnerf_facenerf_fwd_ch): the slab's x0 / dir matrices hold
+ * x[:, 0:pts_ch] / x[:, pts_ch:], zero-padded to 64 columns.  The entry above is this one at 63 / 27. */
+int idealnerf_facenerf_train_fwd_ch(const float* packed, const float* folded, int precision, const float* x, int pts_ch,
+                                    int views_ch, int64_t n, float* out, float* acts, void* stream);
 
 /* Workspace of idealnerf_facenerf_bwd for n rows (the size idealnerf_pass_bwd needs for n points). */
 size_t idealnerf_facenerf_bwd_workspace_bytes(int64_t n);
@@ -510,7 +537,7 @@ size_t idealnerf_facenerf_bwd_workspace_bytes(int64_t n);
  * Backward of FaceNeRF.forward (models/face_nerf.py:40-80) for n rows, from the slab idealnerf_facenerf_train_fwd filled.
  *   g_out [n, 4]: dL / d out, in the (rgb_raw, sigma_raw) order of idealnerf_facenerf_fwd.
  *   grads: OVERWRITTEN, every entry including the conditioning columns (as idealnerf_pass_bwd); feature_linear has none.
- *   d_x [n, 90]: OVERWRITTEN with dL / dx; NULL skips its kernel.
+ *   d_x [n, pts_ch + views_ch] (the widths `p` names; [n, 90] at the defaults): OVERWRITTEN with dL / dx; NULL skips its kernel.
  *   d_aud [dim_aud], d_expr [dim_expr], d_latent [dim_latent]: ACCUMULATED (+=); any may be NULL.  expr enters all three
  *   layers as expr * 1 / 3 (face_nerf.py:49): d_expr = (db0 . W0[:, expr] + db5 . W5[:, expr] + dbv0 . Wv0[:, expr]) / 3.
  * n == 0 writes nothing.  Argument errors return IDN_EINVAL before any launch; a short workspace IDN_EWORKSPACE.
