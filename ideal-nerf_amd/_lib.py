@@ -34,6 +34,10 @@ class FaceNerfGrads(C.Structure):
                 ("alpha_w", fp), ("alpha_b", fp), ("rgb_w", fp), ("rgb_b", fp)]
 
 
+class PassBwdExtra(C.Structure):
+    _fields_ = [("d_expr", fp), ("d_rays", fp), ("d_views0_bias", fp)]   # idn_pass_bwd_extra: each may be NULL
+
+
 class CompositeOut(C.Structure):
     _fields_ = [(n, fp) for n in ("rgb_map", "disp_map", "acc_map", "depth_map", "weights", "rgb_fg", "last_weight")]
 
@@ -143,6 +147,8 @@ PROTOTYPES = {
                                           fp, C.c_int64, C.c_int, fp, fp, fp, fp, fp, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_pass_bwd_cond": (C.c_int, [C.POINTER(FaceNerfParams), fp, fp, fp, fp, fp, fp, fp, fp, C.c_int64, C.c_int, fp, fp, fp,
                                           fp, fp, fp, fp, C.c_size_t, fp]),
+    "idealnerf_pass_bwd_ex": (C.c_int, [C.POINTER(FaceNerfParams), C.POINTER(FaceNerfGrads), fp, fp, fp, fp, fp, fp, fp,
+                                        fp, C.c_int64, C.c_int, fp, fp, fp, fp, fp, fp, C.POINTER(PassBwdExtra), fp, C.c_size_t, fp]),
     "idealnerf_facenerf_train_fwd": (C.c_int, [fp, fp, C.c_int, fp, C.c_int64, fp, fp, fp]),
     "idealnerf_facenerf_train_fwd_ch": (C.c_int, [fp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int64, fp, fp, fp]),
     "idealnerf_facenerf_bwd_workspace_bytes": (C.c_size_t, [C.c_int64]),

@@ -6,8 +6,10 @@ activation-saving MLP variant, backward is two C calls (fine pass, coarse pass),
 compositing-backward + 11 layers of MFMA GEMMs + the conditioning fold.  Gradients reach
 every FaceNeRF parameter of both networks, ``aud_para`` (and through it the audio nets,
 which stay ordinary autograd modules), ``latent_code`` and -- only when ``rays`` require one (pose refinement,
-pose_refine.py) -- the ray records: origins, directions and view directions, summed over the two passes.  Sampled depths are detached
-exactly as upstream (:345); ``expr`` is data.  A FaceNeRFAgg pair (agg_aud_exp_nerf.Network) goes through the same function:
+pose_refine.py) -- the ray records: origins, directions and view directions, summed over the two passes.  ``expr`` and ``bc_rgb``
+get theirs on the same condition (cond_refine.py): d expr from the conditioning fold of both passes (``idealnerf_pass_bwd_ex``),
+d bc = g_rgb_map * last_weight of each pass, the exact derivative of the fp32 forward (rgb_map is linear in the background).
+Sampled depths are detached exactly as upstream (:345).  A FaceNeRFAgg pair (agg_aud_exp_nerf.Network) goes through the same function:
 each network's fused feature is its conditioning vector, its columns of ``views_linears.0`` are a bias term
 (``_pass_bwd``), and torch carries the feature's gradient into ``agg_linears`` and the audio nets.
 
@@ -44,7 +46,7 @@ def _train_query(net, folded, rays, z):
 
 
 def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, frozen=False,
-              d_rays=None):
+              d_rays=None, d_expr=None):
     """One pass's backward -> its 24 parameter gradients by PARAM_KEYS.  frozen = (need_aud, need_latent) for a network none of
     whose parameters needs a gradient: the conditioning-only plan -- d_aud / d_latent alone, each only if needed (neither: no
     launch at all), and None for every parameter.
@@ -55,14 +57,20 @@ def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw,
 
     d_rays [n, 11] (pose refinement): OVERWRITTEN with the pass's gradient of the ray records, by the entry that also runs
     the input-row gradient and its per-ray reduction (ops.pass_bwd_rays); None: that entry is never reached.  The frozen
-    plan has no ray gradient."""
+    plan has no ray gradient.
+
+    d_expr [dim_expr] (expression refinement): ACCUMULATED, in either plan, through ops.pass_bwd_ex; None: the calls above,
+    unchanged.  In the frozen plan it counts as a wanted output beside d_aud / d_latent."""
     ext = net.bias_columns()
     if frozen and d_rays is not None:
         raise _lib.IdealNerfError("rays require a gradient but the network is frozen: the conditioning-only backward "
                                   "(idealnerf_pass_bwd_cond) returns no ray gradient")
     if frozen:
         d_aud, d_latent = (d if want else None for d, want in zip((d_aud, d_latent), frozen))
-        if d_aud is not None or d_latent is not None:
+        if d_expr is not None:
+            ops.pass_bwd_ex(net.kernel_params(), None, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud,
+                            d_latent, d_expr=d_expr)
+        elif d_aud is not None or d_latent is not None:
             args = (net.kernel_params(), aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
             if ext is not None and d_aud is not None:
                 b = torch.empty(ext.shape[0], dtype=torch.float32, device=ext.device)
@@ -75,7 +83,9 @@ def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw,
     # (no column stays uninitialised: the fold kernel writes all conditioning columns, the GEMM reductions all others)
     grads = {k: torch.empty_like(sd[k]) for k in PARAM_KEYS}
     args = (net.kernel_params(), grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
-    if d_rays is None:
+    if d_expr is not None:
+        ops.pass_bwd_ex(*args, d_expr=d_expr, d_rays=d_rays)
+    elif d_rays is None:
         ops.pass_bwd(*args)
     else:
         ops.pass_bwd_rays(*args, d_rays)
@@ -120,6 +130,7 @@ class RenderRaysFn(torch.autograd.Function):
         # (need d aud of the coarse pass, of the fine pass -- one and the same where the vector is shared --, need d latent)
         ctx.needs = (need_aud, need_aud if aud_fine is None else aud_fine.requires_grad, latent is not None and latent.requires_grad)
         ctx.shared_aud = aud_fine is None
+        need_bc = ctx.needs_input_grad[6]   # (only then are the two [n] coefficient vectors kept for the backward)
         if ctx.needs_input_grad[5]:   # rays (pose refinement): both passes run the full backward, or none can return d rays
             n_keys = len(PARAM_KEYS)
             trained = [any(t.requires_grad for t in params[i * n_keys:(i + 1) * n_keys]) for i in range(2 if Ni > 0 else 1)]
@@ -128,6 +139,7 @@ class RenderRaysFn(torch.autograd.Function):
                                           "requires one): the conditioning-only backward returns no ray gradient")
         if Ni == 0:
             ctx.saved = (rays, bc, raw_c, z_c, acts_c)
+            ctx.bc_weights = (comp_c["last_weight"],) if need_bc else None
             outs = [comp_c["rgb_map"], comp_c["disp_map"], comp_c["acc_map"]]
             if with_fg:
                 outs.append(comp_c["rgb_fg"])
@@ -138,6 +150,7 @@ class RenderRaysFn(torch.autograd.Function):
         raw_f, acts_f = _train_query(fine, ff, rays, z_f)
         comp_f = ops.composite_fwd(raw_f, z_f, rays, bc, with_fg=with_fg, with_weights=False)
         ctx.saved = (rays, bc, raw_c, z_c, acts_c, raw_f, z_f, acts_f)
+        ctx.bc_weights = (comp_c["last_weight"], comp_f["last_weight"]) if need_bc else None
         outs = [comp_f["rgb_map"], comp_f["disp_map"], comp_f["acc_map"], comp_c["rgb_map"], comp_c["disp_map"],
                 comp_c["acc_map"], smp["z_std"], comp_f["last_weight"]]
         if with_fg:
@@ -167,26 +180,40 @@ class RenderRaysFn(torch.autograd.Function):
         # new is allocated or launched and the step is what it was
         need_rays = ctx.needs_input_grad[5]
         new_d_rays = lambda: torch.empty_like(ctx.saved[0]) if need_rays else None
+        # d expr: one buffer both passes accumulate into, as for the latent code; d bc: no kernel -- rgb_map (rgb0) is linear in the
+        # background with the pass's last_weight as coefficient, and rgb_fg has no background term.  Each only if asked for.
+        d_expr = torch.zeros_like(expr) if ctx.needs_input_grad[7] and expr is not None else None
+        d_bc = None
         if Ni == 0:
             rays, bc, raw_c, z_c, acts_c = ctx.saved
             d_rays = new_d_rays()
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[0]), c(g[3]) if with_fg else None,
-                           None, c(g[2]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat), d_rays=d_rays)
+                           None, c(g[2]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat), d_rays=d_rays, d_expr=d_expr)
             gf = {k: None for k in PARAM_KEYS}
+            if ctx.bc_weights is not None:
+                d_bc = torch.zeros_like(bc) if g[0] is None else g[0] * ctx.bc_weights[0][:, None]
         else:
             rays, bc, raw_c, z_c, acts_c, raw_f, z_f, acts_f = ctx.saved
             d_rays_f, d_rays = new_d_rays(), new_d_rays()
             gf = _pass_bwd(fine, aud_f, expr, lat, acts_f, raw_f, z_f, rays, bc, c(g[0]), c(g[8]) if with_fg else None,
-                           c(g[7]), c(g[2]), d_aud_f, d_lat, frozen=frozen_f and (need_aud_f, need_lat), d_rays=d_rays_f)
+                           c(g[7]), c(g[2]), d_aud_f, d_lat, frozen=frozen_f and (need_aud_f, need_lat), d_rays=d_rays_f,
+                           d_expr=d_expr)
             gc = _pass_bwd(coarse, aud, expr, lat, acts_c, raw_c, z_c, rays, bc, c(g[3]), c(g[9]) if with_fg else None,
                            c(g[10]) if with_fg else None, c(g[5]), d_aud, d_lat, frozen=frozen_c and (need_aud, need_lat),
-                           d_rays=d_rays)
+                           d_rays=d_rays, d_expr=d_expr)
             if need_rays:
                 d_rays += d_rays_f   # coarse + fine, one fp32 addition per element
-        ctx.saved = None
+            if ctx.bc_weights is not None:
+                lw_c, lw_f = ctx.bc_weights
+                d_bc = torch.zeros_like(bc) if g[0] is None else g[0] * lw_f[:, None]
+                if g[3] is not None:
+                    d_bc = d_bc + g[3] * lw_c[:, None]
+        ctx.saved = ctx.bc_weights = None
         param_grads = [gc[k] for k in PARAM_KEYS] + [gf[k] for k in PARAM_KEYS]
         fixed = [None] * RenderRaysFn.N_FIXED
         fixed[5] = d_rays
+        fixed[6] = d_bc
+        fixed[7] = d_expr
         fixed[10] = d_aud if need_aud else None
         fixed[11] = d_aud_f if need_aud_f and not ctx.shared_aud else None
         fixed[12] = d_lat if need_lat else None
@@ -199,7 +226,9 @@ def render_rays_apply(network, coarse, fine, rays, bc_rgb, aud_para, latent_code
     if not rays.requires_grad:   # rays that require a gradient (pose refinement) keep their graph edge
         rays = rays.detach()
     rays = rays.to(torch.float32).contiguous()
-    bc = bc_rgb.detach().to(torch.float32).contiguous()
+    if not bc_rgb.requires_grad:   # a background that requires a gradient (cond_refine.Background) keeps its graph edge
+        bc_rgb = bc_rgb.detach()
+    bc = bc_rgb.to(torch.float32).contiguous()
     n, dev = rays.shape[0], rays.device
     S, Ni = args.N_samples, args.N_importance
     t_rand, u = network.draw_randoms(n, S, Ni, perturb, pytest, dev)
@@ -211,6 +240,8 @@ def render_rays_apply(network, coarse, fine, rays, bc_rgb, aud_para, latent_code
     cond_fine = fine.conditioning(aud_para, expr)[0] if Ni > 0 else None
     if cond_fine is cond:
         cond_fine = None
+    if expr_k is not None and expr_k.requires_grad:   # (its gradient comes back as fp32, the kernels' type)
+        expr_k = expr_k.to(torch.float32)
     outs = RenderRaysFn.apply(coarse, fine, S, Ni, with_fg, rays, bc, expr_k, t_rand, u, cond, cond_fine, latent_code,
                               bool(lindisp), *params)
     ret = {'rgb_map': outs[0], 'disp_map': outs[1], 'acc_map': outs[2]}

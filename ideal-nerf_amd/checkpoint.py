@@ -25,19 +25,24 @@ def latest_checkpoint(run_dir: str, contains: str = ".tar"):
     return os.path.join(run_dir, names[-1]) if names else None
 
 
-def _with_pose_deltas(ckpt: dict, pose_deltas):
-    """The file gains ``pose_deltas`` [n_frames, 6] only for a run that refines its cameras (pose_refine.PoseRefiner)."""
-    if pose_deltas is not None:
-        ckpt["pose_deltas"] = pose_deltas.detach().clone()
+def _with_pose_deltas(ckpt: dict, pose_deltas, expr_deltas=None, background=None):
+    """The file gains ``pose_deltas`` [n_frames, 6] only for a run that refines its cameras (pose_refine.PoseRefiner), and
+    ``expr_deltas`` [n_frames, dim_expr] / ``background`` [H, W, 3] only for one that refines its expressions / learns its
+    background (cond_refine.ExprRefiner / Background)."""
+    for key, value in (("pose_deltas", pose_deltas), ("expr_deltas", expr_deltas), ("background", background)):
+        if value is not None:
+            ckpt[key] = value.detach().clone()
     return ckpt
 
 
-def save_checkpoint(path: str, network, optimizer, latent_codes, global_step: int, pose_deltas=None):
-    """audio_exp_nerf.py:586-591.  pose_deltas (no counterpart upstream): see ``load_pose_deltas``; None: upstream's keys."""
+def save_checkpoint(path: str, network, optimizer, latent_codes, global_step: int, pose_deltas=None, expr_deltas=None,
+                    background=None):
+    """audio_exp_nerf.py:586-591.  pose_deltas / expr_deltas / background (no counterpart upstream): see ``load_pose_deltas``,
+    ``load_expr_deltas``, ``load_background``; all None: upstream's keys."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(_with_pose_deltas({"global_step": global_step, "model_state_dict": network.state_dict(),
                                   "optimizer": optimizer.state_dict() if optimizer is not None else None,
-                                  "latent_codes": latent_codes.data}, pose_deltas), path)
+                                  "latent_codes": latent_codes.data}, pose_deltas, expr_deltas, background), path)
 
 
 def load_pose_deltas(path: str, map_location=None):
@@ -47,6 +52,24 @@ def load_pose_deltas(path: str, map_location=None):
     if "pose_deltas" not in ckpt:
         raise KeyError(f"{path} holds no pose_deltas: it was written by a run without pose refinement")
     return ckpt["pose_deltas"]
+
+
+def _load_key(path, key, map_location, written_by):
+    ckpt = torch.load(path, map_location=map_location, weights_only=False)
+    if key not in ckpt:
+        raise KeyError(f"{path} holds no {key}: it was written by a run without {written_by}")
+    return ckpt[key]
+
+
+def load_expr_deltas(path: str, map_location=None):
+    """-> the ``expr_deltas`` [n_frames, dim_expr] a run with ``refine_expr`` saved.  A file without them raises, as
+    ``load_pose_deltas`` does: resuming from it would silently restart the expressions."""
+    return _load_key(path, "expr_deltas", map_location, "expression refinement")
+
+
+def load_background(path: str, map_location=None):
+    """-> the ``background`` [H, W, 3] (float32, unclamped) a run with ``learn_background`` saved.  A file without it raises."""
+    return _load_key(path, "background", map_location, "a learned background")
 
 
 def load_checkpoint(path: str, network, optimizer=None, map_location=None, strict=True):
@@ -62,14 +85,15 @@ def load_checkpoint(path: str, network, optimizer=None, map_location=None, stric
 DATA_PARALLEL_PREFIX = "module."
 
 
-def save_baseline_checkpoint(path: str, network, optimizer, global_step: int, pose_deltas=None):
+def save_baseline_checkpoint(path: str, network, optimizer, global_step: int, pose_deltas=None, background=None):
     """The AD-NeRF baseline's run file (head_baseline.py:516-520): {'global_step', 'model_state_dict', 'optimizer'}, no latent
     codes.  Upstream wraps the network in ``nn.DataParallel`` on this path (:448), so its keys carry ``module.``: they are
     written that way, and upstream's trainer and tester load the file as their own."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(_with_pose_deltas({"global_step": global_step,
                                   "model_state_dict": {DATA_PARALLEL_PREFIX + k: v for k, v in network.state_dict().items()},
-                                  "optimizer": optimizer.state_dict() if optimizer is not None else None}, pose_deltas), path)
+                                  "optimizer": optimizer.state_dict() if optimizer is not None else None}, pose_deltas,
+                                 None, background), path)
 
 
 def load_baseline_checkpoint(path: str, network, optimizer=None, map_location=None):

@@ -376,22 +376,43 @@ static int check_grads(const idn_facenerf_grads* grads) {
     return IDN_OK;
 }
 
+// The one host function behind the four pass-backward entries.  frozen: no gradient tensors (the conditioning-only plan).
+// Every argument error is answered here or at launch_pass_bwd's workspace check, before any HIP call.
+static int pass_bwd_any(const idn_facenerf_params* p, const idn_facenerf_grads* grads, bool frozen, const float* aud,
+                        const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
+                        const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
+                        const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
+                        float* d_latent, const idn_pass_bwd_extra* extra, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (int e = check_params(p)) return e;
+    if (!frozen)
+        if (int e = check_grads(grads)) return e;
+    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
+        (p->dim_latent > 0) != (latent != nullptr))
+        return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
+    float* d_expr = extra ? extra->d_expr : nullptr;
+    float* d_rays = extra ? extra->d_rays : nullptr;
+    float* d_vb = extra ? extra->d_views0_bias : nullptr;
+    if (d_expr && (p->dim_expr == 0 || !expr)) return fail(IDN_EINVAL, "d_expr for a network without an expression");
+    if (frozen && d_rays) return fail(IDN_EUNSUPPORTED, "the conditioning-only backward (grads NULL) returns no ray gradient");
+    if (!frozen && d_vb) return fail(IDN_EINVAL, "d_views0_bias is the frozen plan's: with grads it is grads->views_b[0]");
+    const bool want_cond = d_aud || d_latent || d_expr;
+    if (frozen && d_vb && !want_cond) return fail(IDN_EINVAL, "d_views0_bias needs d_aud, d_latent or d_expr (with none the pass is not run)");
+    if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
+    if (n_rays == 0 || (frozen && !want_cond)) return IDN_OK;   // nothing to deliver
+    if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_pass_bwd(*p, frozen ? nullptr : grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples,
+                           g_rgb_map, g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
+                           (hipStream_t)stream, d_rays, d_expr, d_vb);
+}
+
 int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
                        const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
                        const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
                        const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
                        float* d_latent, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int e = check_params(p)) return e;
-    if (int e = check_grads(grads)) return e;
-    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
-        (p->dim_latent > 0) != (latent != nullptr))
-        return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
-    if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
-    if (n_rays == 0) return IDN_OK;
-    if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_pass_bwd(*p, grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
-                           g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
-                           (hipStream_t)stream);
+    return pass_bwd_any(p, grads, false, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map, g_rgb_fg,
+                        g_last_weight, g_acc, d_aud, d_latent, nullptr, workspace, workspace_bytes, stream);
 }
 
 int idealnerf_pass_bwd_rays(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
@@ -399,17 +420,9 @@ int idealnerf_pass_bwd_rays(const idn_facenerf_params* p, const idn_facenerf_gra
                             const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
                             const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
                             float* d_latent, float* d_rays, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int e = check_params(p)) return e;
-    if (int e = check_grads(grads)) return e;
-    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
-        (p->dim_latent > 0) != (latent != nullptr))
-        return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
-    if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
-    if (n_rays == 0) return IDN_OK;
-    if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_pass_bwd(*p, grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
-                           g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
-                           (hipStream_t)stream, d_rays);
+    const idn_pass_bwd_extra extra{nullptr, d_rays, nullptr};
+    return pass_bwd_any(p, grads, false, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map, g_rgb_fg,
+                        g_last_weight, g_acc, d_aud, d_latent, &extra, workspace, workspace_bytes, stream);
 }
 
 int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, const float* expr, const float* latent,
@@ -417,16 +430,18 @@ int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, cons
                             int64_t n_rays, int n_samples, const float* g_rgb_map, const float* g_rgb_fg,
                             const float* g_last_weight, const float* g_acc, float* d_aud, float* d_latent, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    if (int e = check_params(p)) return e;
-    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
-        (p->dim_latent > 0) != (latent != nullptr))
-        return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
-    if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
-    if (n_rays == 0 || (!d_aud && !d_latent)) return IDN_OK;   // nothing to deliver
-    if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_pass_bwd(*p, nullptr, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
-                           g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
-                           (hipStream_t)stream);
+    return pass_bwd_any(p, nullptr, true, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map, g_rgb_fg,
+                        g_last_weight, g_acc, d_aud, d_latent, nullptr, workspace, workspace_bytes, stream);
+}
+
+int idealnerf_pass_bwd_ex(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
+                          const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
+                          const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
+                          const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
+                          float* d_latent, const idn_pass_bwd_extra* extra, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    return pass_bwd_any(p, grads, grads == nullptr, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
+                        g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, extra, workspace, workspace_bytes, stream);
 }
 
 int idealnerf_facenerf_train_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,

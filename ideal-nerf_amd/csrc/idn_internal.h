@@ -338,12 +338,15 @@ int launch_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* pro
 
 // train.hip: backward of one render pass
 size_t bwd_workspace_bytes(int64_t n_points);
-// gr == nullptr: the conditioning-only backward of a frozen network (d_aud / d_latent alone; no gradient tensor is written)
+// gr == nullptr: the conditioning-only backward of a frozen network (d_aud / d_latent / d_expr alone; no gradient tensor is
+// written).  d_expr [dim_expr] != null: accumulated, either plan.  d_vb [128] != null (gr == nullptr only): views_linears.0's
+// bias gradient, overwritten.
 int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
                     const float* g_acc, float* d_aud, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s,
-                    float* d_rays = nullptr);   // d_rays [n_rays, 11] != null: also the gradient of the ray records (overwritten)
+                    float* d_rays = nullptr,    // d_rays [n_rays, 11] != null: also the gradient of the ray records (overwritten)
+                    float* d_expr = nullptr, float* d_vb = nullptr);
 // ray_grad.hip: d_x [n_rays * S, pts_ch + views_ch] (the input-row gradient of the pass's points) -> d_rays [n_rays, 11];
 // column 6 of d_rays holds dL / d |rays_d| on entry
 int launch_ray_grad(const float* d_x, int pts_ch, int views_ch, const float* rays, const float* z, int64_t n_rays, int S,

@@ -9,7 +9,8 @@
 //   ray gradient      (idealnerf_pass_bwd_rays) after all of that: dx_kernel into the workspace, then ray_grad.hip; the compositing
 //                     backward's kNorm variant supplies dL / d |rays_d|
 //   frozen network    (no gradient tensors: idealnerf_pass_bwd_cond) instead of the dW products, colsum_rows / colsum_finish on
-//                     dA[0] and dA[5], and the d cond range of fold_bwd alone
+//                     dA[0] and dA[5], and the d cond range of fold_bwd alone; with d expr or views_linears.0's bias gradient
+//                     wanted (idealnerf_pass_bwd_ex) also on the 128 delta columns of dV0, over the pass's real rows
 //
 // Activations come from the training variant of the MLP kernel as row-major matrices
 // (idn_internal.h, "activation slab").  Everything is deterministic: no float atomics.
@@ -178,7 +179,7 @@ struct FoldBwdArgs {
     const float* db0; const float* db5; const float* dbv;  // [256], [256], [128]
     float* gW0; float* gW5; float* gWv0;                    // gradient tensors (full nn.Linear layout)
     float* d_aud; float* d_latent;                          // accumulated (+=), may be null
-    float* d_expr;                                          // accumulated (+=), may be null (idealnerf_pass_bwd: expr is data)
+    float* d_expr;                                          // accumulated (+=), may be null (the expression takes no gradient)
 };
 __device__ __forceinline__ float cond_val(const FoldBwdArgs& d, int c) {
     if (c < d.p.dim_aud) return d.aud[c];
@@ -188,7 +189,7 @@ __device__ __forceinline__ float cond_val(const FoldBwdArgs& d, int c) {
     return d.latent[c];
 }
 // kCondOnly: the launch covers the d cond index range alone (a frozen network: bwd_tail without gradient tensors) -- gW0 / gW5 /
-// gWv0 and dbv are never touched
+// gWv0 are never touched, dbv only with d_expr
 template <bool kCondOnly>
 __global__ void fold_bwd_kernel(FoldBwdArgs d) {
     const int C = d.p.dim_aud + d.p.dim_expr + d.p.dim_latent;
@@ -241,7 +242,8 @@ __global__ void fold_bwd_kernel(FoldBwdArgs d) {
 // Column sums of two [rows, 256] fp32 matrices (row pitch 256): the bias gradients db0' / db5' the conditioning fold reads, for
 // a pass whose weight gradients nobody wants.  Deterministic, no float atomics: workgroup (b, m) sums rows
 // [b rows_per_block, (b + 1) rows_per_block) of matrix m in row order, one thread per column (a row is one coalesced 1 KB
-// line), in fp64; colsum_finish_kernel adds the partial sums in block order.
+// line), in fp64; colsum_finish_kernel adds the partial sums in block order.  Launched with 128 threads and one matrix
+// (grid.y = 1) the pair sums columns 0..127 alone: views_linears.0's deltas in dV0, dbv'.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void colsum_rows_kernel(const float* m0, const float* m1, long rows, long rows_per_block, double* part) {
     const float* m = blockIdx.y ? m1 : m0;
@@ -316,10 +318,12 @@ static int backward_pipe() {
 // rows): the transposed weight stream, the delta chain, the weight / bias gradient products and the conditioning fold.
 // launch_pass_bwd seeds the head deltas with the compositing backward, launch_facenerf_bwd with the caller's d raw.
 // grads == nullptr (a frozen network): after the delta chain only what d aud / d latent need -- the column sums of dA[0] and
-// dA[5] and the d cond range of the fold; no weight-gradient product runs and no gradient tensor is written.
+// dA[5] and the d cond range of the fold; no weight-gradient product runs and no gradient tensor is written.  There d_expr
+// and d_vb [128] (views_linears.0's bias gradient, overwritten) need dbv': the column sums of dV0[:, 0:128] over the P real
+// rows (the padding rows' deltas are whatever the chain made of rows the head deltas leave at zero: they stay out).
 static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grads, const float* aud, const float* expr,
-                    const float* latent, const float* acts, int64_t Pp, const BwdWs& w, float* d_aud, float* d_expr,
-                    float* d_latent, hipStream_t s) {
+                    const float* latent, const float* acts, int64_t P, int64_t Pp, const BwdWs& w, float* d_aud, float* d_expr,
+                    float* d_latent, hipStream_t s, float* d_vb = nullptr) {
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
     // the network's encoding widths: the leading dimensions of its three mixed-input tensors and the columns the narrow
     // takes keep of the 64-column products (the slab's x0 / dir matrices are 64 wide whatever the width)
@@ -340,18 +344,34 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
         TRY(launch_delta_chain(w.wbwd, acts, Pp, w.dRGB, w.dV0, w.dV[0], w.dV[1], w.dA, s));
     }
     if (!grads) {
-        if (C == 0) return IDN_OK;
+        const bool want_dbv = d_expr != nullptr || d_vb != nullptr;
+        if (C == 0 && !want_dbv) return IDN_OK;
         float* db = w.cpart;                                        // [2][256]: db0', db5'
         double* part = reinterpret_cast<double*>(w.cpart + 512);    // [blocks][2][256] (the pool is 256-byte aligned)
         const int64_t chunks = Pp / 128;
         const int64_t rows_per_block = (chunks + kCondColsumBlocks - 1) / kCondColsumBlocks * 128;
-        const int blocks = (int)((Pp + rows_per_block - 1) / rows_per_block);
-        hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 2), dim3(256), 0, s, (const float*)w.dA[0], (const float*)w.dA[5], (long)Pp,
-                           (long)rows_per_block, part);
-        IDN_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(colsum_finish_kernel, dim3(2), dim3(256), 0, s, (const double*)part, blocks, db);
-        IDN_HIP_CHECK(hipGetLastError());
-        FoldBwdArgs f{p, aud, expr, latent, db, db + 256, nullptr, nullptr, nullptr, nullptr, d_aud, d_latent, nullptr};
+        if (C > 0) {
+            const int blocks = (int)((Pp + rows_per_block - 1) / rows_per_block);
+            hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 2), dim3(256), 0, s, (const float*)w.dA[0], (const float*)w.dA[5], (long)Pp,
+                               (long)rows_per_block, part);
+            IDN_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(colsum_finish_kernel, dim3(2), dim3(256), 0, s, (const double*)part, blocks, db);
+            IDN_HIP_CHECK(hipGetLastError());
+        }
+        // dbv' [128]: the same two kernels, 128 threads wide, on dV0's delta columns and the real rows alone; `part` is free
+        // again (the stream orders it behind the finish above), the result goes to the caller's buffer or, with none, to the
+        // partial-product pool this plan never uses
+        float* dbv = d_vb ? d_vb : w.part;
+        if (want_dbv) {
+            const int blocks = (int)((P + rows_per_block - 1) / rows_per_block);
+            hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 1), dim3(128), 0, s, (const float*)w.dV0, (const float*)w.dV0, (long)P,
+                               (long)rows_per_block, part);
+            IDN_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(128), 0, s, (const double*)part, blocks, dbv);
+            IDN_HIP_CHECK(hipGetLastError());
+        }
+        if (C == 0) return IDN_OK;
+        FoldBwdArgs f{p, aud, expr, latent, db, db + 256, dbv, nullptr, nullptr, nullptr, d_aud, d_latent, d_expr};
         hipLaunchKernelGGL(fold_bwd_kernel<true>, dim3((C * 64 + 255) / 256), dim3(256), 0, s, f);
         IDN_HIP_CHECK(hipGetLastError());
         return IDN_OK;
@@ -444,7 +464,8 @@ static void launch_composite_bwd(const CompBwdArgs& a, int64_t n_rays, int S, hi
 int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
                     const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
                     const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
-                    const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s, float* d_rays) {
+                    const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s, float* d_rays,
+                    float* d_expr, float* d_vb) {
     const int64_t P = n_rays * S;
     const int64_t Pp = (P + 127) / 128 * 128;
     if (S < 2 || S > 64 * kMaxSpl) return fail(IDN_EUNSUPPORTED, "pass_bwd: n_samples %d outside [2, %d]", S, 64 * kMaxSpl);
@@ -466,7 +487,7 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, 
         else launch_composite_bwd<false>(a, n_rays, S, s);
         IDN_HIP_CHECK(hipGetLastError());
     }
-    if (int e = bwd_tail(p, gr, aud, expr, latent, acts, Pp, w, d_aud, nullptr, d_latent, s)) return e;
+    if (int e = bwd_tail(p, gr, aud, expr, latent, acts, P, Pp, w, d_aud, d_expr, d_latent, s, d_vb)) return e;
     if (d_rays) {
         float* d_x = w.dA[1];
         static_assert(IDN_PTS_CH + IDN_VIEWS_CH <= 256, "the input-row gradient fits a delta matrix");
@@ -623,7 +644,7 @@ int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& 
                            w.dRGB, w.dV0);
         IDN_HIP_CHECK(hipGetLastError());
     }
-    if (int e = bwd_tail(p, &gr, aud, expr, latent, acts, Pp, w, d_aud, d_expr, d_latent, s)) return e;
+    if (int e = bwd_tail(p, &gr, aud, expr, latent, acts, n, Pp, w, d_aud, d_expr, d_latent, s)) return e;
     if (d_x) return launch_dx(p, w, n, Pp, d_x, s);
     return IDN_OK;
 }

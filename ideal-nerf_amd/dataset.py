@@ -443,6 +443,12 @@ class ResidentFrames:
         the next call in stream order)."""
         return ops.sample_pixels(self.maps[index], self.counts, self.seed, draw, out=self._sel, workspace=self._ws)
 
+    def selection(self):
+        """The flat pixel indices of the latest ``select`` / ``batch`` (int64 [N_rand], row-major over H x W): row i of that
+        batch's rays, targets and background rows belongs to pixel ``selection()[i]``.  The loader's own buffer, as ``select``
+        returns it: the next draw overwrites it in stream order."""
+        return self._sel
+
     def batch(self, index, draw):
         """-> (batch_rays [2, n, 3], target_s [n, 3], bc_rgb [n, 3], auds, raw_img, pose, expr, index), every tensor on the device."""
         index = int(index)

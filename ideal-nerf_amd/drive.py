@@ -32,8 +32,16 @@ def _same_on_every_rank(build):
         return build()
 
 
+def _learned_background(frames, path, device):
+    """The checkpoint's ``background`` (``train(learn_background=True)``) in place of the loader's ``bc.jpg``: the frames are
+    rendered over it.  ValueError without a checkpoint, KeyError (``checkpoint.load_background``) for one that holds none."""
+    if path is None:
+        raise ValueError("learned_background: no checkpoint was loaded (no_reload, or none in the run directory)")
+    frames.background_img = checkpoint.load_background(path, map_location=device).to(device)
+
+
 def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", still_every=10, seed=None, group=None,
-               precision=None, model="head"):
+               precision=None, model="head", learned_background=False):
     """The eval script's ``eval()`` on the flags ``args`` (``helper.config_parser().parse_args()``): ``DrivingFrames(args.datadir,
     args.aud_file, "val", args, skip=args.testskip)``, a ``Network`` with ``to_render_config(args)`` and the loader's focal
     length, the checkpoint ``args.ft_path`` -- else the newest ``*.tar`` of ``basedir/expname`` --, read whole and without
@@ -45,7 +53,8 @@ def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", st
     ``args.save_path``; every ``still_every``-th frame is also written there as ``{datadir[8:]}_{aud_file[-9:-4]}_ExpPose_{i}.jpg``.
     ``precision``: ``set_render_precision``'s.  ``model``: "head", or "agg" for a run of ``train_agg.train``
     (``agg_aud_exp_nerf.Network``; its newest ``{epoch:06d}_head.tar``).  ValueError where the network's expression width --
-    ``args.dim_expr``, the agg pair's 79 -- is not the expression track's.
+    ``args.dim_expr``, the agg pair's 79 -- is not the expression track's.  ``learned_background``: render over the
+    checkpoint's ``background`` instead of ``bc.jpg`` (it raises if the checkpoint holds none); off: nothing changes.
     -> ``render_head_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
     from .agg_aud_exp_nerf import DIM_EXPR, build_head_network
     frames = dataset.DrivingFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device)
@@ -55,11 +64,14 @@ def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", st
         raise ValueError(f"dim_expr is {dim_expr}, the expression track {args.evalExpr_path} is {width} wide")
     network = _same_on_every_rank(lambda: build_head_network(args, frames.H, frames.W, frames.focal, model)).to(device)
     latent_code = torch.zeros(32, dtype=torch.float32)
+    path = None
     if not args.no_reload:
         path = args.ft_path if not _unset(args.ft_path) else checkpoint.latest_checkpoint(os.path.join(args.basedir, args.expname))
         if path is not None:
             _, codes = checkpoint.load_checkpoint(path, network, map_location=device)
             latent_code = codes[0]
+    if learned_background:
+        _learned_background(frames, path, device)
     if precision is not None:
         set_render_precision(network, precision)
     name = f"{args.datadir[8:].lstrip(os.sep)}_{args.aud_file[-9:-4]}"
@@ -129,7 +141,8 @@ def baseline_names(args):
     return f"V_{name}_N_baseline.avi", name + "_ADNeRF_{i}.jpg"
 
 
-def drive_baseline(args, *, out=None, device="cuda", codec="MJPG", still_every=10, seed=None, group=None, precision=None):
+def drive_baseline(args, *, out=None, device="cuda", codec="MJPG", still_every=10, seed=None, group=None, precision=None,
+                   learned_background=False):
     """The baseline tester's ``test()`` (NeRFs/HeadNeRF/test/test_nerf.py:140-190) on the flags ``args``
     (``helper.config_parser().parse_args()``): ``BaselineTestFrames(args.datadir, args.aud_file, "val", args,
     skip=args.testskip)`` -- the val poses, frame i with audio row i --, a ``head_baseline.Network`` with
@@ -141,17 +154,21 @@ def drive_baseline(args, *, out=None, device="cuda", codec="MJPG", still_every=1
     ``out`` defaults to upstream's ``V_{datadir[8:]}_{aud_file[:-4]}_N_baseline.avi`` under ``args.save_path``; every
     ``still_every``-th frame is also written there as ``{datadir[8:]}_{aud_file[:-4]}_ADNeRF_{i}.jpg``.  Channels as upstream
     (:184-189): the red/blue-swapped bytes go to BOTH writers, the clip's (which takes them as BGR) and the stills' (which
-    takes them as RGB).  Frame-parallel inside a process group like ``drive_head``.
+    takes them as RGB).  Frame-parallel inside a process group like ``drive_head``.  ``learned_background``: as ``drive_head``
+    (the run file of ``train_baseline.train(learn_background=True)``; an AD-NeRF ``ft_path`` holds none).
     -> ``render_head_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
     from .agg_aud_exp_nerf import build_head_network
     frames = dataset.BaselineTestFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device)
     network = _same_on_every_rank(lambda: build_head_network(args, frames.H, frames.W, frames.focal, "baseline")).to(device)
     if not _unset(args.ft_path):
+        path = args.ft_path
         checkpoint.load_adnerf(args.ft_path, network, map_location=device)
     else:
         path = checkpoint.latest_checkpoint(os.path.join(args.basedir, args.expname), contains="tar")
         if path is not None:
             checkpoint.load_baseline_checkpoint(path, network, map_location=device)
+    if learned_background:
+        _learned_background(frames, path, device)
     if precision is not None:
         set_render_precision(network, precision)
     clip_name, still_name = baseline_names(args)

@@ -252,35 +252,33 @@ def query_rays_train_fwd(packed, folded, rays, z, precision=_lib.IDN_PREC_BF16X6
 
 
 def _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias=None,
-              d_rays=None, with_rays=False):
-    """The checks and the call behind `pass_bwd` (grads: a dict), `pass_bwd_rays` (with_rays) and `pass_bwd_cond` (grads: None)."""
+              d_rays=None, with_rays=False, d_expr=None, ex=False):
+    """The checks and the call behind `pass_bwd` (grads: a dict), `pass_bwd_rays` (with_rays), `pass_bwd_cond` (grads: None)
+    and `pass_bwd_ex` (ex: either plan through idealnerf_pass_bwd_ex, with d_expr / d_rays / d_views0_bias as its extras)."""
     lib = _lib.load()
     if grads is None:
         grads = {}
     n, S = z.shape
     for t, name, shape in ((raw, "raw", (n, S, 4)), (rays, "rays", (n, RAY_FLOATS)), (bc, "bc_rgb", (n, 3)),
                            (g_rgb, "g_rgb_map", (n, 3)), (g_fg, "g_rgb_fg", (n, 3)), (g_lw, "g_last_weight", (n,)),
-                           (g_acc, "g_acc", (n,)), (d_rays, "d_rays", (n, RAY_FLOATS))):
+                           (g_acc, "g_acc", (n,)), (d_rays, "d_rays", (n, RAY_FLOATS)), (d_expr, "d_expr", (p.dim_expr,))):
         _shape(t, name, *shape)
     tensors = (aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent)
-    with _Launch(*tensors, d_rays, *grads.values()) as L:
+    with _Launch(*tensors, d_rays, d_expr, d_views0_bias if ex else None, *grads.values()) as L:
         ws = _workspace(lib.idealnerf_pass_bwd_workspace_bytes(n, S), z.device, L.stream)   # scratch of this (device, stream): two streams training on one GPU do not share it
         ptrs = [_ptr(t) for t in tensors]
-        if with_rays:
+        if ex:
+            _shape(d_views0_bias, "d_views0_bias", W_HID // 2)
+            extra = _lib.PassBwdExtra(_ptr(d_expr, "d_expr"), _ptr(d_rays, "d_rays"), _ptr(d_views0_bias, "d_views0_bias"))
+            check(lib.idealnerf_pass_bwd_ex(C.byref(p), C.byref(grads_struct(grads)) if grads else None, *ptrs[:8], n, S, *ptrs[8:],
+                                            C.byref(extra), ws.data_ptr(), ws.numel(), L.stream))
+        elif with_rays:
             check(lib.idealnerf_pass_bwd_rays(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], _ptr(d_rays, "d_rays"),
                                               ws.data_ptr(), ws.numel(), L.stream))
         elif grads:
             check(lib.idealnerf_pass_bwd(C.byref(p), C.byref(grads_struct(grads)), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
         else:
             check(lib.idealnerf_pass_bwd_cond(C.byref(p), *ptrs[:8], n, S, *ptrs[8:], ws.data_ptr(), ws.numel(), L.stream))
-            if d_views0_bias is not None:
-                _shape(d_views0_bias, "d_views0_bias", W_HID // 2)
-                # The pass's delta chain has left views_linears.0's deltas in the workspace: the tenth [p_pad, 256] matrix of
-                # csrc/train.hip: carve_bwd (eight of pts_linears.l, one of views_linears.2 | .1, then dV0: columns 0..127).
-                # Their column sums over the pass's points, in fp64, before anything else on this stream touches the scratch.
-                p_pad = (n * S + 127) // 128 * 128
-                dv0 = ws[9 * p_pad * 1024:10 * p_pad * 1024].view(torch.float32).view(p_pad, 256)
-                d_views0_bias.copy_(torch.sum(dv0[:n * S, :W_HID // 2], dim=0, dtype=torch.float64))
     return grads
 
 
@@ -303,13 +301,26 @@ def pass_bwd_cond(p, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_l
     accumulated; nothing else is written.
 
     d_views0_bias [128] (optional, OVERWRITTEN): the gradient of views_linears.0's bias -- what `pass_bwd` returns as that
-    entry of `grads` -- for a network whose conditioning also reaches that bias (FaceNeRFAgg).  The C entry does not return it;
-    it is summed here from the deltas the entry leaves in this stream's workspace, whose place there is csrc/train.hip's
-    carve_bwd (tests/test_agg_gpu.py::test_agg_frozen_pair_d_aud_vs_fp64 fails if that layout moves).  Needs d_aud or
-    d_latent: with both None the entry launches nothing."""
+    entry of `grads` -- for a network whose conditioning also reaches that bias (FaceNeRFAgg).  That entry does not return it:
+    with it the call goes through idealnerf_pass_bwd_ex, which sums the deltas' columns itself (fp64, fixed order, the pass's
+    real rows).  Needs d_aud or d_latent: with both None the entry launches nothing."""
     if d_views0_bias is not None and d_aud is None and d_latent is None:
         raise IdealNerfError("pass_bwd_cond: d_views0_bias needs d_aud or d_latent (with neither the pass is not run)")
-    _pass_bwd(p, None, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias)
+    _pass_bwd(p, None, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_views0_bias,
+              ex=d_views0_bias is not None)
+
+
+def pass_bwd_ex(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, d_expr=None,
+                d_rays=None, d_views0_bias=None):
+    """The pass backward with every optional gradient (idealnerf_pass_bwd_ex).  grads: a dict as `pass_bwd` takes it (the
+    training plan), or None (the frozen plan of `pass_bwd_cond`: it runs when any of d_aud / d_latent / d_expr is given).
+      d_expr [dim_expr]: ACCUMULATED, like d_aud -- the gradient of the expression the pass was conditioned on;
+      d_rays [n, 11]: OVERWRITTEN, as `pass_bwd_rays` (the training plan only);
+      d_views0_bias [128]: OVERWRITTEN, the bias gradient of views_linears.0, written by the entry itself (the frozen plan only).
+    Every other output is bit for bit what `pass_bwd` / `pass_bwd_rays` / `pass_bwd_cond` return on the same inputs.  The
+    background needs no call: d bc = g_rgb * last_weight[:, None] of the pass's forward."""
+    return _pass_bwd(p, grads, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent,
+                     d_views0_bias=d_views0_bias, d_rays=d_rays, d_expr=d_expr, ex=True)
 
 
 def query_rays_fwd(packed, folded, rays, z, precision=IDN_PREC_F32) -> torch.Tensor:

@@ -125,7 +125,8 @@ def _summary_writer(logdir):
 
 
 def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30,
-          val="reference", refine_poses=False, pose_lrate=None):
+          val="reference", refine_poses=False, pose_lrate=None, refine_expr=False, expr_lrate=None, learn_background=False,
+          bg_lrate=None):
     """The reference's ``train()`` (audio_exp_nerf.py:451-593) on the flags ``args`` (``helper.config_parser().parse_args()``):
     write_config, the train and validation datasets, ``Network`` + ``init_weights``, ``latent_codes = ones[n_frames, 32]``, Adam,
     warm start from ``ft_path`` or resume from the newest ``*.tar`` of ``basedir/expname``, then epochs over the frames in
@@ -160,20 +161,37 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     ``pose_lrate`` (default 0.1 * lrate: a starting point nobody has tuned) and decays by the same schedule; inside a process
     group the gradient all-reduce covers them.  The checkpoint gains ``pose_deltas`` and a resumed run restores them.  Validation
     frames are rendered from their own poses.
-    -> dict(network, optimizer, latent_codes, global_step, data_size[, pose_refiner])."""
+
+    refine_expr / learn_background (no counterpart upstream either; off: nothing below exists, and the file's keys, the
+    optimizer's groups and every launch of the step are what they were): two more inputs of the offline pipeline train with the
+    model (``cond_refine``).  refine_expr: one additive correction per training frame on the tracker's expression row
+    (``ExprRefiner``, zero at the start), applied to the step's expression before the network sees it; the render backward
+    returns d expr.  learn_background: the background image is a parameter (``Background``, initialised from ``bc.jpg`` as
+    uint8 / 255, not clamped); the step renders over its pixels at the batch's pixel indices -- which only the resident loader
+    hands over (``ResidentFrames.selection``): with loader = "reference" it raises ValueError -- and the render backward
+    returns d bc.  Each is a parameter group of the same Adam with a rate of its own that decays by the same schedule and is
+    covered by the gradient all-reduce: ``expr_lrate`` (default 0.1 * lrate) and ``bg_lrate`` (default lrate) -- both starting
+    points nobody has tuned.  The checkpoint gains ``expr_deltas`` / ``background`` and a resumed run restores them (it
+    continues bit for bit under the conditions above as long as no pixel is drawn more than twice in a batch: two addends
+    commute).  Validation frames keep their own expressions and are rendered over the learned background.  A model without an
+    expression (the AD-NeRF baseline) raises ValueError for refine_expr.  The torso stage has neither option.
+    -> dict(network, optimizer, latent_codes, global_step, data_size[, pose_refiner][, expr_refiner][, background])."""
     from . import dataset
     return _train_head_model(args, "head", dataset.ResidentFrames, dataset.GetData, lambda epoch: 'head.tar', True, loader=loader,
                              sample_seed=sample_seed, device=device, steps=steps, on_log=on_log, on_step=on_step,
-                             max_bytes=max_bytes, val=val, refine_poses=refine_poses, pose_lrate=pose_lrate)
+                             max_bytes=max_bytes, val=val, refine_poses=refine_poses, pose_lrate=pose_lrate,
+                             refine_expr=refine_expr, expr_lrate=expr_lrate, learn_background=learn_background, bg_lrate=bg_lrate)
 
 
 def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name, flip, *, loader, sample_seed, device, steps,
-                      on_log, on_step, max_bytes, val, with_codes=True, refine_poses=False, pose_lrate=None):
+                      on_log, on_step, max_bytes, val, with_codes=True, refine_poses=False, pose_lrate=None, refine_expr=False,
+                      expr_lrate=None, learn_background=False, bg_lrate=None):
     """The body of ``train`` for a head-stage model (``agg_aud_exp_nerf.HEAD_MODELS``): its two loader classes, its checkpoint
     name per epoch, and whether the validation image is channel-flipped (the loader reads BGR).  with_codes=False (the AD-NeRF
     baseline): no per-frame latent codes exist -- Adam runs over the network alone, the step is ``baseline_train_step`` on the
     loaders' 7-tuples, ``ft_path`` is read in full (``checkpoint.load_adnerf``) and the run file is
-    ``checkpoint.save_baseline_checkpoint``'s; the returned ``latent_codes`` is None.  refine_poses / pose_lrate: as ``train``."""
+    ``checkpoint.save_baseline_checkpoint``'s; the returned ``latent_codes`` is None.  refine_poses / pose_lrate, refine_expr / expr_lrate,
+    learn_background / bg_lrate: as ``train``."""
     import numpy as np
     from . import checkpoint
     from .agg_aud_exp_nerf import build_head_network
@@ -184,6 +202,16 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
         raise ValueError(f"loader must be 'resident' or 'reference', got {loader!r}")
     if val not in ("reference", "resident"):
         raise ValueError(f"val must be 'reference' or 'resident', got {val!r}")
+    # the expression's width: the agg pair's is its own constant (79), the head pair's the flag; the baseline has none
+    if model == "agg":
+        from .agg_aud_exp_nerf import DIM_EXPR as dim_expr
+    else:
+        dim_expr = getattr(args, "dim_expr", 0) if with_codes else 0
+    if refine_expr and not dim_expr:
+        raise ValueError(f"refine_expr: the {model} model takes no expression")
+    if learn_background and loader != "resident":
+        raise ValueError("learn_background needs the step's pixel indices, which the resident loader alone hands over "
+                         "(loader='resident')")
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
     rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if dist_on else (0, 1)
     basedir, expname = args.basedir, args.expname
@@ -221,6 +249,18 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
         pose_lrate = 0.1 * args.lrate if pose_lrate is None else float(pose_lrate)
         optimizer.add_param_group({'params': [refiner.deltas], 'lr': pose_lrate, 'lr_scale': pose_lrate / args.lrate})
 
+    expr_refiner = background = None
+    if refine_expr:
+        from .cond_refine import ExprRefiner
+        expr_refiner = ExprRefiner(data_size, dim_expr).to(device)
+        expr_lrate = 0.1 * args.lrate if expr_lrate is None else float(expr_lrate)
+        optimizer.add_param_group({'params': [expr_refiner.deltas], 'lr': expr_lrate, 'lr_scale': expr_lrate / args.lrate})
+    if learn_background:
+        from .cond_refine import Background
+        background = Background(dataset_train.background).to(device)
+        bg_lrate = args.lrate if bg_lrate is None else float(bg_lrate)
+        optimizer.add_param_group({'params': [background.image], 'lr': bg_lrate, 'lr_scale': bg_lrate / args.lrate})
+
     global_step = 0
     if args.ft_path is not None and args.ft_path != 'None':
         logger.info(f'Found ckpts:{[args.ft_path]}')
@@ -236,13 +276,18 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
                 global_step = checkpoint.load_baseline_checkpoint(ckpt_path, network, optimizer, map_location=device)
             if refiner is not None:
                 refiner.deltas.data.copy_(checkpoint.load_pose_deltas(ckpt_path, map_location=device))
+            if expr_refiner is not None:
+                expr_refiner.deltas.data.copy_(checkpoint.load_expr_deltas(ckpt_path, map_location=device))
+            if background is not None:
+                background.image.data.copy_(checkpoint.load_background(ckpt_path, map_location=device))
 
     network.train()
 
     def validate(step):
+        bg = None if background is None else background().detach()   # a validation frame stands before the learned background
         if frames_val is None:
-            return validation_frame(network, dataset_val, latent_codes, step, sample_seed, flip=flip), None
-        return resident_validation_frame(network, frames_val, latent_codes, step, sample_seed, flip=flip)
+            return validation_frame(network, dataset_val, latent_codes, step, sample_seed, flip=flip, background=bg), None
+        return resident_validation_frame(network, frames_val, latent_codes, step, sample_seed, flip=flip, background=bg)
 
     if with_codes:
         step_fn = lambda data, step: train_step(network, optimizer, data, latent_codes, step, data_size, lrate=args.lrate,
@@ -262,12 +307,24 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
         # the deltas beside everything else in the checkpoint
         plain_step = step_fn
         step_fn = lambda data, step: plain_step((refiner(int(data[-1]), data[0]), *data[1:]), step)
+    if expr_refiner is not None:   # (the tuples with an expression end in expr, index)
+        pose_step = step_fn
+        step_fn = lambda data, step: pose_step((*data[:-2], expr_refiner(int(data[-1]), data[-2]), data[-1]), step)
+    if background is not None:
+        # bc_rgb is the third field of every head-stage tuple: the parameter's pixels at the indices the loader has just drawn
+        # (its buffer holds them until the next draw: past this step's backward) in place of the rows it gathered from bc.jpg
+        expr_step = step_fn
+        step_fn = lambda data, step: expr_step((*data[:2], background.rows(dataset_train.selection()), *data[3:]), step)
+    if refiner is not None or expr_refiner is not None or background is not None:
+        extras = dict(pose_deltas=None if refiner is None else refiner.deltas)
+        if background is not None:
+            extras["background"] = background.image
         if with_codes:
-            save = lambda path, net, opt, codes, step: checkpoint.save_checkpoint(path, net, opt, codes, step,
-                                                                                  pose_deltas=refiner.deltas)
+            if expr_refiner is not None:
+                extras["expr_deltas"] = expr_refiner.deltas
+            save = lambda path, net, opt, codes, step: checkpoint.save_checkpoint(path, net, opt, codes, step, **extras)
         else:
-            save = lambda path, net, opt, codes, step: checkpoint.save_baseline_checkpoint(path, net, opt, step,
-                                                                                           pose_deltas=refiner.deltas)
+            save = lambda path, net, opt, codes, step: checkpoint.save_baseline_checkpoint(path, net, opt, step, **extras)
     global_step = _run_epochs(
         args, network, optimizer, latent_codes, data_size, global_step, steps, rank, on_log, on_step,
         batch=lambda it, step: (dataset_train.batch(it, draw_index(step, rank, world)) if loader == "resident"
@@ -276,6 +333,10 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
     out = dict(network=network, optimizer=optimizer, latent_codes=latent_codes, global_step=global_step, data_size=data_size)
     if refiner is not None:
         out["pose_refiner"] = refiner
+    if expr_refiner is not None:
+        out["expr_refiner"] = expr_refiner
+    if background is not None:
+        out["background"] = background
     return out
 
 
@@ -344,7 +405,7 @@ def _validation_index(n, global_step, sample_seed):
     return int(torch.randint(n, (1,), generator=gen))
 
 
-def validation_frame(network, dataset_val, latent_codes, global_step, sample_seed=0, flip=True):
+def validation_frame(network, dataset_val, latent_codes, global_step, sample_seed=0, flip=True, background=None):
     """audio_exp_nerf.py:568-581: one randomly chosen validation frame rendered in eval mode under no_grad with
     ``latent_codes[0]``, stacked over its ground truth, channels flipped to RGB -> [3, 2 H, W] on the host; the network
     goes back to train mode.  The frame is chosen by a generator of its own seeded from (sample_seed, global_step) --
@@ -354,12 +415,18 @@ def validation_frame(network, dataset_val, latent_codes, global_step, sample_see
     val_i = _validation_index(len(dataset_val), global_step, sample_seed)
     network.eval()
     try:
-        item = _as_loader_item(dataset_val[val_i], latent_codes is not None)
+        item = _over_background(_as_loader_item(dataset_val[val_i], latent_codes is not None), background)
         with torch.no_grad():
             rgb = network([_eval_tuple(item, latent_codes), global_step, dataset_val.data_size])[0]
     finally:
         network.train()
     return _pred_over_label(rgb, _raw_img(item, latent_codes), flip)
+
+
+def _over_background(item, background):
+    """A head-stage loader's eval item with ``background`` [H, W, 3] (a learned one: ``train(learn_background=True)``) in its
+    bg_img field, the third; None: the item as it is."""
+    return item if background is None else (*item[:2], background, *item[3:])
 
 
 def _eval_tuple(item, latent_codes):
@@ -377,7 +444,7 @@ def _pred_over_label(rgb, raw_img, flip):
     return pred_with_label[[2, 1, 0], :, :] if flip else pred_with_label
 
 
-def resident_validation_frame(network, frames_val, latent_codes, global_step, sample_seed=0, flip=True):
+def resident_validation_frame(network, frames_val, latent_codes, global_step, sample_seed=0, flip=True, background=None):
     """``validation_frame`` from a resident validation clip (``dataset.ResidentFrames(mode="val")``, or the torso stage's): the
     same frame index from the same generator, the frame's inputs from ``frames_val.frame`` (no file read, no host meshgrid), and
     the render scored on the device against the frame's ground truth, whole frame and per sampling region
@@ -388,7 +455,7 @@ def resident_validation_frame(network, frames_val, latent_codes, global_step, sa
     val_i = _validation_index(len(frames_val), global_step, sample_seed)
     network.eval()
     try:
-        data = frames_val.frame(val_i)
+        data = _over_background(frames_val.frame(val_i), background)
         with torch.no_grad():
             rgb = network([_eval_tuple(data, latent_codes), global_step, frames_val.data_size])[0]
             table = ops.frame_scores(rgb, frames_val.imgs[val_i], frames_val.maps[val_i])

@@ -486,7 +486,7 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
  *   raw2outputs' dists = dz * |rays_d| (baseline.py:341-343): d rays_d += (sum_{s < S-1} dL/d dist_s dz_s) rays_d / |rays_d|
  *     (the last sample's 1e10 spacing saturates alpha and is left out).
  * Depths carry no gradient (coarse depths depend on near / far alone; fine depths are detached upstream, :345); the
- * background, the expression and near / far get none here.  Fixed summation order, no float atomics: a ray's gradient is a
+ * background, the expression and near / far get none here (the first two: idealnerf_pass_bwd_ex).  Fixed summation order, no float atomics: a ray's gradient is a
  * function of the inputs alone, wherever the ray stands in the batch.  d_rays == NULL: exactly idealnerf_pass_bwd.
  * Argument errors return IDN_EINVAL, a short workspace IDN_EWORKSPACE, before any HIP call.  The frozen plan
  * (idealnerf_pass_bwd_cond) has no such variant.  Additive entry: the ABI version is unchanged.
@@ -511,6 +511,46 @@ int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, cons
                             int64_t n_rays, int n_samples, const float* g_rgb_map, const float* g_rgb_fg,
                             const float* g_last_weight, const float* g_acc, float* d_aud, float* d_latent, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/*
+ * Optional outputs of idealnerf_pass_bwd_ex; every field may be NULL, and a NULL struct pointer is a struct of NULLs.
+ *   d_expr [dim_expr]: ACCUMULATED (+=), like d_aud:
+ *     d expr[e] = (d cond[dim_aud + e] + sum_n Wv0[n][256 + views_ch + e] dbv'[n]) / 3
+ *     (expr / 3 enters pts_linears.0, pts_linears.5 and views_linears.0, face_nerf.py:49; dbv' is views_linears.0's bias
+ *     gradient).  The expression's weight-gradient columns are what they were.  Non-NULL for a network with dim_expr == 0
+ *     (or with expr == NULL): IDN_EINVAL.
+ *   d_rays [n_rays, IDN_RAY_FLOATS]: OVERWRITTEN, exactly as idealnerf_pass_bwd_rays documents.
+ *   d_views0_bias [128]: OVERWRITTEN; the frozen plan only (with grads it is grads->views_b[0]: IDN_EINVAL).  The gradient of
+ *     views_linears.0's bias, for a caller whose conditioning also reaches that bias; it needs one of d_aud / d_latent /
+ *     d_expr (IDN_EINVAL otherwise: with none of them the pass is not run).
+ */
+typedef struct idn_pass_bwd_extra {
+    float* d_expr;
+    float* d_rays;
+    float* d_views0_bias;
+} idn_pass_bwd_extra;
+
+/*
+ * The pass backward with every optional gradient: the arguments of idealnerf_pass_bwd plus `extra`.
+ *   grads != NULL: the training plan.  With d_expr the conditioning fold also sums the expression's columns of
+ *     views_linears.0 against that layer's bias gradient; with d_rays the entry is idealnerf_pass_bwd_rays.
+ *   grads == NULL: the frozen plan, idealnerf_pass_bwd_cond.  d_expr / d_views0_bias need dbv' there: the column sums, over
+ *     the pass's n_rays * n_samples points (never the padding rows up to a multiple of 128), of the views_linears.0 deltas
+ *     the delta chain leaves in the workspace -- summed as that entry sums pts_linears.0 / .5: fp64, row blocks in row order,
+ *     partial sums added in block order, no atomics.  It runs when any of d_aud, d_latent, d_expr is wanted and launches
+ *     nothing when none is.  d_rays there: IDN_EUNSUPPORTED.
+ * Every output the three entries above share is bit for bit theirs, whatever `extra` asks for; with every extra NULL the
+ * entry IS the corresponding one of them (they call the same host function).  The background takes no kernel:
+ * rgb_map is linear in bc_rgb with the pass's last_weight as coefficient, d bc = g_rgb_map * last_weight[:, None].  Near /
+ * far and depths still get no gradient.  Argument errors return before any HIP call.  Additive entry: the ABI version is
+ * unchanged.
+ */
+int idealnerf_pass_bwd_ex(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
+                          const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
+                          const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
+                          const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
+                          float* d_latent, const idn_pass_bwd_extra* extra, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /*
  * FaceNeRF.forward with gradients (models/face_nerf.py:40-80): the module trained on pre-embedded rows, outside

@@ -5,6 +5,7 @@
     python tools/drive_clip.py --flow head  --config <file> [--gpus N] [--precision P] [--out PATH] [--codec raw] [--global-step S]
     python tools/drive_clip.py --flow torso --config <file> [--gpus N] [--precision P] [--out PATH] [--codec raw]
     python tools/drive_clip.py --flow head --model baseline --config <adnerf_baseline.txt> [--gpus N] ...
+    python tools/drive_clip.py --flow head --config <file> --learned_background    # over the checkpoint's learned background
 
 --flow head is ``drive.drive_head`` (the reference's eval script): the flags of the head stage's config file -- ``datadir``,
 ``aud_file``, ``evalExpr_path``, ``testskip``, ``basedir`` / ``expname`` or ``ft_path``, ``save_path`` --, the identity's val poses,
@@ -56,6 +57,9 @@ def parse(argv):
     p.add_argument("--seed", type=int, default=None, help="per-frame draws seeded with seed + frame (perturb > 0)")
     p.add_argument("--model", choices=("head", "agg", "baseline"), default="head",
                    help="--flow head: the run's model (agg: train_agg.train's; baseline: train_baseline.train's or an AD-NeRF ft_path)")
+    p.add_argument("--learned_background", action="store_true",
+                   help="--flow head: render over the checkpoint's `background` (train_head.py --learn_background) instead of bc.jpg; "
+                        "an error if the checkpoint holds none")
     return p.parse_args(argv)
 
 
@@ -64,6 +68,8 @@ def main(argv=None):
     args = parse(argv)
     if args.config is None:
         sys.exit("drive_clip.py: --config <file> is required (the stage's config file)")
+    if args.learned_background and args.flow != "head":
+        sys.exit("drive_clip.py: --learned_background belongs to --flow head (the torso stage learns no background)")
     if args.gpus > 1 and "RANK" not in os.environ:
         from render_clip import launch
         return launch(args.gpus, argv, script=__file__)
@@ -75,10 +81,11 @@ def main(argv=None):
         from idealnerf_amd import drive
         common = dict(out=args.out, device=dev, codec=args.codec, still_every=args.still_every, seed=args.seed,
                       precision=args.precision)
+        learned = dict(learned_background=True) if args.learned_background else {}
         if args.flow == "head" and args.model == "baseline":
-            res = drive.drive_baseline(args, **common)
+            res = drive.drive_baseline(args, **common, **learned)
         elif args.flow == "head":
-            res = drive.drive_head(args, global_step=args.global_step, model=args.model, **common)
+            res = drive.drive_head(args, global_step=args.global_step, model=args.model, **common, **learned)
         else:
             res = drive.drive_torso(args, **common)
         if res is not None:

@@ -6,6 +6,7 @@
                                [--gpus N] --out scores.json
     python tools/score_clip.py --out scores.json                                   # a generated clip, xavier weights
     python tools/score_clip.py --timing-json profiles/score_clip.json
+    python tools/score_clip.py --config <file> --ckpt head.tar --learned_background --out scores.json   # over the learned background
 
 The val split of the config's dataset directory goes to the device once (``dataset.ResidentFrames(mode="val")``) and is scored
 once per entry of --precisions through ``set_render_precision``; the file holds, per arithmetic, the per-frame table, the
@@ -55,6 +56,9 @@ def parse(argv):
     p.add_argument("--model", choices=("head", "agg", "baseline"), default="head",
                    help="agg: the feature-aggregation network and its loader; baseline: the AD-NeRF baseline and its loader "
                         "(--ckpt: a {epoch:06d}_head.tar of train_baseline.train or an AD-NeRF four-dict file)")
+    p.add_argument("--learned_background", action="store_true",
+                   help="render over the checkpoint's `background` (train_head.py --learn_background) instead of bc.jpg; an error "
+                        "without --ckpt or if the checkpoint holds none")
     return p.parse_args(argv)
 
 
@@ -89,6 +93,10 @@ def build(args, dev):
     from idealnerf_amd.agg_aud_exp_nerf import build_head_network
     resident = {"agg": dataset.ResidentAggFrames, "baseline": dataset.ResidentBaselineFrames}.get(args.model, dataset.ResidentFrames)
     frames = resident(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=dev)
+    if args.learned_background:   # what frame() hands the full-frame render as bg_img
+        if not args.ckpt:
+            raise SystemExit("--learned_background needs --ckpt")
+        frames.background_unit = checkpoint.load_background(args.ckpt, map_location="cpu").to(dev)
     torch.manual_seed(0)   # the audio nets: every rank builds the same network
     net = build_head_network(args, frames.H, frames.W, frames.focal, args.model)
     step, latent = net.args.nosmo_iters, torch.ones(32)
