@@ -73,6 +73,17 @@ class RenderOpts(C.Structure):
     _fields_ = [("colour_gate", C.c_int), ("gate_counters", fp)]
 
 
+class CullGridStruct(C.Structure):
+    _fields_ = [("bits", fp), ("G", C.c_int), ("lo", C.c_float * 3), ("cell", C.c_float)]   # idn_cull_grid
+
+
+CULL_MAX_OUTPUTS = 12   # IDN_CULL_MAX_OUTPUTS
+
+
+class CullOutput(C.Structure):
+    _fields_ = [("dense", fp), ("live", fp), ("channels", C.c_int), ("fill_background", C.c_int), ("value", C.c_float)]   # idn_cull_output
+
+
 DW_MAX_PRODUCTS, DW_MAX_TAKES, DW_MAX_COLSUM_TAKES = 16, 4, 2   # IDN_DW_MAX_*
 
 
@@ -161,6 +172,12 @@ PROTOTYPES = {
     "idealnerf_delta_chain_workspace_bytes": (C.c_size_t, []),
     "idealnerf_delta_chain": (C.c_int, [C.POINTER(FaceNerfParams), C.c_int, fp, C.c_int64, fp, fp, fp, fp, C.c_int,
                                         C.POINTER(C.c_int), fp, C.c_size_t, fp]),
+    "idealnerf_cull_mark": (C.c_int, [fp, C.c_int64, C.c_float, fp, fp]),
+    "idealnerf_cull_cells": (C.c_int, [fp, C.c_int, C.c_int, fp, fp]),
+    "idealnerf_cull_classify_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "idealnerf_cull_classify": (C.c_int, [C.POINTER(CullGridStruct), C.POINTER(Frame), C.c_float, C.c_int, fp, fp, fp, C.c_size_t, fp]),
+    "idealnerf_cull_gather": (C.c_int, [fp, C.c_int64, C.POINTER(Frame), fp, fp, fp, fp]),
+    "idealnerf_cull_scatter": (C.c_int, [fp, C.c_int64, C.c_int64, fp, C.POINTER(CullOutput), C.c_int, fp]),
     "idealnerf_profile_begin": (None, []),
     "idealnerf_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "idealnerf_profile_end_kinds": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -174,6 +174,10 @@ class Network(nn.Module):
             return render_rays_apply(self, coarse, fine, rays, bc_rgb, aud_para, latent_code, expr, perturb, pytest,
                                      with_fg, lindisp=lindisp)
         bc_rgb = bc_rgb.to(torch.float32).contiguous()
+        grid, grid_name = (None, None) if frame is None else self._cull_grid(coarse)
+        if grid is not None:
+            return self._render_culled(grid, grid_name, frame, bc_rgb, aud_para, latent_code, expr, coarse, fine, with_fg, retraw,
+                                       lindisp, perturb, white_bkgd, raw_noise_std, pytest, taps)
         if frame is None:
             rays = rays.to(torch.float32).contiguous()
             n, dev = rays.shape[0], rays.device
@@ -218,6 +222,59 @@ class Network(nn.Module):
                 ret['rgb_map_fg0'] = out['rgb_fg0']
         if taps:
             ret.update({k: v for k, v in out.items() if k.startswith('tap_')})
+        return ret
+
+    # ---- ray cull (cull.py): opt-in empty-space skipping of full-frame inference renders ----
+    def set_cull(self, head=None, torso=None):
+        """Install (or, with None, remove) the ``cull.CullGrid`` of the head pair (face_nerf_coarse / face_nerf_fine) and of
+        the torso pair (torso_coarse_nerf / torso_fine_nerf).  With a grid installed, an inference render of a full frame
+        (`frame` mode) of that pair renders only the pixels the grid calls live and writes the others down."""
+        self._cull = {k: g for k, g in (("head", head), ("torso", torso)) if g is not None}
+
+    def _cull_grid(self, coarse):
+        grids = getattr(self, "_cull", None)
+        if not grids:
+            return None, None
+        name = "head" if coarse is self.face_nerf_coarse else "torso" if coarse is getattr(self, "torso_coarse_nerf", None) else None
+        return grids.get(name), name
+
+    def _render_culled(self, grid, grid_name, frame, bc_rgb, aud_para, latent_code, expr, coarse, fine, with_fg, retraw, lindisp,
+                       perturb, white_bkgd, raw_noise_std, pytest, taps):
+        """`_render` of a full frame with a cull grid: the live pixels through the same ops.render_rays_fwd (rays mode, same
+        options), the others filled.  perturb > 0: the draws are made for the live rays -- [n_live, .] tensors, or in-kernel
+        with the row within the live list as the ray index -- so the numbers differ from the unculled frame's."""
+        from . import cull
+        cull.refuse(grid_name, taps, retraw, white_bkgd, raw_noise_std, lindisp)
+        args = self.args
+        S, Ni = args.N_samples, args.N_importance
+        dev = bc_rgb.device
+        names = ['rgb_map', 'disp_map', 'acc_map'] + (['rgb0', 'disp0', 'acc0', 'z_std', 'last_weight'] if Ni > 0 else [])
+        if with_fg:
+            names += ['rgb_fg'] + (['last_weight0', 'rgb_fg0'] if Ni > 0 else [])
+
+        def render_live(rays, bc_live, n):
+            if self.in_kernel_draws and perturb > 0. and not pytest:
+                draws, t_rand, u = (int(torch.randint(0, 2 ** 62, (1,)).item()), 0), None, None
+            else:
+                draws = None
+                t_rand, u = self.draw_randoms(n, S, Ni, perturb, pytest, dev)
+            fc = coarse.folded_bias(aud_para, expr, latent_code)
+            ff = fine.folded_bias(aud_para, expr, latent_code) if Ni > 0 else None
+            return ops.render_rays_fwd(rays, bc_live, coarse.packed_weights(), fc, fine.packed_weights() if Ni > 0 else None, ff,
+                                       linspace01(S, dev), u, Ni, t_rand=t_rand, with_fg=with_fg, precision=coarse.prec_code,
+                                       precision_fine=fine.prec_code if Ni > 0 else None, fused=0, draws=draws)
+
+        with torch.no_grad():
+            out = cull.render_culled(grid, frame, bc_rgb, render_live, names)
+        ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
+        if with_fg:
+            ret['rgb_map_fg'] = out['rgb_fg']
+        if Ni > 0:
+            for k in ('rgb0', 'disp0', 'acc0', 'z_std', 'last_weight'):
+                ret[k] = out[k]
+            if with_fg:
+                ret['last_weight0'] = out['last_weight0']
+                ret['rgb_map_fg0'] = out['rgb_fg0']
         return ret
 
     @staticmethod

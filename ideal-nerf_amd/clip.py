@@ -96,8 +96,97 @@ def _forward_tuple(data, latent_code, model):
     return tuple(data) if model == "baseline" else (*data[:7], latent_code, data[7])
 
 
+def head_cull_conditioning(network, items, global_step, dataset_size, latent_code, model="head"):
+    """What a cull grid of the head pair is built from (cull.build_grid): per item of `items` -- the tuples the loop hands to
+    ``network([tuple, global_step, dataset_size])``, collated by a loader or not -- the (aud_para, expr, latent_code) triple
+    ``Network.forward`` passes to the render, made by the functions it calls (``audio_feature`` and through it
+    ``smoothed_audio_feature``, ``expr_feature``), and the camera.  -> (conds, cameras [n, 3, 4] on the host, H, W)."""
+    dev = next(network.parameters()).device
+    sq = lambda t: torch.squeeze(torch.as_tensor(t)).to(device=dev, dtype=torch.float32)
+    conds, cameras, size = [], [], None
+    was_training = network.training
+    network.eval()
+    try:
+        with torch.no_grad():
+            for data in items:
+                data = _forward_tuple(data, latent_code, model)
+                baseline = model == "baseline"
+                auds, raw_img, pose, index = data[3], torch.as_tensor(data[4]), data[5], data[-1]
+                aud = network.audio_feature(sq(auds), int(index), global_step, dataset_size)
+                expr = None if baseline else network.expr_feature(sq(data[6]))
+                latent = None if baseline else torch.squeeze(torch.as_tensor(data[7])).to(dev)
+                conds.append((aud, expr, latent))
+                cameras.append(torch.squeeze(torch.as_tensor(pose)).detach().to(device="cpu", dtype=torch.float32)[:3, :4])
+                # (the frame size as the class's forward reads it off raw_img)
+                size = tuple(torch.squeeze(raw_img).shape[:2]) if baseline else (raw_img.shape[1], raw_img.shape[1])
+    finally:
+        network.train(was_training)
+    return conds, torch.stack(cameras), int(size[0]), int(size[1])
+
+
+def torso_cull_conditioning(network, poses, auds, expr, latent_code, frames):
+    """What the two cull grids of the head + torso flow are built from: for the clip's `frames`, the head pair's
+    (aud_smo[j], expr row, latent_code) and the torso pair's (torso_signal(aud_smo[j], poses[j]), None, None) -- the tensors
+    ``_torso_pairs`` passes, made by the functions it calls (``clip_audio_features``, ``torso_signal``).
+    -> (head_conds, torso_conds, head cameras [n, 3, 4] on the host)."""
+    device = next(network.parameters()).device
+    f32 = lambda t: torch.as_tensor(t).to(device=device, dtype=torch.float32)
+    poses_host = torch.as_tensor(poses).detach().to(device="cpu", dtype=torch.float32)
+    poses_dev, latent_code = f32(poses), f32(latent_code)
+    expr = None if expr is None else f32(expr)
+    per_frame = expr is not None and expr.dim() == 2
+    with torch.no_grad():
+        aud_smo = clip_audio_features(network.aud_net, network.aud_att_net, f32(auds), network.args.smo_size)
+        head = [(aud_smo[j], expr[j] if per_frame else expr, latent_code) for j in frames]
+        torso = [(network.torso_signal(aud_smo[j], poses_dev[j]), None, None) for j in frames]
+    return head, torso, torch.stack([poses_host[j][:3, :4] for j in frames])
+
+
+@contextlib.contextmanager
+def _culled(network, cull, build):
+    """cull is None: nothing happens (the network is not touched).  Else `build(options)` -> dict(head=, torso=) of grids is
+    run before the first frame, the grids are installed for the body and removed whatever happens in it."""
+    if cull is None:
+        yield None
+        return
+    from . import cull as cull_mod
+    grids = build(cull_mod.options(cull))
+    network.set_cull(**grids)
+    try:
+        yield grids
+    finally:
+        network.set_cull(head=None, torso=None)
+
+
+def _with_cull_summary(done, grids):
+    if done is not None and grids is not None:
+        from . import cull as cull_mod
+        done = dict(done, cull=cull_mod.summary(grids))
+    return done
+
+
+def _head_grid(network, items, global_step, dataset_size, latent_code, model, opts):
+    from . import cull as cull_mod
+    conds, cameras, H, W = head_cull_conditioning(network, items, global_step, dataset_size, latent_code, model)
+    nets = (network.face_nerf_coarse, network.face_nerf_fine) if network.N_importance > 0 else (network.face_nerf_coarse,)
+    return dict(head=cull_mod.build_grid(nets, conds, cameras, H, W, network.focal, network.near, network.far, **opts))
+
+
+def _torso_grids(network, poses, auds, bc_img, expr, latent_code, torso_pose, frames, opts):
+    from . import cull as cull_mod
+    head_c, torso_c, cameras = torso_cull_conditioning(network, poses, auds, expr, latent_code, frames)
+    H, W = int(bc_img.shape[0]), int(bc_img.shape[1])
+    fine = network.N_importance > 0
+    kw = dict(H=H, W=W, focal=network.focal, near=network.near, far=network.far, **opts)
+    torso_cam = torch.as_tensor(torso_pose).detach().to(device="cpu", dtype=torch.float32)[:3, :4]
+    return dict(head=cull_mod.build_grid((network.face_nerf_coarse, network.face_nerf_fine) if fine else (network.face_nerf_coarse,),
+                                         head_c, cameras, **kw),
+                torso=cull_mod.build_grid((network.torso_coarse_nerf, network.torso_fine_nerf) if fine else (network.torso_coarse_nerf,),
+                                          torso_c, torso_cam[None], **kw))
+
+
 def render_head_clip(network, dataset, path, global_step, *, latent_code, frames=None, seed=None, fps=25, codec="MJPG",
-                     swap_rb=False, still_every=0, still_path=None, group=None, model="head", stills_as_rgb=False):
+                     swap_rb=False, still_every=0, still_path=None, group=None, model="head", stills_as_rgb=False, cull=None):
     """The head-only eval loop: every frame of ``frames`` (default: the whole ``dataset``, a ``dataset.GetData`` in
     val mode) through ``network([data, global_step, dataset.data_size])`` in eval mode under no_grad, converted on
     the device and written to the AVI at ``path`` in order; ``still_path="dir/name_{i}.jpg"`` with
@@ -107,6 +196,10 @@ def render_head_clip(network, dataset, path, global_step, *, latent_code, frames
     ``stills_as_rgb``: the stills are written the way ``imageio.imwrite`` writes the frame's bytes -- taken as RGB, quality 75
     -- where the sink writes them as cv2 does (taken as BGR, quality 95): test_nerf.py:184-189 hands ONE array to both
     writers.  Each still is then written by the rank that rendered the frame.
+    ``cull``: None, or ``dict(G=, dilate=, sigma_min=, frame_stride=)`` (any subset; cull.DEFAULTS) -- before the first frame every
+    rank builds the head pair's occupancy grid from the WHOLE clip (it reads every frame's item once more for it), installs
+    it (``network.set_cull``) and removes it at the end; the result gains ``cull = dict(build_seconds, network_seconds,
+    occupied_share, live_share)``.
 
     Returns on rank 0 ``dict(n_frames, nonfinite_frames, seconds, frames_per_s, world)`` (seconds: first render to
     the file being closed), None on the other ranks.  A frame with a NaN/Inf is reported, not fatal."""
@@ -129,8 +222,11 @@ def render_head_clip(network, dataset, path, global_step, *, latent_code, frames
 
     if stills_as_rgb and still_every and not still_path:
         raise ValueError("still_every needs still_path")
-    return _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, 0 if stills_as_rgb else still_every, still_path,
-                None)
+    whole_clip = lambda: iter(DataLoader(Subset(dataset, frames), batch_size=1, shuffle=False, num_workers=0))
+    with _culled(network, cull, lambda o: _head_grid(network, whole_clip(), global_step, dataset.data_size, latent_code, model, o)) as grids:
+        done = _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, 0 if stills_as_rgb else still_every,
+                    still_path, None)
+    return _with_cull_summary(done, grids)
 
 
 def _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose):
@@ -167,7 +263,7 @@ def _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose):
 
 
 def render_torso_clip(network, poses, auds, bc_img, path, *, expr, latent_code, torso_pose, aud_ids=None, frames=None,
-                      seed=None, fps=25, codec="MJPG", swap_rb=False, still_every=0, still_path=None, group=None):
+                      seed=None, fps=25, codec="MJPG", swap_rb=False, still_every=0, still_path=None, group=None, cull=None):
     """The head + torso clip loop for a ``train_torso.Network``.  poses [F, >=3, 4], auds [F, 16, 29] (the clip's
     DeepSpeech windows), bc_img [H, W, 3] in [0, 1], torso_pose [>=3, 4] (the fixed camera of the torso pair).  expr: one
     expression vector for the whole clip, or a track [F, E] -- row j goes to frame j of the clip, whatever ``frames`` selects
@@ -183,7 +279,9 @@ def render_torso_clip(network, poses, auds, bc_img, path, *, expr, latent_code, 
 
     ``still_path`` is a directory here: with ``still_every=10`` it receives ``{aud_id}.jpg`` and
     ``{aud_id}_torso.jpg`` of every 10th frame (:526-531; aud_ids defaults to the frame numbers).  The reference
-    writes ``rgb8[:, :, ::-1]`` to its cv2 writer, which is ``swap_rb=True`` here.  Returns as render_head_clip."""
+    writes ``rgb8[:, :, ::-1]`` to its cv2 writer, which is ``swap_rb=True`` here.  Returns as render_head_clip.
+    ``cull`` as there: one grid per pair, each from the whole clip's conditioning; the torso pair's camera is the one
+    ``torso_pose``, so its pixels are classified once per clip."""
     device = next(network.parameters()).device
     n_clip = int(poses.shape[0])
     frames = list(range(n_clip) if frames is None else frames)
@@ -202,8 +300,10 @@ def render_torso_clip(network, poses, auds, bc_img, path, *, expr, latent_code, 
         return out, flag
 
     names = os.path.join(still_path, "{i}.jpg") if still_every and still_path else None
-    return _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, still_every, names,
-                [aud_ids[j] for j in frames])
+    with _culled(network, cull, lambda o: _torso_grids(network, poses, auds, bc_img, expr, latent_code, torso_pose, frames, o)) as grids:
+        done = _run(frames, render_one, network, path, group, seed, fps, codec, swap_rb, still_every, names,
+                    [aud_ids[j] for j in frames])
+    return _with_cull_summary(done, grids)
 
 
 def summarise_clip(table):
@@ -248,7 +348,7 @@ def _score(frames, score_one, network, path, group, seed, fps, codec, swap_rb, d
 
 
 def score_head_clip(network, frames, global_step, *, latent_code, frame_ids=None, path=None, seed=None, group=None, fps=25,
-                    codec="MJPG", swap_rb=False, model="head"):
+                    codec="MJPG", swap_rb=False, model="head", cull=None):
     """``render_head_clip`` with the ground truth beside it.  ``frames`` is a val-mode ``dataset.ResidentFrames``: frame j of
     ``frame_ids`` (default: all of them) comes from ``frames.frame(j)`` -- no file read, no host meshgrid -- goes through
     ``network([data, global_step, frames.data_size])`` in eval mode under no_grad (the caller's mode is restored), and the float
@@ -266,7 +366,7 @@ def score_head_clip(network, frames, global_step, *, latent_code, frame_ids=None
     seconds, frames_per_s, world)``: ``table`` float64 [n, 5, 4] on the host (rows ops.SCORE_GROUPS, columns
     ops.SCORE_COLUMNS), per_frame / mean / pooled as ``summarise_clip``; nonfinite_frames: POSITIONS in the clip whose render
     holds a NaN/Inf (their sums are not finite, so ``mean`` counts them in n_excluded); seconds: first render to the table
-    on the host."""
+    on the host.  ``cull`` as ``render_head_clip``."""
     device = next(network.parameters()).device
     ids = list(range(frames.data_size) if frame_ids is None else frame_ids)
     ws = torch.empty(ops.frame_scores_workspace_doubles(frames.H, frames.W), dtype=torch.float64, device=device)
@@ -280,18 +380,21 @@ def score_head_clip(network, frames, global_step, *, latent_code, frame_ids=None
         flag = torch.zeros(1, dtype=torch.int32, device=device)
         return ops.to8b(rgb, swap_rb, flag), flag
 
-    return _score(ids, score_one, network, path, group, seed, fps, codec, swap_rb, device)
+    items = lambda: (frames.frame(j) for j in ids)
+    with _culled(network, cull, lambda o: _head_grid(network, items(), global_step, frames.data_size, latent_code, model, o)) as grids:
+        done = _score(ids, score_one, network, path, group, seed, fps, codec, swap_rb, device)
+    return _with_cull_summary(done, grids)
 
 
 def score_torso_clip(network, poses, auds, bc_img, truth, *, regions=None, expr, latent_code, torso_pose, frames=None,
-                     path=None, seed=None, group=None, fps=25, codec="MJPG", swap_rb=False):
+                     path=None, seed=None, group=None, fps=25, codec="MJPG", swap_rb=False, cull=None):
     """``render_torso_clip`` with the ground truth beside it: truth uint8 [F, H, W, 3] and (optionally) regions uint8 [F, H, W]
     (``dataset.region_byte_map``) on the device, indexed like poses; expr as there (one vector, or a track [F, E] indexed by
     the clip's frame number).  Per frame the same two render pairs; what is scored is
     the FLOAT composite ``rgb * last_weight[..., None] + rgb_fg`` -- a torch expression with one frame-sized temporary, since
     the fused tail (``ops.compose_to8b``) keeps the composite in registers and hands out bytes only; with ``path`` the clip's
     bytes still come from that fused tail, so the file is ``render_torso_clip``'s.  Everything else, and the return value, as
-    ``score_head_clip``."""
+    ``score_head_clip``; ``cull`` as ``render_torso_clip``."""
     device = next(network.parameters()).device
     ids = list(range(int(poses.shape[0])) if frames is None else frames)
     pairs = _torso_pairs(network, poses, auds, bc_img, expr, latent_code, torso_pose)
@@ -305,4 +408,6 @@ def score_torso_clip(network, poses, auds, bc_img, truth, *, regions=None, expr,
         flag = torch.zeros(1, dtype=torch.int32, device=device)
         return ops.compose_to8b(rgb, last_w, rgb_fg, swap_rb, flag), flag
 
-    return _score(ids, score_one, network, path, group, seed, fps, codec, swap_rb, device)
+    with _culled(network, cull, lambda o: _torso_grids(network, poses, auds, bc_img, expr, latent_code, torso_pose, ids, o)) as grids:
+        done = _score(ids, score_one, network, path, group, seed, fps, codec, swap_rb, device)
+    return _with_cull_summary(done, grids)

@@ -719,4 +719,77 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, const i
     return IDN_OK;
 }
 
+// ---- ray cull (cull.hip) -----------------------------------------------------------------
+static int check_cull_G(int G) {
+    if (G < 32 || G > 1024 || G % 32) return fail(IDN_EINVAL, "G = %d: the grid edge is a multiple of 32 in 32..1024", G);
+    return IDN_OK;
+}
+static int check_cull_frame(const idn_frame* f) {
+    if (!f) return fail(IDN_EINVAL, "frame is NULL");
+    if (f->H <= 0 || f->W <= 0 || f->row0 < 0 || f->nrows < 0 || f->row0 + f->nrows > f->H) return fail(IDN_EINVAL, "bad frame/rows");
+    if ((int64_t)f->nrows * f->W > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "more than 2^31-1 pixels in one band");
+    return IDN_OK;
+}
+
+int idealnerf_cull_mark(const float* raw, int64_t n, float sigma_min, uint8_t* corners, void* stream) {
+    if (n < 0) return fail(IDN_EINVAL, "n < 0");
+    if (n == 0) return IDN_OK;
+    if (!raw || !corners) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_cull_mark(raw, n, sigma_min, corners, (hipStream_t)stream);
+}
+
+int idealnerf_cull_cells(const uint8_t* corners, int G, int dilate, uint32_t* bits, void* stream) {
+    if (int e = check_cull_G(G)) return e;
+    if (dilate < 0) return fail(IDN_EINVAL, "dilate %d < 0", dilate);
+    if (!corners || !bits) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_cull_cells(corners, G, dilate > G ? G : dilate, bits, (hipStream_t)stream);
+}
+
+size_t idealnerf_cull_classify_workspace_bytes(int64_t n_pixels) { return n_pixels > 0 ? cull_classify_workspace_bytes(n_pixels) : 0; }
+
+int idealnerf_cull_classify(const idn_cull_grid* grid, const idn_frame* frame, float dz, int K, int64_t* sel, int32_t* n_live,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!grid) return fail(IDN_EINVAL, "grid is NULL");
+    if (int e = check_cull_G(grid->G)) return e;
+    if (int e = check_cull_frame(frame)) return e;
+    if (!(grid->cell > 0.0f)) return fail(IDN_EINVAL, "cell must be positive");
+    if (!(dz > 0.0f) || K < 1 || K > (1 << 20)) return fail(IDN_EINVAL, "march of K = %d steps of dz = %g (K in 1..2^20, dz > 0)", K, (double)dz);
+    if (!grid->bits || !n_live) return fail(IDN_EINVAL, "NULL pointer");
+    const int64_t npix = (int64_t)frame->nrows * frame->W;
+    if (npix == 0) {
+        IDN_HIP_CHECK(hipMemsetAsync(n_live, 0, sizeof(int32_t), (hipStream_t)stream));
+        return IDN_OK;
+    }
+    if (!sel || !workspace) return fail(IDN_EINVAL, "NULL pointer");
+    if (workspace_bytes < cull_classify_workspace_bytes(npix))
+        return fail(IDN_EWORKSPACE, "workspace of %zu bytes, the classification of %lld pixels needs %zu", workspace_bytes, (long long)npix,
+                    cull_classify_workspace_bytes(npix));
+    return launch_cull_classify(*grid, *frame, dz, K, (long long*)sel, n_live, workspace, (hipStream_t)stream);
+}
+
+int idealnerf_cull_gather(const int64_t* sel, int64_t n, const idn_frame* frame, const float* bc, float* rays, float* bc_live,
+                          void* stream) {
+    if (int e = check_cull_frame(frame)) return e;
+    if (n < 0 || n > (int64_t)frame->nrows * frame->W) return fail(IDN_EINVAL, "n = %lld is not in 0..nrows W", (long long)n);
+    if (n == 0) return IDN_OK;
+    if (!sel || !bc || !rays || !bc_live) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_cull_gather((const long long*)sel, n, *frame, bc, rays, bc_live, (hipStream_t)stream);
+}
+
+int idealnerf_cull_scatter(const int64_t* sel, int64_t n_live, int64_t n_pixels, const float* bc, const idn_cull_output* outputs,
+                           int n_outputs, void* stream) {
+    if (n_pixels < 0 || n_live < 0 || n_live > n_pixels) return fail(IDN_EINVAL, "bad sizes n_live=%lld n_pixels=%lld", (long long)n_live, (long long)n_pixels);
+    if (n_outputs < 0 || n_outputs > IDN_CULL_MAX_OUTPUTS) return fail(IDN_EINVAL, "n_outputs %d outside 0..%d", n_outputs, IDN_CULL_MAX_OUTPUTS);
+    if (n_outputs > 0 && !outputs) return fail(IDN_EINVAL, "NULL pointer");
+    for (int k = 0; k < n_outputs; ++k) {
+        const idn_cull_output& o = outputs[k];
+        if (o.channels != 1 && o.channels != 3) return fail(IDN_EINVAL, "output %d: channels %d (1 or 3)", k, o.channels);
+        if (o.fill_background && (o.channels != 3 || !bc)) return fail(IDN_EINVAL, "output %d: the background fill needs 3 channels and bc", k);
+        if (!o.dense || (n_live > 0 && !o.live)) return fail(IDN_EINVAL, "output %d: NULL pointer", k);
+    }
+    if (n_live > 0 && !sel) return fail(IDN_EINVAL, "NULL pointer");
+    if (n_pixels == 0 || n_outputs == 0) return IDN_OK;
+    return launch_cull_scatter((const long long*)sel, n_live, n_pixels, bc, outputs, n_outputs, (hipStream_t)stream);
+}
+
 }  // extern "C"

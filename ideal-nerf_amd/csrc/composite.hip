@@ -12,35 +12,11 @@ namespace idn {
 // ---------------------------------------------------------------------------
 // a1: get_rays + record assembly (helper.py:228-243, audio_exp_nerf.py:396-427)
 // ---------------------------------------------------------------------------
-struct C2W {
-    float m[12];
-};
 __global__ void frame_rays_kernel(C2W c, int W, float focal, float cx, float cy, float near_, float far_, long pix0,
                                   int npix, float* out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= npix) return;
-    const long pix = pix0 + idx;      // row-major pixel index in the frame
-    const int row = (int)(pix / W), col = (int)(pix % W);
-    const float i = (float)col, j = (float)row;
-    const float d0 = (i - cx) / focal;
-    const float d1 = -(j - cy) / focal;
-    const float d2 = -1.0f;
-    float d[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) d[r] = (d0 * c.m[4 * r + 0] + d1 * c.m[4 * r + 1]) + d2 * c.m[4 * r + 2];
-    const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    float* o = out + (long)idx * IDN_RAY_FLOATS;
-    o[0] = c.m[3];
-    o[1] = c.m[7];
-    o[2] = c.m[11];
-    o[3] = d[0];
-    o[4] = d[1];
-    o[5] = d[2];
-    o[6] = near_;
-    o[7] = far_;
-    o[8] = d[0] / nrm;
-    o[9] = d[1] / nrm;
-    o[10] = d[2] / nrm;
+    frame_ray_record(c, W, focal, cx, cy, near_, far_, pix0 + idx, out + (long)idx * IDN_RAY_FLOATS);
 }
 
 int launch_frame_rays(const float* c2w_host, int H, int W, float focal, float cx, float cy, float near_, float far_,

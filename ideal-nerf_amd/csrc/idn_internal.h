@@ -261,6 +261,16 @@ int launch_gather_rays(const long long* sel, int64_t n, const float* c2w_host, c
                        float cx, float cy, const unsigned char* image, const unsigned char* background, const float* target_table,
                        const float* background_table, float* batch_rays, float* batch_rays2, float* target_s, float* bc_rgb,
                        hipStream_t s);
+// cull.hip: occupancy grid (mark, cells) and the per-frame ray cull (classify + compact, gather, fill + scatter)
+int launch_cull_mark(const float* raw, int64_t n, float sigma_min, unsigned char* corners, hipStream_t s);
+int launch_cull_cells(const unsigned char* corners, int G, int dilate, unsigned* bits, hipStream_t s);
+size_t cull_classify_workspace_bytes(int64_t npix);
+int launch_cull_classify(const idn_cull_grid& grid, const idn_frame& frame, float dz, int K, long long* sel, int* n_live, void* ws,
+                         hipStream_t s);
+int launch_cull_gather(const long long* sel, int64_t n, const idn_frame& frame, const float* bc, float* rays, float* bc_live,
+                       hipStream_t s);
+int launch_cull_scatter(const long long* sel, int64_t n_live, int64_t npix, const float* bc, const idn_cull_output* outs, int n_outs,
+                        hipStream_t s);
 // metrics.hip: squared error and SSIM of a frame against its uint8 ground truth, whole frame and per region -> out [5, 4] fp64
 size_t frame_scores_workspace_bytes(int H, int W);
 int launch_frame_scores(const float* pred, const unsigned char* truth, const unsigned char* regions, int H, int W, double* out,

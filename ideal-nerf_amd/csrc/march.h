@@ -35,6 +35,39 @@ __device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigne
 __device__ __forceinline__ float draw_t_rand(const Draws& d, long ray, int s) { return philox_uniform(d.seed, 2ull * (unsigned long long)(d.ray0 + ray), (unsigned)s); }
 __device__ __forceinline__ float draw_u(const Draws& d, long ray, int j) { return philox_uniform(d.seed, 2ull * (unsigned long long)(d.ray0 + ray) + 1ull, (unsigned)j); }
 
+// a1: get_rays + record assembly (helper.py:228-243, audio_exp_nerf.py:396-427) of ONE pixel: the direction of pixel `pix`
+// (row-major index in the frame) and its [o, d, near, far, viewdir] record.  The one statement of this arithmetic: the frame's
+// ray kernel (composite.hip) and the ray cull (cull.hip) both call it, so their rows agree bit for bit.
+struct C2W {
+    float m[12];
+};
+__device__ __forceinline__ void frame_ray_dir(const C2W& c, int W, float focal, float cx, float cy, long pix, float (&d)[3]) {
+    const int row = (int)(pix / W), col = (int)(pix % W);
+    const float i = (float)col, j = (float)row;
+    const float d0 = (i - cx) / focal;
+    const float d1 = -(j - cy) / focal;
+    const float d2 = -1.0f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) d[r] = (d0 * c.m[4 * r + 0] + d1 * c.m[4 * r + 1]) + d2 * c.m[4 * r + 2];
+}
+__device__ __forceinline__ void frame_ray_record(const C2W& c, int W, float focal, float cx, float cy, float near_, float far_,
+                                                 long pix, float* o) {
+    float d[3];
+    frame_ray_dir(c, W, focal, cx, cy, pix, d);
+    const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    o[0] = c.m[3];
+    o[1] = c.m[7];
+    o[2] = c.m[11];
+    o[3] = d[0];
+    o[4] = d[1];
+    o[5] = d[2];
+    o[6] = near_;
+    o[7] = far_;
+    o[8] = d[0] / nrm;
+    o[9] = d[1] / nrm;
+    o[10] = d[2] / nrm;
+}
+
 __device__ __forceinline__ double shfl_up_d(double v, int delta) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __shfl_up(lo, delta, 64);

@@ -41,7 +41,7 @@ def _learned_background(frames, path, device):
 
 
 def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", still_every=10, seed=None, group=None,
-               precision=None, model="head", learned_background=False):
+               precision=None, model="head", learned_background=False, cull=None):
     """The eval script's ``eval()`` on the flags ``args`` (``helper.config_parser().parse_args()``): ``DrivingFrames(args.datadir,
     args.aud_file, "val", args, skip=args.testskip)``, a ``Network`` with ``to_render_config(args)`` and the loader's focal
     length, the checkpoint ``args.ft_path`` -- else the newest ``*.tar`` of ``basedir/expname`` --, read whole and without
@@ -55,6 +55,7 @@ def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", st
     (``agg_aud_exp_nerf.Network``; its newest ``{epoch:06d}_head.tar``).  ValueError where the network's expression width --
     ``args.dim_expr``, the agg pair's 79 -- is not the expression track's.  ``learned_background``: render over the
     checkpoint's ``background`` instead of ``bc.jpg`` (it raises if the checkpoint holds none); off: nothing changes.
+    ``cull``: ``render_head_clip``'s (None, or the occupancy grid's options: empty rays are not rendered).
     -> ``render_head_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
     from .agg_aud_exp_nerf import DIM_EXPR, build_head_network
     frames = dataset.DrivingFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device)
@@ -80,7 +81,7 @@ def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", st
     for d in {os.path.dirname(os.path.abspath(p)) for p in (out, stills) if p}:
         os.makedirs(d, exist_ok=True)
     res = clip.render_head_clip(network, frames, out, global_step, latent_code=latent_code, seed=seed, codec=codec,
-                                still_every=still_every, still_path=stills, group=group)
+                                still_every=still_every, still_path=stills, group=group, **({} if cull is None else dict(cull=cull)))
     return None if res is None else dict(res, path=out)
 
 
@@ -95,7 +96,7 @@ def head_expr_width(run_dir, input_ch_views=27):
     return int(state["face_nerf_coarse.views_linears.0.weight"].shape[1]) - input_ch_views - 256
 
 
-def drive_torso(args, *, out=None, device="cuda", codec="MJPG", still_every=10, seed=None, group=None, precision=None):
+def drive_torso(args, *, out=None, device="cuda", codec="MJPG", still_every=10, seed=None, group=None, precision=None, cull=None):
     """``test_torso.py --with_test`` on the flags ``args`` (``train_torso.config_parser().parse_args()``): the track of
     ``dataset.load_test_data(args.datadir, args.aud_file, args.test_pose_file, args.testskip, args.test_size, args.aud_start)``,
     a ``train_torso.Network`` whose head pair has the expression width of the run directory's head checkpoint
@@ -105,7 +106,8 @@ def drive_torso(args, *, out=None, device="cuda", codec="MJPG", still_every=10, 
 
     Where the head pair takes an expression, frame j gets row j of ``dataset.load_test_exprs(args.evalExpr_path or
     args.test_pose_file, args.testskip, F)`` (ValueError where its width is not the head pair's); a head pair without
-    expression columns gets none.  -> ``render_torso_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
+    expression columns gets none.  ``cull``: ``render_torso_clip``'s.  -> ``render_torso_clip``'s dict plus ``path`` on rank 0,
+    None on the other ranks."""
     from .train_torso import Network, load_stage_checkpoints
     poses, auds, bc_img, (H, W, focal, _, _), aud_ids, torso_pose = dataset.load_test_data(
         args.datadir, args.aud_file, args.test_pose_file, args.testskip, args.test_size, args.aud_start)
@@ -131,7 +133,7 @@ def drive_torso(args, *, out=None, device="cuda", codec="MJPG", still_every=10, 
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     res = clip.render_torso_clip(network, poses, auds, bc_img / 255, out, expr=track, latent_code=codes[0], torso_pose=torso_pose,
                                  aud_ids=aud_ids, seed=seed, codec=codec, swap_rb=True, still_every=still_every,
-                                 still_path=args.save_path, group=group)
+                                 still_path=args.save_path, group=group, **({} if cull is None else dict(cull=cull)))
     return None if res is None else dict(res, path=out)
 
 
@@ -142,7 +144,7 @@ def baseline_names(args):
 
 
 def drive_baseline(args, *, out=None, device="cuda", codec="MJPG", still_every=10, seed=None, group=None, precision=None,
-                   learned_background=False):
+                   learned_background=False, cull=None):
     """The baseline tester's ``test()`` (NeRFs/HeadNeRF/test/test_nerf.py:140-190) on the flags ``args``
     (``helper.config_parser().parse_args()``): ``BaselineTestFrames(args.datadir, args.aud_file, "val", args,
     skip=args.testskip)`` -- the val poses, frame i with audio row i --, a ``head_baseline.Network`` with
@@ -155,7 +157,7 @@ def drive_baseline(args, *, out=None, device="cuda", codec="MJPG", still_every=1
     ``still_every``-th frame is also written there as ``{datadir[8:]}_{aud_file[:-4]}_ADNeRF_{i}.jpg``.  Channels as upstream
     (:184-189): the red/blue-swapped bytes go to BOTH writers, the clip's (which takes them as BGR) and the stills' (which
     takes them as RGB).  Frame-parallel inside a process group like ``drive_head``.  ``learned_background``: as ``drive_head``
-    (the run file of ``train_baseline.train(learn_background=True)``; an AD-NeRF ``ft_path`` holds none).
+    (the run file of ``train_baseline.train(learn_background=True)``; an AD-NeRF ``ft_path`` holds none).  ``cull``: as ``drive_head``.
     -> ``render_head_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
     from .agg_aud_exp_nerf import build_head_network
     frames = dataset.BaselineTestFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device)
@@ -177,5 +179,6 @@ def drive_baseline(args, *, out=None, device="cuda", codec="MJPG", still_every=1
     for d in {os.path.dirname(os.path.abspath(p)) for p in (out, stills) if p}:
         os.makedirs(d, exist_ok=True)
     res = clip.render_head_clip(network, frames, out, 0, latent_code=None, seed=seed, codec=codec, swap_rb=True,
-                                still_every=still_every, still_path=stills, group=group, model="baseline", stills_as_rgb=True)
+                                still_every=still_every, still_path=stills, group=group, model="baseline", stills_as_rgb=True,
+                                **({} if cull is None else dict(cull=cull)))
     return None if res is None else dict(res, path=out)

@@ -1070,3 +1070,127 @@ def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals
             if tap_rays is not None:
                 out["tap_rays"] = tap_rays
     return out
+
+
+# ---- ray cull (csrc/cull.hip; cull.py builds and uses the grid) ----------------------------------------------------------
+def _cull_G(G):
+    if isinstance(G, bool) or not isinstance(G, int) or G < 32 or G > 1024 or G % 32:
+        raise IdealNerfError(f"G = {G!r}: the grid edge is a multiple of 32 in 32..1024")
+    return G
+
+
+def cull_mark(raw, sigma_min, corners) -> torch.Tensor:
+    """corners[i] |= raw[i, 3] > sigma_min (idealnerf_cull_mark): raw [n, 4] fp32, corners uint8 [n], updated in place."""
+    lib = _lib.load()
+    _shape(raw, "raw", None, 4)
+    n = raw.shape[0]
+    _shape(corners, "corners", n)
+    with _Launch(raw, corners) as L:
+        check(lib.idealnerf_cull_mark(_ptr(raw, "raw"), n, float(sigma_min), _ptr(corners, "corners", torch.uint8), L.stream))
+    return corners
+
+
+def cull_cells(corners, G, dilate) -> torch.Tensor:
+    """Marked lattice corners uint8 [(G+1)^3] -> cell bits int32 [G^3 / 32], 32 cells per word along x (idealnerf_cull_cells):
+    a cell is set when a corner of a cell within `dilate` cells of it (Chebyshev) is marked."""
+    lib = _lib.load()
+    G = _cull_G(G)
+    if isinstance(dilate, bool) or not isinstance(dilate, int) or dilate < 0:
+        raise IdealNerfError(f"dilate = {dilate!r}: a whole number of cells >= 0")
+    _shape(corners, "corners", (G + 1) ** 3)
+    with _Launch(corners) as L:
+        ptr = _ptr(corners, "corners", torch.uint8)
+        bits = torch.empty(G ** 3 // 32, dtype=torch.int32, device=corners.device)
+        check(lib.idealnerf_cull_cells(ptr, G, dilate, bits.data_ptr(), L.stream))
+    return bits
+
+
+def _cull_grid_struct(bits, G, lo, cell):
+    G = _cull_G(G)
+    _shape(bits, "bits", G ** 3 // 32)
+    if not float(cell) > 0.0:
+        raise IdealNerfError(f"cell = {cell!r} must be positive")
+    g = _lib.CullGridStruct()
+    g.bits, g.G, g.cell = _ptr(bits, "bits", torch.int32), G, float(cell)
+    g.lo = (C.c_float * 3)(*[float(v) for v in lo])
+    return g
+
+
+def cull_classify(bits, G, lo, cell, frame, dz, K, sel=None, n_live=None):
+    """The live pixels of the frame's row band (idealnerf_cull_classify): -> (sel int64 [nrows W], n_live int32 [1]), both on
+    the device; sel[:n_live] holds the live pixels (row-major in the band) in ascending order, the rest is not written.
+    dz, K: the march z_k = near + k dz, k < K, z_K = far (`cull.march_steps` chooses them)."""
+    lib = _lib.load()
+    npix = frame.nrows * frame.W
+    _shape(sel, "sel", npix)
+    _shape(n_live, "n_live", 1)
+    if not float(dz) > 0.0 or int(K) < 1 or int(K) > 1 << 20:
+        raise IdealNerfError(f"a march of K = {K} steps of dz = {dz} (K in 1..2^20, dz > 0)")
+    with _Launch(bits, sel, n_live) as L:
+        g = _cull_grid_struct(bits, G, lo, cell)
+        if sel is None:
+            sel = torch.empty(npix, dtype=torch.int64, device=bits.device)
+        if n_live is None:
+            n_live = torch.empty(1, dtype=torch.int32, device=bits.device)
+        ws = _workspace(lib.idealnerf_cull_classify_workspace_bytes(npix), bits.device, L.stream or 0)
+        check(lib.idealnerf_cull_classify(C.byref(g), C.byref(frame), float(dz), int(K), _ptr(sel, "sel", torch.int64),
+                                          _ptr(n_live, "n_live", torch.int32), ws.data_ptr(), ws.numel(), L.stream))
+    return sel, n_live
+
+
+def cull_gather(sel, frame, bc_rgb):
+    """(rays [n, 11], bc_live [n, 3]) of the band's pixels `sel` (int64 [n]): each ray row is the row `frame_rays` writes for
+    that pixel, bit for bit (idealnerf_cull_gather).  bc_rgb [nrows W, 3]: the band's background."""
+    lib = _lib.load()
+    _shape(sel, "sel", None)
+    n, npix = sel.shape[0], frame.nrows * frame.W
+    _shape(bc_rgb, "bc_rgb", npix, 3)
+    if n > npix:
+        raise IdealNerfError(f"sel holds {n} pixels, the band has {npix}")
+    with _Launch(sel, bc_rgb) as L:
+        ptrs = (_ptr(sel, "sel", torch.int64), _ptr(bc_rgb, "bc_rgb"))
+        rays = torch.empty((n, RAY_FLOATS), dtype=torch.float32, device=sel.device)
+        bc_live = torch.empty((n, 3), dtype=torch.float32, device=sel.device)
+        check(lib.idealnerf_cull_gather(ptrs[0], n, C.byref(frame), ptrs[1], rays.data_ptr(), bc_live.data_ptr(), L.stream))
+    return rays, bc_live
+
+
+def cull_scatter(sel, n_live, bc_rgb, outputs) -> Dict[str, torch.Tensor]:
+    """fill + scatter (idealnerf_cull_scatter).  outputs: name -> (live [n_live, ...] or None when n_live == 0, channels, fill)
+    with fill = "bc" (the background pixel; channels 3) or a float.  -> name -> dense [n_pixels(, 3)]: the fill in every pixel,
+    row i of live at pixel sel[i]."""
+    lib = _lib.load()
+    npix, n_live = bc_rgb.shape[0], int(n_live)
+    _shape(bc_rgb, "bc_rgb", npix, 3)
+    if not 0 <= n_live <= npix or (n_live and (sel is None or sel.dim() != 1 or sel.shape[0] < n_live)):
+        raise IdealNerfError(f"n_live = {n_live} with {npix} pixels and sel {None if sel is None else list(sel.shape)}")
+    if len(outputs) > _lib.CULL_MAX_OUTPUTS:
+        raise IdealNerfError(f"{len(outputs)} outputs: one call takes {_lib.CULL_MAX_OUTPUTS}")
+    for name, (live, ch, fill) in outputs.items():
+        if ch not in (1, 3) or (fill == "bc" and ch != 3):
+            raise IdealNerfError(f"{name}: channels {ch} / fill {fill!r}")
+        if n_live:
+            _shape(live, name, *((n_live, 3) if ch == 3 else (n_live,)))
+    lives = [v[0] for v in outputs.values() if n_live]
+    with _Launch(sel, bc_rgb, *lives) as L:
+        bc_ptr, sel_ptr = _ptr(bc_rgb, "bc_rgb"), _ptr(sel, "sel", torch.int64)
+        recs = (_lib.CullOutput * max(len(outputs), 1))()
+        dense = {}
+        for r, (name, (live, ch, fill)) in zip(recs, outputs.items()):
+            dense[name] = torch.empty((npix, 3) if ch == 3 else (npix,), dtype=torch.float32, device=bc_rgb.device)
+            r.dense, r.live, r.channels = dense[name].data_ptr(), _ptr(live, name) if n_live else None, ch
+            r.fill_background, r.value = int(fill == "bc"), 0.0 if fill == "bc" else float(fill)
+        check(lib.idealnerf_cull_scatter(sel_ptr, n_live, npix, bc_ptr, recs, len(outputs), L.stream))
+    return dense
+
+
+def profile_begin():
+    """Start counting the network-kernel launches (idealnerf_profile_begin)."""
+    _lib.load().idealnerf_profile_begin()
+
+
+def profile_end():
+    """-> (total_ms, launches, points) of the network-kernel launches since `profile_begin` (idealnerf_profile_end)."""
+    ms, launches, points = C.c_double(0), C.c_int64(0), C.c_int64(0)
+    check(_lib.load().idealnerf_profile_end(C.byref(ms), C.byref(launches), C.byref(points)))
+    return ms.value, launches.value, points.value

@@ -51,6 +51,40 @@ def xavier_state_dict(module, seed, sigma_gain=None, sigma_bias=None):
     return module
 
 
+def box_density_state_dict(module, seed, centre=(0.0, 0.0, 0.0), half=0.08, slope=200.0, aud_gain=0.0):
+    """Fill a FaceNeRF with an ANALYTIC density: an axis-aligned box with empty space around it (Xavier sigma is positive in
+    about half the volume; nothing can be culled there).  The first three input channels of the point encoding are the
+    coordinates themselves, so with half_eff = half + aud_gain * aud[0]:
+      pts_linears.0      six live units relu(+-slope (x_i - c_i) - slope half_eff), i = 0..2 (coordinate weights on columns
+                         0..2, the audio weight on the first conditioning column); every other row and bias zero
+      pts_linears.1..7   carry those six channels through unchanged (pts_linears.5 takes [input | h]: column c_all + j)
+      alpha_linear       1 - the sum of the six
+    so sigma_raw = 1 inside |x_i - c_i| <= half_eff, falls with slope times the L1 excess outside, and is <= 0 from 1 / slope
+    outward.  The colour branch (views_linears.*, rgb_linear) keeps the seeded Xavier weights of `xavier_state_dict`."""
+    xavier_state_dict(module, seed)
+    sd = {k: v.clone() for k, v in module.state_dict().items()}
+    if aud_gain and not module.dim_aud:
+        raise ValueError("aud_gain needs a network with audio conditioning columns (dim_aud > 0)")
+    c_in, c_all = module.input_xyz_ch, module.pts_linears[0].in_features
+    for i in range(8):
+        sd[f"pts_linears.{i}.weight"].zero_()
+        sd[f"pts_linears.{i}.bias"].zero_()
+    for i in range(3):
+        for j, sign in ((2 * i, 1.0), (2 * i + 1, -1.0)):
+            sd["pts_linears.0.weight"][j, i] = sign * slope
+            sd["pts_linears.0.bias"][j] = -sign * slope * centre[i] - slope * half
+            if module.dim_aud:
+                sd["pts_linears.0.weight"][j, c_in] = -slope * aud_gain
+    for i in range(1, 8):
+        for j in range(6):
+            sd[f"pts_linears.{i}.weight"][j, (c_all if i == 5 else 0) + j] = 1.0
+    sd["alpha_linear.weight"].zero_()
+    sd["alpha_linear.weight"][0, :6] = -1.0
+    sd["alpha_linear.bias"].fill_(1.0)
+    module.load_state_dict(sd)
+    return module
+
+
 def write_clip_directory(d, size, n_frames, seed=0, flat=False, N_rand=64, mouth_rays=8, torso_rays=4, sample_rate=0.95,
                          dim_expr=76, face_rect=None, mouth_range=None):
     """An n_frames-frame directory in the reference's on-disk format (data_util/process_data.py:250-288), size x size: seeded

@@ -717,6 +717,57 @@ int idealnerf_to8b(const float* rgb, int64_t n_pixels, int swap_rb, uint8_t* out
 int idealnerf_compose_to8b(const float* rgb_head, const float* last_weight, const float* rgb_fg, int64_t n_pixels,
                            int swap_rb, uint8_t* out, uint8_t* fg_out, int* nonfinite_flag, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ray cull of the inference frame path (no reference counterpart).  Additive entries: the ABI
+ * version is unchanged.
+ *
+ * A ray all of whose samples have sigma_raw <= 0 renders to its background pixel exactly (alpha = 1 - expf(-1e-6 dist) is
+ * 0.0f while dist <= idealnerf_colour_gate_max_dist(); the last sample's alpha is 1 and its colour is the background).  An
+ * occupancy grid built from the networks' own sigma lets such rays be recognised before any network is evaluated.
+ *
+ * Grid: G^3 cubic cells of edge `cell` over the box lo + [0, G cell]^3, G a multiple of 32 in 32..1024.
+ *   corners  uint8 [(G+1)^3], index ((iz (G+1)) + iy) (G+1) + ix: lattice point lo + (ix, iy, iz) cell
+ *   bits     uint32 [G^3 / 32], word (z G + y) (G / 32) + (x >> 5), bit x & 31: cell (x, y, z)
+ */
+/* corners[i] |= raw[i].w > sigma_min for i < n (raw [n, 4] = a network's output for lattice points; one thread per point). */
+int idealnerf_cull_mark(const float* raw, int64_t n, float sigma_min, uint8_t* corners, void* stream);
+/* A cell is occupied when any of its 8 corners is marked; the set is dilated by `dilate` >= 0 cells in Chebyshev distance
+ * (clamped to G).  One thread computes one word of `bits`; every word is written. */
+int idealnerf_cull_cells(const uint8_t* corners, int G, int dilate, uint32_t* bits, void* stream);
+
+typedef struct idn_cull_grid {
+    const uint32_t* bits; /* device, [G^3 / 32] */
+    int G;
+    float lo[3];
+    float cell;
+} idn_cull_grid;
+/* classify + compact the pixels of the frame's row band.  Pixel q (row-major in the band) has the ray idealnerf_frame_rays
+ * derives for it (the same device function); it is marched at z_k = near + k dz, k = 0..K-1, and z_K = far, and is LIVE when a
+ * march point lies in an occupied cell or outside the box.  The caller chooses dz so that dz |d| <= cell / 2 for every ray of
+ * the frame.  sel [nrows W] int64: the live pixels in ascending order in its first *n_live entries (the rest is not
+ * written); n_live: device int32.  Count per workgroup, scan in index order, write: no atomics, the same bytes on every
+ * run.  frame->rays_out is not read. */
+size_t idealnerf_cull_classify_workspace_bytes(int64_t n_pixels);
+int idealnerf_cull_classify(const idn_cull_grid* grid, const idn_frame* frame, float dz, int K, int64_t* sel, int32_t* n_live,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* rays [n, 11] and bc_live [n, 3] of the band's pixels sel[0..n): each row of rays is the row idealnerf_frame_rays writes for
+ * that pixel, bit for bit; bc [nrows W, 3] is the band's background. */
+int idealnerf_cull_gather(const int64_t* sel, int64_t n, const idn_frame* frame, const float* bc, float* rays, float* bc_live,
+                          void* stream);
+/* fill + scatter, for up to IDN_CULL_MAX_OUTPUTS outputs at once: dense [n_pixels, channels] receives the culled value in
+ * every pixel (`value`, or with fill_background != 0 and channels == 3 the pixel of bc [n_pixels, 3]) and then row i of
+ * live [n_live, channels] at pixel sel[i].  n_live == 0: the fill alone (live may be NULL). */
+#define IDN_CULL_MAX_OUTPUTS 12
+typedef struct idn_cull_output {
+    float* dense;
+    const float* live;
+    int channels;        /* 1 or 3 */
+    int fill_background; /* 0: `value`; 1: the background pixel */
+    float value;
+} idn_cull_output;
+int idealnerf_cull_scatter(const int64_t* sel, int64_t n_live, int64_t n_pixels, const float* bc, const idn_cull_output* outputs,
+                           int n_outputs, void* stream);
+
 /*
  * Measurement aid (no reference counterpart): between begin and end, every launch of
  * the fused PE+MLP kernel is bracketed by HIP events on its own stream.  end()

@@ -60,6 +60,8 @@ def parse(argv):
     p.add_argument("--learned_background", action="store_true",
                    help="--flow head: render over the checkpoint's `background` (train_head.py --learn_background) instead of bc.jpg; "
                         "an error if the checkpoint holds none")
+    from render_clip import cull_arguments
+    cull_arguments(p)
     return p.parse_args(argv)
 
 
@@ -79,8 +81,9 @@ def main(argv=None):
     world, rank, dev, backend = init_ranks()
     try:
         from idealnerf_amd import drive
+        from render_clip import cull_option
         common = dict(out=args.out, device=dev, codec=args.codec, still_every=args.still_every, seed=args.seed,
-                      precision=args.precision)
+                      precision=args.precision, cull=cull_option(args))
         learned = dict(learned_background=True) if args.learned_background else {}
         if args.flow == "head" and args.model == "baseline":
             res = drive.drive_baseline(args, **common, **learned)

@@ -45,7 +45,30 @@ def parse():
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--global-step", type=int, default=None, help="head: default is the checkpoint's, else nosmo_iters")
     ap.add_argument("--tail-timing", action="store_true", help="HIP-event time of ops.compose_to8b against multiply + add + to8b")
+    ap.add_argument("--scene", choices=("xavier", "box"), default="xavier",
+                    help="torso: box = the analytic scene of synthetic.box_density_state_dict (a head box and a lower torso box in empty "
+                         "space; xavier density is positive in about half the volume and nothing culls there)")
+    ap.add_argument("--timing-json", default=None, help="torso: measure --cull 0 against --cull G (default 128) in this process, alternating, "
+                                                        "three rounds of warmed windows, and write the figures there")
+    cull_arguments(ap)
     return ap.parse_args()
+
+
+def cull_arguments(ap):
+    """--cull G and its three options, shared by the clip tools."""
+    ap.add_argument("--cull", type=int, default=0, metavar="G",
+                    help="skip empty rays with a per-clip occupancy grid of G^3 cells (a multiple of 32, e.g. 128); 0: off")
+    ap.add_argument("--cull-dilate", type=int, default=None, help="cells of dilation (default 1)")
+    ap.add_argument("--cull-sigma-min", type=float, default=None, help="a corner is occupied above this sigma_raw (default 0.0)")
+    ap.add_argument("--cull-stride", type=int, default=None,
+                    help="mark every k-th frame's conditioning only (default 1; k > 1 gives up the bit-exact guarantee)")
+
+
+def cull_option(args):
+    """The flows' cull= argument from the command line: None when --cull is 0."""
+    if not args.cull:
+        return None
+    return dict(G=args.cull, dilate=args.cull_dilate, sigma_min=args.cull_sigma_min, frame_stride=args.cull_stride)
 
 
 def launch(n, argv, script=None):
@@ -133,7 +156,11 @@ def torso_scene(args, dev):
     torch.manual_seed(0)   # the audio nets: every rank builds the same network
     net = Network(H, W, syn["focal"], syn["near"], syn["far"], 32768, 64, 128, args=cfg, dim_expr_head=76).to(dev).eval()
     for i, m in enumerate((net.face_nerf_coarse, net.face_nerf_fine, net.torso_coarse_nerf, net.torso_fine_nerf)):
-        synthetic.xavier_state_dict(m, 2 + i, 300.0 if i < 2 else 4.0, 0.3 if i < 2 else -0.2)
+        if args.scene == "box":   # a head box whose half-width follows the audio a little, and a torso box below it
+            synthetic.box_density_state_dict(m, 2 + i, (0.0, 0.0, 0.0) if i < 2 else (0.0, -0.17, 0.0), 0.08 if i < 2 else 0.06, 200.0,
+                                             0.002 if i < 2 else 0.0)
+        else:
+            synthetic.xavier_state_dict(m, 2 + i, 300.0 if i < 2 else 4.0, 0.3 if i < 2 else -0.2)
     idealnerf_amd.set_render_precision(net, args.precision)
     bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]])
     poses = torch.stack([torch.cat([synthetic.frame(H, W, seed=j)["c2w"], bottom], 0) for j in range(args.frames)])
@@ -144,7 +171,9 @@ def torso_scene(args, dev):
 def run_torso(args, dev):
     from idealnerf_amd import clip
     net, track, cond = torso_scene(args, dev)
-    common = dict(cond, seed=args.seed, swap_rb=args.swap_rb)
+    common = dict(cond, seed=args.seed, swap_rb=args.swap_rb, cull=cull_option(args))
+    if args.timing_json:
+        return cull_timing(args, dev, net, track, common)
     if args.warmup:   # first-launch costs (code objects, weight packing, pinned buffers) stay out of the clip's time
         clip.render_torso_clip(net, track["poses"], track["auds"], track["bc_img"], None, frames=range(args.warmup), codec="raw", **common)
     if args.still_every and args.still_path:
@@ -178,7 +207,84 @@ def run_head(args, dev):
     frames = range(min(args.frames, ds.data_size))
     return clip.render_head_clip(net, ds, args.out, step if args.global_step is None else args.global_step, latent_code=latent,
                                  frames=frames, seed=args.seed, codec=args.codec, swap_rb=args.swap_rb,
-                                 still_every=args.still_every, still_path=args.still_path)
+                                 still_every=args.still_every, still_path=args.still_path, cull=cull_option(args))
+
+
+def cull_timing(args, dev, net, track, common, rounds=3):
+    """--cull 0 against --cull G on one scene in one process: per round one window of --frames frames per arm, alternating,
+    each window warmed by --warmup frames and ended by the clip's own end (the last frame's bytes on the host).  The grid is
+    built inside each culled window (its time is reported apart and is NOT in the arm's frames/s: a clip pays it once).
+    Then, on the head pair's frame 0: the HIP-event times of classify, gather and fill + scatter, and the host cost of the
+    one n_live read."""
+    import time
+    import torch
+    from idealnerf_amd import clip, cull, ops
+    opts = cull.options(dict(cull_option(args) or {}, G=args.cull or 128))
+    poses, auds, bc = track["poses"], track["auds"], track["bc_img"]
+    base = {k: v for k, v in common.items() if k != "cull"}
+    n = args.frames
+    frames = list(range(n))
+    arms = {"cull_0": [], f"cull_{opts['G']}": []}
+    info = {}
+    for r in range(rounds):
+        for name in arms:
+            on = name != "cull_0"
+            grids = clip._torso_grids(net, poses, auds, bc, base["expr"], base["latent_code"], base["torso_pose"], frames, opts) if on else {}
+            net.set_cull(**grids)
+            try:
+                clip.render_torso_clip(net, poses, auds, bc, None, frames=range(args.warmup or 1), codec="raw", **base)
+                torch.cuda.synchronize(dev)
+                res = clip.render_torso_clip(net, poses, auds, bc, None, frames=frames, codec="raw", **base)
+            finally:
+                net.set_cull()
+            arms[name].append(res["frames_per_s"])
+            if on:
+                info = cull.summary(grids)
+                info["frames_marked"] = {k: g.stats["frames_marked"] for k, g in grids.items()}
+                info["torso_classifications"] = grids["torso"].classify_calls
+    # the pieces, on the head pair at frame 0
+    grid = clip._torso_grids(net, poses, auds, bc, base["expr"], base["latent_code"], base["torso_pose"], frames, opts)["head"]
+    H, W = int(bc.shape[0]), int(bc.shape[1])
+    frame = ops.make_frame(poses[0][:3, :4], H, W, net.focal, net.near, net.far)
+    bc_flat = bc.to(dev).reshape(-1, 3).contiguous()
+    dz, K = grid.steps(frame)
+
+    def timed(fn, reps=50):
+        for _ in range(5):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3 / reps
+
+    sel, n_dev = ops.cull_classify(grid.bits, grid.G, grid.lo, grid.cell, frame, dz, K)
+    n_live = int(n_dev.item())
+    rays, bc_live = ops.cull_gather(sel[:n_live], frame, bc_flat)
+    live3, live1 = torch.rand(n_live, 3, device=dev), torch.rand(n_live, device=dev)
+    fills = cull._fills(frame.far_)
+    outs = {k: ((live3 if fills[k][0] == 3 else live1), *fills[k]) for k in fills}
+    pieces = dict(classify_us=timed(lambda: ops.cull_classify(grid.bits, grid.G, grid.lo, grid.cell, frame, dz, K, sel, n_dev)),
+                  gather_us=timed(lambda: ops.cull_gather(sel[:n_live], frame, bc_flat)),
+                  fill_scatter_11_outputs_us=timed(lambda: ops.cull_scatter(sel, n_live, bc_flat, outs)), march_steps=K, n_live=n_live)
+    reads = []
+    for _ in range(20):   # the read alone: the classification has finished before the clock starts
+        ops.cull_classify(grid.bits, grid.G, grid.lo, grid.cell, frame, dz, K, sel, n_dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        n_dev.item()
+        reads.append((time.perf_counter() - t0) * 1e6)
+    pieces["n_live_read_idle_queue_us"] = sorted(reads)[len(reads) // 2]
+    out = dict(scene=args.scene, size=args.size, dtype=args.precision, frames_per_window=n, rounds=rounds, warmup=args.warmup or 1,
+               frames_per_s={k: dict(rounds=v, median=sorted(v)[len(v) // 2]) for k, v in arms.items()}, cull=info, pieces=pieces,
+               options=opts, device=torch.cuda.get_device_name(dev))
+    with open(args.timing_json, "w") as f:
+        json.dump(out, f, indent=1)
+    return dict(n_frames=n, nonfinite_frames=[], seconds=0.0, frames_per_s=out["frames_per_s"][f"cull_{opts['G']}"]["median"], world=1,
+                timing=out)
 
 
 def tail_timing(dev, sizes=(450, 512), reps=200):

@@ -59,6 +59,8 @@ def parse(argv):
     p.add_argument("--learned_background", action="store_true",
                    help="render over the checkpoint's `background` (train_head.py --learn_background) instead of bc.jpg; an error "
                         "without --ckpt or if the checkpoint holds none")
+    from render_clip import cull_arguments
+    cull_arguments(p)
     return p.parse_args(argv)
 
 
@@ -126,8 +128,9 @@ def score(args, dev, world):
     for prec in [p.strip() for p in args.precisions.split(",") if p.strip()]:
         idealnerf_amd.set_render_precision(net, prec)
         path = None if args.avi is None else "{0}.{2}{1}".format(*os.path.splitext(args.avi), prec)
+        from render_clip import cull_option
         res = clip.score_head_clip(net, frames, step, latent_code=latent, frame_ids=ids, path=path, seed=0 if args.perturb else None,
-                                   codec="MJPG", model=args.model)
+                                   codec="MJPG", model=args.model, cull=cull_option(args))
         if res is None:
             continue
         first = res if first is None else first
