@@ -26,21 +26,14 @@ static int check_precision_train(int precision) {
     return fail(IDN_EUNSUPPORTED, "the training path runs fp32-grade arithmetic only: IDN_PREC_F32 or IDN_PREC_BF16X6 (got %d)", precision);
 }
 
-int launch_mlp(int precision, const float* packed, const float* folded, const float* x, const float* rays,
-               const float* z, const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw,
-               hipStream_t s, int gate, int64_t* gate_counters, int pts_ch, int views_ch) {
-    if (n_points > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "n_points %lld exceeds 2^31-1 per launch", (long long)n_points);
-    if ((rays || pts) && n_samples < 1) return fail(IDN_EINVAL, "n_samples < 1");
-    if (precision == IDN_PREC_BF16X3)
-        return launch_mlp_bf16x3(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, pts_ch, views_ch);
-    if (precision == IDN_PREC_BF16)
-        return launch_mlp_bf16(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, pts_ch, views_ch);
-    if (precision == IDN_PREC_FP16X3)
-        return launch_mlp_fp16x3(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, pts_ch, views_ch);
-    if (precision == IDN_PREC_BF16X6)
-        return launch_mlp_bf16x6(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, nullptr, 0, pts_ch, views_ch);
-    return launch_mlp_f32(packed, folded, x, rays, z, pts, dirs, n_points, n_samples, raw, s, nullptr, 0, gate, gate_counters, pts_ch,
-                          views_ch);
+int launch_mlp(int precision, const MlpArgs& a, hipStream_t s, MlpGate gate) {
+    if (a.n_points > 0x7fffffffL) return fail(IDN_EUNSUPPORTED, "n_points %lld exceeds 2^31-1 per launch", (long long)a.n_points);
+    if ((a.rays || a.pts) && a.S < 1) return fail(IDN_EINVAL, "n_samples < 1");
+    if (precision == IDN_PREC_BF16X3) return launch_mlp_bf16x3(a, s);
+    if (precision == IDN_PREC_BF16) return launch_mlp_bf16(a, s);
+    if (precision == IDN_PREC_FP16X3) return launch_mlp_fp16x3(a, s);
+    if (precision == IDN_PREC_BF16X6) return launch_mlp_bf16x6(a, s);
+    return launch_mlp_f32(a, s, gate);
 }
 
 static int check_params(const idn_facenerf_params* p) {
@@ -151,8 +144,7 @@ int idealnerf_facenerf_fwd_ch(const float* packed, const float* folded, int prec
     if (n < 0) return fail(IDN_EINVAL, "n < 0");
     if (n == 0) return IDN_OK;
     if (!packed || !folded || !x || !out) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_mlp(precision, packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, 0, nullptr,
-                      pts_ch, views_ch);
+    return launch_mlp(precision, mlp_rows(packed, folded, x, pts_ch, views_ch, n, out), (hipStream_t)stream, MlpGate{});
 }
 int idealnerf_facenerf_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
                            float* out, void* stream) {
@@ -165,8 +157,7 @@ int idealnerf_query_rays_fwd(const float* packed, const float* folded, int preci
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes n_rays=%lld n_samples=%d", (long long)n_rays, n_samples);
     if (n_rays == 0) return IDN_OK;
     if (!packed || !folded || !rays || !z || !raw) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_mlp(precision, packed, folded, nullptr, rays, z, nullptr, nullptr, n_rays * n_samples, n_samples, raw,
-                      (hipStream_t)stream);
+    return launch_mlp(precision, mlp_rays(packed, folded, rays, z, n_rays, n_samples, raw), (hipStream_t)stream, MlpGate{});
 }
 
 int idealnerf_query_points_fwd(const float* packed, const float* folded, int precision, const float* pts,
@@ -175,8 +166,7 @@ int idealnerf_query_points_fwd(const float* packed, const float* folded, int pre
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes n_rays=%lld n_samples=%d", (long long)n_rays, n_samples);
     if (n_rays == 0) return IDN_OK;
     if (!packed || !folded || !pts || !viewdirs || !raw) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_mlp(precision, packed, folded, nullptr, nullptr, nullptr, pts, viewdirs, n_rays * n_samples, n_samples,
-                      raw, (hipStream_t)stream);
+    return launch_mlp(precision, mlp_points(packed, folded, pts, viewdirs, n_rays, n_samples, raw), (hipStream_t)stream, MlpGate{});
 }
 
 int idealnerf_frame_rays(const float* c2w, int H, int W, float focal, float cx, float cy, float near_, float far_,
@@ -351,14 +341,11 @@ int idealnerf_query_rays_train_fwd(const float* packed, const float* folded, int
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes");
     if (n_rays == 0) return IDN_OK;
     if (!packed || !folded || !rays || !z || !raw || !acts) return fail(IDN_EINVAL, "NULL pointer");
-    const int64_t n = n_rays * n_samples;
-    const int64_t p_pad = (n + 127) / 128 * 128;
+    const int64_t p_pad = (n_rays * n_samples + 127) / 128 * 128;
     // (both activation-saving kernels write every row of the slab, the p_pad - n padding rows included -- they repeat the last
     //  point, and their deltas are zero: tests/test_hip_parity.py::test_train_forward_defines_every_row_of_the_activation_slab)
-    if (precision == IDN_PREC_BF16X6)
-        return launch_mlp_bf16x6(packed, folded, nullptr, rays, z, nullptr, nullptr, n, n_samples, raw, (hipStream_t)stream, acts, p_pad);
-    return launch_mlp_f32(packed, folded, nullptr, rays, z, nullptr, nullptr, n, n_samples, raw, (hipStream_t)stream,
-                          acts, p_pad);
+    return launch_mlp(precision, mlp_saving(mlp_rays(packed, folded, rays, z, n_rays, n_samples, raw), acts, p_pad), (hipStream_t)stream,
+                      MlpGate{});
 }
 
 size_t idealnerf_pass_bwd_workspace_bytes(int64_t n_rays, int n_samples) {
@@ -376,34 +363,33 @@ static int check_grads(const idn_facenerf_grads* grads) {
     return IDN_OK;
 }
 
-// The one host function behind the four pass-backward entries.  frozen: no gradient tensors (the conditioning-only plan).
+// The one host function behind the four pass-backward entries.  b.grads null: the frozen (conditioning-only) plan.
 // Every argument error is answered here or at launch_pass_bwd's workspace check, before any HIP call.
-static int pass_bwd_any(const idn_facenerf_params* p, const idn_facenerf_grads* grads, bool frozen, const float* aud,
-                        const float* expr, const float* latent, const float* acts, const float* raw, const float* z,
-                        const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
-                        const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
-                        float* d_latent, const idn_pass_bwd_extra* extra, void* workspace, size_t workspace_bytes,
-                        void* stream) {
+static int pass_bwd_any(const PassBwd& b, void* stream) {
+    const idn_facenerf_params* p = b.p;
+    const BwdCond& c = b.cond;
+    const bool frozen = !b.grads;
     if (int e = check_params(p)) return e;
     if (!frozen)
-        if (int e = check_grads(grads)) return e;
-    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) ||
-        (p->dim_latent > 0) != (latent != nullptr))
+        if (int e = check_grads(b.grads)) return e;
+    if ((p->dim_aud > 0) != (c.aud != nullptr) || (p->dim_expr > 0) != (c.expr != nullptr) ||
+        (p->dim_latent > 0) != (c.latent != nullptr))
         return fail(IDN_EINVAL, "conditioning pointers do not match the widths");
-    float* d_expr = extra ? extra->d_expr : nullptr;
-    float* d_rays = extra ? extra->d_rays : nullptr;
-    float* d_vb = extra ? extra->d_views0_bias : nullptr;
-    if (d_expr && (p->dim_expr == 0 || !expr)) return fail(IDN_EINVAL, "d_expr for a network without an expression");
-    if (frozen && d_rays) return fail(IDN_EUNSUPPORTED, "the conditioning-only backward (grads NULL) returns no ray gradient");
-    if (!frozen && d_vb) return fail(IDN_EINVAL, "d_views0_bias is the frozen plan's: with grads it is grads->views_b[0]");
-    const bool want_cond = d_aud || d_latent || d_expr;
-    if (frozen && d_vb && !want_cond) return fail(IDN_EINVAL, "d_views0_bias needs d_aud, d_latent or d_expr (with none the pass is not run)");
-    if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
-    if (n_rays == 0 || (frozen && !want_cond)) return IDN_OK;   // nothing to deliver
-    if (!acts || !raw || !z || !rays || !bc_rgb) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_pass_bwd(*p, frozen ? nullptr : grads, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples,
-                           g_rgb_map, g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, workspace, workspace_bytes,
-                           (hipStream_t)stream, d_rays, d_expr, d_vb);
+    if (c.d_expr && (p->dim_expr == 0 || !c.expr)) return fail(IDN_EINVAL, "d_expr for a network without an expression");
+    if (frozen && b.d_rays) return fail(IDN_EUNSUPPORTED, "the conditioning-only backward (grads NULL) returns no ray gradient");
+    if (!frozen && c.d_vb) return fail(IDN_EINVAL, "d_views0_bias is the frozen plan's: with grads it is grads->views_b[0]");
+    const bool want_cond = c.d_aud || c.d_latent || c.d_expr;
+    if (frozen && c.d_vb && !want_cond) return fail(IDN_EINVAL, "d_views0_bias needs d_aud, d_latent or d_expr (with none the pass is not run)");
+    if (b.n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
+    if (b.n_rays == 0 || (frozen && !want_cond)) return IDN_OK;   // nothing to deliver
+    if (!b.acts || !b.raw || !b.z || !b.rays || !b.bc) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_pass_bwd(b, (hipStream_t)stream);
+}
+// idealnerf_pass_bwd and _rays have no frozen plan: a NULL grads is their error, behind the params' as in pass_bwd_any
+static int pass_bwd_trained(const PassBwd& b, void* stream) {
+    if (int e = check_params(b.p)) return e;
+    if (!b.grads) return check_grads(b.grads);
+    return pass_bwd_any(b, stream);
 }
 
 int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
@@ -411,8 +397,12 @@ int idealnerf_pass_bwd(const idn_facenerf_params* p, const idn_facenerf_grads* g
                        const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
                        const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
                        float* d_latent, void* workspace, size_t workspace_bytes, void* stream) {
-    return pass_bwd_any(p, grads, false, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map, g_rgb_fg,
-                        g_last_weight, g_acc, d_aud, d_latent, nullptr, workspace, workspace_bytes, stream);
+    PassBwd b = {};
+    b.p = p; b.grads = grads;
+    b.cond.aud = aud; b.cond.expr = expr; b.cond.latent = latent; b.cond.d_aud = d_aud; b.cond.d_latent = d_latent;
+    b.acts = acts; b.raw = raw; b.z = z; b.rays = rays; b.bc = bc_rgb; b.n_rays = n_rays; b.S = n_samples;
+    b.g_rgb = g_rgb_map; b.g_fg = g_rgb_fg; b.g_lw = g_last_weight; b.g_acc = g_acc; b.ws = workspace; b.ws_bytes = workspace_bytes;
+    return pass_bwd_trained(b, stream);
 }
 
 int idealnerf_pass_bwd_rays(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
@@ -420,9 +410,13 @@ int idealnerf_pass_bwd_rays(const idn_facenerf_params* p, const idn_facenerf_gra
                             const float* rays, const float* bc_rgb, int64_t n_rays, int n_samples, const float* g_rgb_map,
                             const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
                             float* d_latent, float* d_rays, void* workspace, size_t workspace_bytes, void* stream) {
-    const idn_pass_bwd_extra extra{nullptr, d_rays, nullptr};
-    return pass_bwd_any(p, grads, false, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map, g_rgb_fg,
-                        g_last_weight, g_acc, d_aud, d_latent, &extra, workspace, workspace_bytes, stream);
+    PassBwd b = {};
+    b.p = p; b.grads = grads;
+    b.cond.aud = aud; b.cond.expr = expr; b.cond.latent = latent; b.cond.d_aud = d_aud; b.cond.d_latent = d_latent;
+    b.acts = acts; b.raw = raw; b.z = z; b.rays = rays; b.bc = bc_rgb; b.n_rays = n_rays; b.S = n_samples;
+    b.g_rgb = g_rgb_map; b.g_fg = g_rgb_fg; b.g_lw = g_last_weight; b.g_acc = g_acc; b.ws = workspace; b.ws_bytes = workspace_bytes;
+    b.d_rays = d_rays;
+    return pass_bwd_trained(b, stream);
 }
 
 int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, const float* expr, const float* latent,
@@ -430,8 +424,12 @@ int idealnerf_pass_bwd_cond(const idn_facenerf_params* p, const float* aud, cons
                             int64_t n_rays, int n_samples, const float* g_rgb_map, const float* g_rgb_fg,
                             const float* g_last_weight, const float* g_acc, float* d_aud, float* d_latent, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    return pass_bwd_any(p, nullptr, true, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map, g_rgb_fg,
-                        g_last_weight, g_acc, d_aud, d_latent, nullptr, workspace, workspace_bytes, stream);
+    PassBwd b = {};
+    b.p = p;
+    b.cond.aud = aud; b.cond.expr = expr; b.cond.latent = latent; b.cond.d_aud = d_aud; b.cond.d_latent = d_latent;
+    b.acts = acts; b.raw = raw; b.z = z; b.rays = rays; b.bc = bc_rgb; b.n_rays = n_rays; b.S = n_samples;
+    b.g_rgb = g_rgb_map; b.g_fg = g_rgb_fg; b.g_lw = g_last_weight; b.g_acc = g_acc; b.ws = workspace; b.ws_bytes = workspace_bytes;
+    return pass_bwd_any(b, stream);
 }
 
 int idealnerf_pass_bwd_ex(const idn_facenerf_params* p, const idn_facenerf_grads* grads, const float* aud,
@@ -440,8 +438,13 @@ int idealnerf_pass_bwd_ex(const idn_facenerf_params* p, const idn_facenerf_grads
                           const float* g_rgb_fg, const float* g_last_weight, const float* g_acc, float* d_aud,
                           float* d_latent, const idn_pass_bwd_extra* extra, void* workspace, size_t workspace_bytes,
                           void* stream) {
-    return pass_bwd_any(p, grads, grads == nullptr, aud, expr, latent, acts, raw, z, rays, bc_rgb, n_rays, n_samples, g_rgb_map,
-                        g_rgb_fg, g_last_weight, g_acc, d_aud, d_latent, extra, workspace, workspace_bytes, stream);
+    PassBwd b = {};
+    b.p = p; b.grads = grads;
+    b.cond.aud = aud; b.cond.expr = expr; b.cond.latent = latent; b.cond.d_aud = d_aud; b.cond.d_latent = d_latent;
+    if (extra) b.cond.d_expr = extra->d_expr, b.cond.d_vb = extra->d_views0_bias, b.d_rays = extra->d_rays;
+    b.acts = acts; b.raw = raw; b.z = z; b.rays = rays; b.bc = bc_rgb; b.n_rays = n_rays; b.S = n_samples;
+    b.g_rgb = g_rgb_map; b.g_fg = g_rgb_fg; b.g_lw = g_last_weight; b.g_acc = g_acc; b.ws = workspace; b.ws_bytes = workspace_bytes;
+    return pass_bwd_any(b, stream);
 }
 
 int idealnerf_facenerf_train_fwd(const float* packed, const float* folded, int precision, const float* x, int64_t n,
@@ -457,11 +460,8 @@ int idealnerf_facenerf_train_fwd_ch(const float* packed, const float* folded, in
     if (!packed || !folded || !x || !out || !acts) return fail(IDN_EINVAL, "NULL pointer");
     if (n > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "n %lld exceeds 2^31-1 per launch", (long long)n);
     const int64_t p_pad = (n + 127) / 128 * 128;
-    if (precision == IDN_PREC_BF16X6)
-        return launch_mlp_bf16x6(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad,
-                                 pts_ch, views_ch);
-    return launch_mlp_f32(packed, folded, x, nullptr, nullptr, nullptr, nullptr, n, 1, out, (hipStream_t)stream, acts, p_pad, 0,
-                          nullptr, pts_ch, views_ch);
+    return launch_mlp(precision, mlp_saving(mlp_rows(packed, folded, x, pts_ch, views_ch, n, out), acts, p_pad), (hipStream_t)stream,
+                      MlpGate{});
 }
 
 size_t idealnerf_facenerf_bwd_workspace_bytes(int64_t n) {
@@ -480,8 +480,8 @@ int idealnerf_facenerf_bwd(const idn_facenerf_params* p, const idn_facenerf_grad
     if (n < 0) return fail(IDN_EINVAL, "n < 0");
     if (n == 0) return IDN_OK;
     if (!acts || !g_out) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_facenerf_bwd(*p, *grads, aud, expr, latent, acts, n, g_out, d_x, d_aud, d_expr, d_latent, workspace,
-                               workspace_bytes, (hipStream_t)stream);
+    const BwdCond cond = {aud, expr, latent, d_aud, d_expr, d_latent, nullptr};   // (d_vb is the frozen pass plan's)
+    return launch_facenerf_bwd(*p, *grads, cond, acts, n, g_out, d_x, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t idealnerf_dw_gemm_workspace_bytes(void) { return dw_gemm_workspace_bytes(); }
@@ -659,7 +659,8 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, const i
         const Draws draws{(unsigned long long)a->rng_seed, (long)(a->rng_ray0 + r0), a->rng_mode};   // this pass's rows of the draw table
         if (int e = launch_coarse_depths(rays, a->t_vals, off(a->t_rand, r0 * S), c, S, a->lindisp, w.z_c, st, draws)) return e;
         if (!a->fused_march)
-            if (int e = launch_mlp(a->precision, a->packed_coarse, a->folded_coarse, nullptr, rays, w.z_c, nullptr, nullptr, c * S, S, w.raw_c, st, gate_c, gate_counters)) return e;
+            if (int e = launch_mlp(a->precision, mlp_rays(a->packed_coarse, a->folded_coarse, rays, w.z_c, c, S, w.raw_c), st, MlpGate{gate_c, gate_counters}))
+                return e;
         idn_composite_out co = {};
         const bool fine = Ni > 0;
         co.rgb_map = off(fine ? a->rgb0 : a->rgb_map, r0 * 3);
@@ -702,8 +703,9 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, const i
                                  off(a->tap_z_samples, r0 * Ni), off(a->tap_inds, r0 * Ni), off(a->tap_cdf, r0 * (S - 1)),
                                  w.z_f, off(a->z_std, r0), st, draws))
             return e;
-        if (int e = launch_mlp(prec_fine, a->packed_fine, a->folded_fine, nullptr, rays, w.z_f, nullptr, nullptr, c * Sf, Sf, w.raw_f, st, gate_f,
-                                 gate_counters ? gate_counters + 2 : nullptr)) return e;
+        if (int e = launch_mlp(prec_fine, mlp_rays(a->packed_fine, a->folded_fine, rays, w.z_f, c, Sf, w.raw_f), st,
+                               MlpGate{gate_f, gate_counters ? gate_counters + 2 : nullptr}))
+            return e;
         idn_composite_out fo = {};
         fo.rgb_map = off(a->rgb_map, r0 * 3);
         fo.disp_map = off(a->disp_map, r0);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
+#include <type_traits>
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/idealnerf.h"
@@ -205,35 +206,76 @@ struct ProfScope {
 int launch_pack_f32(const idn_facenerf_params& p, float* packed, hipStream_t s);
 int launch_pack_bf16x3(const idn_facenerf_params& p, float* packed, hipStream_t s, int fmt = 0);  // fmt 1: fp16 halves
 int launch_pack_bf16x6(const idn_facenerf_params& p, float* packed, hipStream_t s);
-int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                      float* acts = nullptr, int64_t p_pad = 0,    // acts != null: the training forward (saves activations + ReLU masks)
-                      int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);   // x != null: the widths of its rows
 int launch_pack_bf16(const idn_facenerf_params& p, float* packed, hipStream_t s);
-int launch_mlp_bf16(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                    int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
-int launch_mlp_bf16x3(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                      int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
-int launch_mlp_fp16x3(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                      int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
-// precision dispatch for the inference forward
-// gate (fp32 rays mode only; ignored by the other arithmetics): the colour-gated kernel; gate_counters: device int64 [2]
-// (tiles, skipped) it adds to, or null
-int launch_mlp(int precision, const float* packed, const float* folded, const float* x, const float* rays,
-               const float* z, const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw,
-               hipStream_t s, int gate = 0, int64_t* gate_counters = nullptr, int pts_ch = IDN_PTS_CH,
-               int views_ch = IDN_VIEWS_CH);   // x != null: the widths of its rows [n_points, pts_ch + views_ch]
 int launch_fold(const idn_facenerf_params& p, const float* aud, const float* expr, const float* latent,
                 float* folded, hipStream_t s);
-// x != nullptr: pre-embedded rows [n_points, pts_ch + views_ch]; pts != nullptr: raw points [n_points,3] +
-// dirs[n_points/S, 3]; else rays[n_rays,11] + z[n_rays,S]
-int launch_mlp_f32(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                   const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                   float* acts = nullptr, int64_t p_pad = 0, int gate = 0, int64_t* gate_counters = nullptr,
-                   int pts_ch = IDN_PTS_CH, int views_ch = IDN_VIEWS_CH);
+
+// ---------------------------------------------------------------------------
+// Network forward: the kernels' argument record IS the launchers' parameter.  The input mode is the pointer that is set:
+// x (pre-embedded rows), pts (+ dirs), else rays + z.  A call site builds the record with the builder of its mode, so it
+// names its mode and never writes another mode's pointers.
+// ---------------------------------------------------------------------------
+struct MlpArgs {
+    const float* wstream;
+    const float* bias;
+    const float* x;     // kModeX:    [n_points, x_pts_ch + x_views_ch] pre-embedded rows
+    const float* rays;  // kModeRays: [n_rays, 11]
+    const float* z;     // kModeRays: [n_rays, S]
+    const float* pts;   // kModePts:  [n_points, 3]
+    const float* dirs;  // kModePts:  [n_rays, 3] unit view directions
+    long n_points;
+    int S;
+    float* raw;         // [n_points, 4]
+    float* acts;        // training only: activation slab (act_off() matrices of p_pad rows), else null
+    long p_pad;
+    int x_pts_ch, x_views_ch;   // kModeX: the network's encoding widths (3..63, 3..27); the other modes do not read them
+};
+// the colour-gated fp32 rays kernel's arguments (the other kernels' stay as they are)
+struct MlpGateArgs : MlpArgs {
+    unsigned long long* gate_counters;   // (tiles, skipped) this launch adds to, or null
+    int tile_step;                       // tile_order_step(grid) (tile_order.h): the kernel's loop divides nothing
+};
+// both are copied into the kernarg segment as they are: a new field moves every kernel's argument layout
+static_assert(sizeof(MlpArgs) == 104 && std::is_trivially_copyable<MlpArgs>::value, "kernel argument layout");
+static_assert(sizeof(MlpGateArgs) == 120 && std::is_trivially_copyable<MlpGateArgs>::value, "kernel argument layout");
+
+// what every mode sets; the pointers of the modes stay null, the widths at the default
+inline MlpArgs mlp_no_input(const float* packed, const float* folded, int64_t n_points, int S, float* raw) {
+    MlpArgs a = {};
+    a.wstream = packed; a.bias = folded; a.n_points = (long)n_points; a.S = S; a.raw = raw;
+    a.x_pts_ch = IDN_PTS_CH; a.x_views_ch = IDN_VIEWS_CH;
+    return a;
+}
+inline MlpArgs mlp_rows(const float* packed, const float* folded, const float* x, int pts_ch, int views_ch, int64_t n, float* raw) {
+    MlpArgs a = mlp_no_input(packed, folded, n, 1, raw);
+    a.x = x; a.x_pts_ch = pts_ch; a.x_views_ch = views_ch;
+    return a;
+}
+inline MlpArgs mlp_rays(const float* packed, const float* folded, const float* rays, const float* z, int64_t n_rays, int S, float* raw) {
+    MlpArgs a = mlp_no_input(packed, folded, n_rays * S, S, raw);
+    a.rays = rays; a.z = z;
+    return a;
+}
+inline MlpArgs mlp_points(const float* packed, const float* folded, const float* pts, const float* dirs, int64_t n_rays, int S, float* raw) {
+    MlpArgs a = mlp_no_input(packed, folded, n_rays * S, S, raw);
+    a.pts = pts; a.dirs = dirs;
+    return a;
+}
+// the training forward: the same launch also fills the activation slab (p_pad = n_points rounded up to 128)
+inline MlpArgs mlp_saving(MlpArgs a, float* acts, int64_t p_pad) {
+    a.acts = acts; a.p_pad = (long)p_pad;
+    return a;
+}
+// fp32 rays-mode inference only: the colour-gated kernel; counters: device int64 [2] (tiles, skipped) it adds to, or null
+struct MlpGate { int on; int64_t* counters; };
+// one launcher per arithmetic (mlp_launch.h holds their common body), and the precision dispatch in front of them.
+// acts set: the training forward (IDN_PREC_F32 and IDN_PREC_BF16X6 build it).  The gate is the fp32 launcher's alone.
+int launch_mlp_f32(const MlpArgs& a, hipStream_t s, MlpGate gate);
+int launch_mlp_bf16x3(const MlpArgs& a, hipStream_t s);
+int launch_mlp_fp16x3(const MlpArgs& a, hipStream_t s);
+int launch_mlp_bf16(const MlpArgs& a, hipStream_t s);
+int launch_mlp_bf16x6(const MlpArgs& a, hipStream_t s);
+int launch_mlp(int precision, const MlpArgs& a, hipStream_t s, MlpGate gate);
 
 int launch_frame_rays(const float* c2w, int H, int W, float focal, float cx, float cy, float near_, float far_,
                       int row0, int nrows, float* rays_out, hipStream_t s);
@@ -348,23 +390,33 @@ int launch_dw_products(int64_t rows, int pipe, int x6_items, idn_dw_product* pro
 
 // train.hip: backward of one render pass
 size_t bwd_workspace_bytes(int64_t n_points);
-// gr == nullptr: the conditioning-only backward of a frozen network (d_aud / d_latent / d_expr alone; no gradient tensor is
-// written).  d_expr [dim_expr] != null: accumulated, either plan.  d_vb [128] != null (gr == nullptr only): views_linears.0's
-// bias gradient, overwritten.
-int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
-                    const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
-                    const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
-                    const float* g_acc, float* d_aud, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s,
-                    float* d_rays = nullptr,    // d_rays [n_rays, 11] != null: also the gradient of the ray records (overwritten)
-                    float* d_expr = nullptr, float* d_vb = nullptr);
+// the conditioning vectors of a network and where a backward puts their gradients (a null gradient is not delivered)
+struct BwdCond {
+    const float *aud, *expr, *latent;
+    float *d_aud, *d_expr, *d_latent;   // d_expr [dim_expr]: accumulated
+    float* d_vb;                        // [128], the frozen plan only: views_linears.0's bias gradient, overwritten
+};
+// One pass backward, as the four idealnerf_pass_bwd* entries fill it; a field an entry does not have stays null.
+struct PassBwd {
+    const idn_facenerf_params* p;
+    const idn_facenerf_grads* grads;    // null: the conditioning-only plan of a frozen network (no gradient tensor is written)
+    BwdCond cond;
+    const float *acts, *raw, *z, *rays, *bc;
+    int64_t n_rays;
+    int S;
+    const float *g_rgb, *g_fg, *g_lw, *g_acc;   // the gradients of the pass's four outputs
+    float* d_rays;                      // [n_rays, 11] != null: also the gradient of the ray records (overwritten)
+    void* ws;
+    size_t ws_bytes;
+};
+int launch_pass_bwd(const PassBwd& b, hipStream_t s);
 // ray_grad.hip: d_x [n_rays * S, pts_ch + views_ch] (the input-row gradient of the pass's points) -> d_rays [n_rays, 11];
 // column 6 of d_rays holds dL / d |rays_d| on entry
 int launch_ray_grad(const float* d_x, int pts_ch, int views_ch, const float* rays, const float* z, int64_t n_rays, int S,
                     float* d_rays, hipStream_t s);
 // FaceNeRF.forward's backward on pre-embedded rows: head deltas from g_out [n, 4], the same tail as launch_pass_bwd, d expr
 // from the fold and (d_x != null) the input-row gradient d_x [n, pts_ch + views_ch]
-int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
-                        const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
-                        float* d_expr, float* d_latent, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const BwdCond& cond, const float* acts,
+                        int64_t n, const float* g_out, float* d_x, void* ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace idn

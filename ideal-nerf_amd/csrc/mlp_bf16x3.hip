@@ -15,7 +15,7 @@
 // pack_bf16x3_kernel orders the weights.
 #include <type_traits>
 
-#include "mlp_common.h"
+#include "mlp_launch.h"
 
 namespace idn {
 
@@ -544,69 +544,19 @@ __global__ __launch_bounds__(64 * kPlainWaves, 1) void mlp_bf16_kernel(MlpArgs a
     __syncthreads();
 }
 
-int launch_mlp_bf16(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                    const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                    int pts_ch, int views_ch) {
-    constexpr int NW = kPlainWaves, PT = kPlainSets;
-    if (n_points <= 0) return IDN_OK;
-    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
+int launch_mlp_bf16(const MlpArgs& a, hipStream_t s) {
     static LaunchSetup setup;
-    int num_cu = 0;
-    if (int e = setup.get([]() -> int {
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModeRays>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModeX>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bf16_kernel<kModePts>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            return IDN_OK;
-        }, &num_cu))
-        return e;
-    const int64_t ntiles = (n_points + 32 * NW * PT - 1) / (32 * NW * PT);
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, nullptr, 0, pts_ch, views_ch};
-    ProfScope prof(s, n_points);
-    if (x)
-        hipLaunchKernelGGL((mlp_bf16_kernel<kModeX>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
-    else if (pts)
-        hipLaunchKernelGGL((mlp_bf16_kernel<kModePts>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
-    else
-        hipLaunchKernelGGL((mlp_bf16_kernel<kModeRays>), dim3(grid), dim3(64 * NW), kMlpLds, s, a);
-    IDN_HIP_CHECK(hipGetLastError());
-    return IDN_OK;
+    static const MlpKernels kernels = mlp_inference_kernels(&mlp_bf16_kernel<kModeRays>, &mlp_bf16_kernel<kModeX>, &mlp_bf16_kernel<kModePts>,
+                                                            kMlpLds, 32 * kPlainWaves * kPlainSets, 64 * kPlainWaves);
+    return launch_mlp_kernels(kernels, setup, a, MlpGate{}, s);
 }
 
 #endif  // IDN_X3_FP16
 
-int X3_LAUNCH(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                      int pts_ch, int views_ch) {
-    if (n_points <= 0) return IDN_OK;
-    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
+int X3_LAUNCH(const MlpArgs& a, hipStream_t s) {
     static LaunchSetup setup;
-    int num_cu = 0;
-    if (int e = setup.get([]() -> int {
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&X3_KERNEL<kModeRays>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&X3_KERNEL<kModeX>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&X3_KERNEL<kModePts>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            return IDN_OK;
-        }, &num_cu))
-        return e;
-    const int64_t ntiles = (n_points + 127) / 128;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, nullptr, 0, pts_ch, views_ch};
-    ProfScope prof(s, n_points);
-    if (x)
-        hipLaunchKernelGGL((X3_KERNEL<kModeX>), dim3(grid), dim3(256), kMlpLds, s, a);
-    else if (pts)
-        hipLaunchKernelGGL((X3_KERNEL<kModePts>), dim3(grid), dim3(256), kMlpLds, s, a);
-    else
-        hipLaunchKernelGGL((X3_KERNEL<kModeRays>), dim3(grid), dim3(256), kMlpLds, s, a);
-    IDN_HIP_CHECK(hipGetLastError());
-    return IDN_OK;
+    static const MlpKernels kernels = mlp_inference_kernels(&X3_KERNEL<kModeRays>, &X3_KERNEL<kModeX>, &X3_KERNEL<kModePts>, kMlpLds, 128, 256);
+    return launch_mlp_kernels(kernels, setup, a, MlpGate{}, s);
 }
 
 }  // namespace idn

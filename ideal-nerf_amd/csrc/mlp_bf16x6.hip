@@ -20,6 +20,7 @@
 // Weight stream: per step a TRIPLE of fragments (p1, p2, p3) in 48-fragment ring slots: a slice is 16 steps, every
 // layer starts where it does in the other streams modulo the ring, and the 3.375 MiB stream stays in the per-XCD L2.
 #include "mlp_x6.h"
+#include "mlp_launch.h"
 
 namespace idn {
 namespace x6 {
@@ -323,46 +324,23 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x6_kernel(MlpArgs a) {
 
 }  // namespace x6
 
-int launch_mlp_bf16x6(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                      const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                      float* acts, int64_t p_pad, int pts_ch, int views_ch) {
-    if (n_points <= 0) return IDN_OK;
-    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
-    if (acts && pts) return fail(IDN_EUNSUPPORTED, "the activation-saving forward takes rays or pre-embedded rows");
+int launch_mlp_bf16x6(const MlpArgs& a, hipStream_t s) {
+    constexpr int kLds = x6::mlp_lds6<x6::WStream6x3>();   // the saving kernels take the same
+    static_assert(kLds <= 160 * 1024, "LDS per CU");
     static LaunchSetup setup;
-    int num_cu = 0;
-    constexpr int kLdsInfer = x6::mlp_lds6<x6::WStream6x3>(), kLdsTrain = kLdsInfer;
-    static_assert(kLdsInfer <= 160 * 1024, "LDS per CU");
-    if (int e = setup.get([]() -> int {
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModeRays, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsInfer));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModeRays, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTrain));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModeX, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsInfer));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModeX, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTrain));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&x6::mlp_bf16x6_kernel<kModePts, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsInfer));
-            return IDN_OK;
-        }, &num_cu))
-        return e;
-    const int64_t ntiles = (n_points + 127) / 128;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad, pts_ch, views_ch};
-    ProfScope prof(s, n_points, acts ? IDN_PROF_MLP_FWD_SAVE_X6 : IDN_PROF_MLP_FWD);
-    if (x && acts)   // FaceNeRF.forward with gradients: the same instruction sequence as the line below plus the slab stores
-        hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModeX, true>), dim3(grid), dim3(256), kLdsTrain, s, a);
-    else if (x)
-        hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModeX, false>), dim3(grid), dim3(256), kLdsInfer, s, a);
-    else if (pts)
-        hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModePts, false>), dim3(grid), dim3(256), kLdsInfer, s, a);
-    else if (acts)
-        hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModeRays, true>), dim3(grid), dim3(256), kLdsTrain, s, a);
-    else
-        hipLaunchKernelGGL((x6::mlp_bf16x6_kernel<kModeRays, false>), dim3(grid), dim3(256), kLdsInfer, s, a);
-    IDN_HIP_CHECK(hipGetLastError());
-    return IDN_OK;
+    static const MlpKernels kernels = [] {
+        MlpKernels k = {};
+        k.cell[kModeRays][0] = {&x6::mlp_bf16x6_kernel<kModeRays, false>, kLds};
+        k.cell[kModeRays][1] = {&x6::mlp_bf16x6_kernel<kModeRays, true>, kLds};
+        k.cell[kModeX][0] = {&x6::mlp_bf16x6_kernel<kModeX, false>, kLds};
+        k.cell[kModeX][1] = {&x6::mlp_bf16x6_kernel<kModeX, true>, kLds};   // FaceNeRF.forward with gradients: the inference kernel's instruction sequence plus the slab stores
+        k.cell[kModePts][0] = {&x6::mlp_bf16x6_kernel<kModePts, false>, kLds};
+        k.tile_points = 128; k.threads = 256;
+        k.prof_kind_saving = IDN_PROF_MLP_FWD_SAVE_X6;
+        k.no_saving = "the activation-saving forward takes rays or pre-embedded rows";
+        return k;
+    }();
+    return launch_mlp_kernels(kernels, setup, a, MlpGate{}, s);
 }
 
 }  // namespace idn

@@ -328,27 +328,7 @@ __device__ __forceinline__ float pe_slot(const PeAxes& ax, const PeLane& ln) {
     }
 }
 
-enum { kModeRays = 0, kModeX = 1, kModePts = 2 };
-struct MlpArgs {
-    const float* wstream;
-    const float* bias;
-    const float* x;     // kModeX:    [n_points, x_pts_ch + x_views_ch] pre-embedded rows
-    const float* rays;  // kModeRays: [n_rays, 11]
-    const float* z;     // kModeRays: [n_rays, S]
-    const float* pts;   // kModePts:  [n_points, 3]
-    const float* dirs;  // kModePts:  [n_rays, 3] unit view directions
-    long n_points;
-    int S;
-    float* raw;         // [n_points, 4]
-    float* acts;        // training only: activation slab (act_off() matrices of p_pad rows), else null
-    long p_pad;
-    int x_pts_ch, x_views_ch;   // kModeX: the network's encoding widths (3..63, 3..27); the other modes do not read them
-};
-// the colour-gated fp32 rays kernel's arguments (the other kernels' stay as they are)
-struct MlpGateArgs : MlpArgs {
-    unsigned long long* gate_counters;   // (tiles, skipped) this launch adds to, or null
-    int tile_step;                       // tile_order_step(grid) (tile_order.h): the kernel's loop divides nothing
-};
+enum { kModeRays = 0, kModeX = 1, kModePts = 2 };   // of an MlpArgs / MlpGateArgs (idn_internal.h)
 
 // Raw inputs of one lane's point.  They are loaded one pass ahead (right after a slice opens in
 // the middle of the previous pass and "touched" after the next one, where the slice barrier's

@@ -16,7 +16,7 @@
 //     weight stream keeps flowing across tiles (the colour-gated instantiation: in rounds of
 //     one tile per workgroup, rotated round by round -- tile_order.h).
 #include "mlp_f32_layers.h"
-#include "tile_order.h"
+#include "mlp_launch.h"
 
 namespace idn {
 
@@ -378,55 +378,23 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(std::conditional_t<GATE
     __syncthreads();
 }
 
-int launch_mlp_f32(const float* packed, const float* folded, const float* x, const float* rays, const float* z,
-                   const float* pts, const float* dirs, int64_t n_points, int n_samples, float* raw, hipStream_t s,
-                   float* acts, int64_t p_pad, int gate, int64_t* gate_counters, int pts_ch, int views_ch) {
-    if (n_points <= 0) return IDN_OK;
+int launch_mlp_f32(const MlpArgs& a, hipStream_t s, MlpGate gate) {
     static LaunchSetup setup;
-    int num_cu = 0;
-    if (int e = setup.get([]() -> int {
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeRays, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeRays, false, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsGate));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeX, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModePts, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLds));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeRays, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsTrain));
-            IDN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_f32_kernel<kModeX, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsTrain));
-            return IDN_OK;
-        }, &num_cu))
-        return e;
-    const int64_t ntiles = (n_points + 127) / 128;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    if (gate && (acts || x || pts)) return fail(IDN_EUNSUPPORTED, "the colour gate is built for the rays-mode inference launch");
-    if (x && !widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", pts_ch, views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
-    MlpArgs a{packed, folded, x, rays, z, pts, dirs, (long)n_points, n_samples, raw, acts, (long)p_pad, pts_ch, views_ch};
-    ProfScope prof(s, n_points, acts ? IDN_PROF_MLP_FWD_SAVE : IDN_PROF_MLP_FWD);
-    if (acts) {
-        if (pts) return fail(IDN_EUNSUPPORTED, "activation saving is built for the rays+z and the pre-embedded-row input modes");
-        if (x)   // FaceNeRF.forward with gradients: the slab's x0 / dir matrices hold the rows' own encodings
-            hipLaunchKernelGGL((mlp_f32_kernel<kModeX, true>), dim3(grid), dim3(256), kMlpLdsTrain, s, a);
-        else
-            hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, true>), dim3(grid), dim3(256), kMlpLdsTrain, s, a);
-    } else if (x)
-        hipLaunchKernelGGL((mlp_f32_kernel<kModeX, false>), dim3(grid), dim3(256), kMlpLds, s, a);
-    else if (pts)
-        hipLaunchKernelGGL((mlp_f32_kernel<kModePts, false>), dim3(grid), dim3(256), kMlpLds, s, a);
-    else if (gate) {
-        MlpGateArgs ga;
-        static_cast<MlpArgs&>(ga) = a;
-        ga.gate_counters = reinterpret_cast<unsigned long long*>(gate_counters);
-        ga.tile_step = tile_order_step(grid);
-        hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, false, true>), dim3(grid), dim3(256), kMlpLdsGate, s, ga);
-    }
-    else
-        hipLaunchKernelGGL((mlp_f32_kernel<kModeRays, false>), dim3(grid), dim3(256), kMlpLds, s, a);
-    IDN_HIP_CHECK(hipGetLastError());
-    return IDN_OK;
+    static const MlpKernels kernels = [] {
+        MlpKernels k = {};
+        // (named in the order this file has always instantiated them: the code object lists its kernels in that order)
+        k.cell[kModeRays][0] = {&mlp_f32_kernel<kModeRays, false>, kMlpLds};
+        k.gated = &mlp_f32_kernel<kModeRays, false, true>; k.gated_lds = kMlpLdsGate;
+        k.cell[kModeX][0] = {&mlp_f32_kernel<kModeX, false>, kMlpLds};
+        k.cell[kModePts][0] = {&mlp_f32_kernel<kModePts, false>, kMlpLds};
+        k.cell[kModeRays][1] = {&mlp_f32_kernel<kModeRays, true>, kMlpLdsTrain};
+        k.cell[kModeX][1] = {&mlp_f32_kernel<kModeX, true>, kMlpLdsTrain};   // FaceNeRF.forward with gradients: the slab's x0 / dir matrices hold the rows' own encodings
+        k.tile_points = 128; k.threads = 256;
+        k.prof_kind_saving = IDN_PROF_MLP_FWD_SAVE;
+        k.no_saving = "activation saving is built for the rays+z and the pre-embedded-row input modes";
+        return k;
+    }();
+    return launch_mlp_kernels(kernels, setup, a, gate, s);
 }
 
 }  // namespace idn

@@ -321,9 +321,8 @@ static int backward_pipe() {
 // dA[5] and the d cond range of the fold; no weight-gradient product runs and no gradient tensor is written.  There d_expr
 // and d_vb [128] (views_linears.0's bias gradient, overwritten) need dbv': the column sums of dV0[:, 0:128] over the P real
 // rows (the padding rows' deltas are whatever the chain made of rows the head deltas leave at zero: they stay out).
-static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grads, const float* aud, const float* expr,
-                    const float* latent, const float* acts, int64_t P, int64_t Pp, const BwdWs& w, float* d_aud, float* d_expr,
-                    float* d_latent, hipStream_t s, float* d_vb = nullptr) {
+static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grads, const BwdCond& cond, const float* acts, int64_t P,
+                    int64_t Pp, const BwdWs& w, hipStream_t s) {
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
     // the network's encoding widths: the leading dimensions of its three mixed-input tensors and the columns the narrow
     // takes keep of the 64-column products (the slab's x0 / dir matrices are 64 wide whatever the width)
@@ -344,7 +343,7 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
         TRY(launch_delta_chain(w.wbwd, acts, Pp, w.dRGB, w.dV0, w.dV[0], w.dV[1], w.dA, s));
     }
     if (!grads) {
-        const bool want_dbv = d_expr != nullptr || d_vb != nullptr;
+        const bool want_dbv = cond.d_expr != nullptr || cond.d_vb != nullptr;
         if (C == 0 && !want_dbv) return IDN_OK;
         float* db = w.cpart;                                        // [2][256]: db0', db5'
         double* part = reinterpret_cast<double*>(w.cpart + 512);    // [blocks][2][256] (the pool is 256-byte aligned)
@@ -361,7 +360,7 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
         // dbv' [128]: the same two kernels, 128 threads wide, on dV0's delta columns and the real rows alone; `part` is free
         // again (the stream orders it behind the finish above), the result goes to the caller's buffer or, with none, to the
         // partial-product pool this plan never uses
-        float* dbv = d_vb ? d_vb : w.part;
+        float* dbv = cond.d_vb ? cond.d_vb : w.part;
         if (want_dbv) {
             const int blocks = (int)((P + rows_per_block - 1) / rows_per_block);
             hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 1), dim3(128), 0, s, (const float*)w.dV0, (const float*)w.dV0, (long)P,
@@ -371,7 +370,7 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
             IDN_HIP_CHECK(hipGetLastError());
         }
         if (C == 0) return IDN_OK;
-        FoldBwdArgs f{p, aud, expr, latent, db, db + 256, dbv, nullptr, nullptr, nullptr, d_aud, d_latent, d_expr};
+        FoldBwdArgs f{p, cond.aud, cond.expr, cond.latent, db, db + 256, dbv, nullptr, nullptr, nullptr, cond.d_aud, cond.d_latent, cond.d_expr};
         hipLaunchKernelGGL(fold_bwd_kernel<true>, dim3((C * 64 + 255) / 256), dim3(256), 0, s, f);
         IDN_HIP_CHECK(hipGetLastError());
         return IDN_OK;
@@ -427,8 +426,8 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
     TRY(q.finish());
 #undef TRY
     {
-        FoldBwdArgs f{p, aud, expr, latent, gr.pts_b[0], gr.pts_b[5], gr.views_b[0], gr.pts_w[0], gr.pts_w[5],
-                      gr.views_w[0], d_aud, d_latent, d_expr};
+        FoldBwdArgs f{p, cond.aud, cond.expr, cond.latent, gr.pts_b[0], gr.pts_b[5], gr.views_b[0], gr.pts_w[0], gr.pts_w[5],
+                      gr.views_w[0], cond.d_aud, cond.d_latent, cond.d_expr};
         const int total = IDN_W * C + (IDN_W / 2) * p.dim_expr + C * 64;   // one wavefront per conditioning column at the end
         if (total > 0) {
             hipLaunchKernelGGL(fold_bwd_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, s, f);
@@ -461,16 +460,15 @@ static void launch_composite_bwd(const CompBwdArgs& a, int64_t n_rays, int S, hi
 // workspace: the delta matrix of pts_linears.1 is free once the weight gradients are reduced, and p_pad x 256 floats hold
 // n x (pts_ch + views_ch <= 90)) and its reduction to the ray records (ray_grad.hip).  The compositing backward leaves dL / d |rays_d| in column 6
 // of d_rays, which the reduction reads before it writes that column's zero.
-int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, const float* aud, const float* expr,
-                    const float* latent, const float* acts, const float* raw, const float* z, const float* rays,
-                    const float* bc, int64_t n_rays, int S, const float* g_rgb, const float* g_fg, const float* g_lw,
-                    const float* g_acc, float* d_aud, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s, float* d_rays,
-                    float* d_expr, float* d_vb) {
+int launch_pass_bwd(const PassBwd& b, hipStream_t s) {
+    const idn_facenerf_params& p = *b.p;
+    const int64_t n_rays = b.n_rays; const int S = b.S;
+    float* const d_rays = b.d_rays;
     const int64_t P = n_rays * S;
     const int64_t Pp = (P + 127) / 128 * 128;
     if (S < 2 || S > 64 * kMaxSpl) return fail(IDN_EUNSUPPORTED, "pass_bwd: n_samples %d outside [2, %d]", S, 64 * kMaxSpl);
-    const BwdWs w = carve_bwd(reinterpret_cast<char*>(ws_), Pp);
-    if (!ws_ || ws_bytes < w.bytes) return fail(IDN_EWORKSPACE, "backward workspace %zu < %zu", ws_bytes, w.bytes);
+    const BwdWs w = carve_bwd(reinterpret_cast<char*>(b.ws), Pp);
+    if (!b.ws || b.ws_bytes < w.bytes) return fail(IDN_EWORKSPACE, "backward workspace %zu < %zu", b.ws_bytes, w.bytes);
 
     // d(outputs) -> d raw, written straight into the head deltas (zero elsewhere)
     IDN_HIP_CHECK(hipMemsetAsync(w.dRGB, 0, (size_t)Pp * 64 * 4, s));
@@ -481,18 +479,18 @@ int launch_pass_bwd(const idn_facenerf_params& p, const idn_facenerf_grads* gr, 
     // it reaches only output rows / column sums 129..255, which `take` never asks for
     if (Pp > P) IDN_HIP_CHECK(hipMemsetAsync(w.dV0 + (size_t)P * 256, 0, (size_t)(Pp - P) * 256 * 4, s));
     {
-        CompBwdArgs a{reinterpret_cast<const float4*>(raw), z, rays, bc, g_rgb, g_fg, g_lw, g_acc,
+        CompBwdArgs a{reinterpret_cast<const float4*>(b.raw), b.z, b.rays, b.bc, b.g_rgb, b.g_fg, b.g_lw, b.g_acc,
                       w.dRGB, 64, w.dV0 + kSigmaChannel, 256, (long)n_rays, S, d_rays ? d_rays + 6 : nullptr, IDN_RAY_FLOATS};
         if (d_rays) launch_composite_bwd<true>(a, n_rays, S, s);
         else launch_composite_bwd<false>(a, n_rays, S, s);
         IDN_HIP_CHECK(hipGetLastError());
     }
-    if (int e = bwd_tail(p, gr, aud, expr, latent, acts, P, Pp, w, d_aud, d_expr, d_latent, s, d_vb)) return e;
+    if (int e = bwd_tail(p, b.grads, b.cond, b.acts, P, Pp, w, s)) return e;
     if (d_rays) {
         float* d_x = w.dA[1];
         static_assert(IDN_PTS_CH + IDN_VIEWS_CH <= 256, "the input-row gradient fits a delta matrix");
         if (int e = launch_dx(p, w, P, Pp, d_x, s)) return e;
-        return launch_ray_grad(d_x, pts_ch_of(p), views_ch_of(p), rays, z, n_rays, S, d_rays, s);
+        return launch_ray_grad(d_x, pts_ch_of(p), views_ch_of(p), b.rays, b.z, n_rays, S, d_rays, s);
     }
     return IDN_OK;
 }
@@ -632,9 +630,8 @@ static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, in
     return IDN_OK;
 }
 
-int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const float* aud, const float* expr,
-                        const float* latent, const float* acts, int64_t n, const float* g_out, float* d_x, float* d_aud,
-                        float* d_expr, float* d_latent, void* ws_, size_t ws_bytes, hipStream_t s) {
+int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const BwdCond& cond, const float* acts,
+                        int64_t n, const float* g_out, float* d_x, void* ws_, size_t ws_bytes, hipStream_t s) {
     const int64_t Pp = (n + 127) / 128 * 128;
     const BwdWs w = carve_bwd(reinterpret_cast<char*>(ws_), Pp);
     if (!ws_ || ws_bytes < w.bytes) return fail(IDN_EWORKSPACE, "backward workspace %zu < %zu", ws_bytes, w.bytes);
@@ -644,7 +641,7 @@ int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& 
                            w.dRGB, w.dV0);
         IDN_HIP_CHECK(hipGetLastError());
     }
-    if (int e = bwd_tail(p, &gr, aud, expr, latent, acts, n, Pp, w, d_aud, d_expr, d_latent, s)) return e;
+    if (int e = bwd_tail(p, &gr, cond, acts, n, Pp, w, s)) return e;
     if (d_x) return launch_dx(p, w, n, Pp, d_x, s);
     return IDN_OK;
 }

@@ -169,6 +169,30 @@ def test_query_rays_matches_oracle(idn, dev):
     assert torch.equal(raw, raw2)  # same points, same encodings, same arithmetic
 
 
+@pytest.mark.parametrize("name,prec", [("f32", 0), ("bf16x3", 1), ("bf16", 2), ("fp16x3", 3), ("bf16x6", 4)])
+def test_query_points_equals_query_rays_in_every_arithmetic(idn, dev, name, prec):
+    """The points mode of every arithmetic's kernel (`query_points_fwd`; the other tests run it in fp32 alone): on
+    pts = o + d * z, rounded as the rays mode rounds it, and the rays' view directions it hands the encoding and the layers
+    the same fp32 inputs as `query_rays_fwd` on the rays and depths, so the outputs are the same bits.  3 rays x 43 samples
+    = 129 points: one full 128-point tile and a ragged tail of one point."""
+    dims = oracle.facenerf_dims()
+    params = scale_sigma(oracle.xavier_facenerf_params(7, dims))
+    syn = oracle.synthetic_frame(16, 16, seed=3, dims=dims)
+    ro, rd = oracle.camera_rays(16, 16, syn["focal"], syn["c2w"])
+    rays = oracle.ray_records(ro, rd, NEAR, FAR)[[0, 100, 255]].contiguous()
+    z = oracle.coarse_depths(rays[:, 6:7], rays[:, 7:8], 43).contiguous()
+    pts = (rays[:, None, 0:3] + rays[:, None, 3:6] * z[:, :, None]).contiguous()
+    assert pts.dtype == torch.float32 and pts.shape == (3, 43, 3)
+    sd = {k: v.to(dev).contiguous() for k, v in params.items()}
+    ps = idn.ops.params_struct(sd, dims["dim_aud"], dims["dim_expr"], dims["dim_latent"])
+    packed = idn.ops.pack_weights(ps, dev, prec)
+    folded = idn.ops.fold_conditioning(ps, syn["aud"].to(dev), syn["expr"].to(dev), syn["latent"].to(dev), dev)
+    by_rays = idn.ops.query_rays_fwd(packed, folded, rays.to(dev), z.to(dev), prec)
+    by_points = idn.ops.query_points_fwd(packed, folded, pts.to(dev), rays[:, 8:11].contiguous().to(dev), prec)
+    assert by_rays.shape == (3, 43, 4) and bool(torch.isfinite(by_rays).all()) and float(by_rays.abs().max()) > 0
+    assert torch.equal(by_points, by_rays), name
+
+
 # --------------------------------------------------------------------------- a1, a3
 def test_frame_rays_golden(idn, dev, golden):
     g = golden("frame32")
