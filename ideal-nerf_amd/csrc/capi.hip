@@ -509,6 +509,22 @@ int idealnerf_delta_chain(const idn_facenerf_params* p, int pipe, const float* a
                                     workspace_bytes, (hipStream_t)stream);
 }
 
+int idealnerf_composite_bwd(const float* raw, const float* z, const float* rays, const float* bc_rgb, int64_t n_rays,
+                            int n_samples, const float* g_rgb_map, const float* g_rgb_fg, const float* g_last_weight,
+                            const float* g_acc, float* d_rgb, int ld_rgb, float* d_sig, int ld_sig, float* d_norm, int ld_norm,
+                            void* stream) {
+    if (n_rays < 0) return fail(IDN_EINVAL, "composite_bwd: n_rays < 0");
+    if (n_rays == 0) return IDN_OK;
+    if (!raw || !z || !rays || !bc_rgb || !d_rgb || !d_sig) return fail(IDN_EINVAL, "composite_bwd: NULL pointer");
+    if ((uintptr_t)raw & 15) return fail(IDN_EINVAL, "composite_bwd: raw is not 16-byte aligned");
+    if (ld_rgb < 3 || ld_sig < 1 || (d_norm && ld_norm < 1))
+        return fail(IDN_EINVAL, "composite_bwd: row pitch %d / %d / %d below 3 / 1 / 1", ld_rgb, ld_sig, ld_norm);
+    if (n_rays > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "composite_bwd: n_rays %lld exceeds 2^31-1 per launch", (long long)n_rays);
+    const CompBwdArgs a{reinterpret_cast<const float4*>(raw), z, rays, bc_rgb, g_rgb_map, g_rgb_fg, g_last_weight, g_acc,
+                        d_rgb, ld_rgb, d_sig, ld_sig, (long)n_rays, n_samples, d_norm, ld_norm};
+    return launch_composite_bwd(a, (hipStream_t)stream);
+}
+
 void idealnerf_profile_begin(void) {
     g_prof_n = 0;
     g_prof_on = true;

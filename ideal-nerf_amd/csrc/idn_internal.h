@@ -410,6 +410,21 @@ struct PassBwd {
     size_t ws_bytes;
 };
 int launch_pass_bwd(const PassBwd& b, hipStream_t s);
+// The compositing backward, d(rgb_map, rgb_fg, last_weight, acc) -> d raw: the first launch of launch_pass_bwd, which calls this
+// function, and all of idealnerf_composite_bwd.
+struct CompBwdArgs {
+    const float4* raw; const float* z; const float* rays; const float* bc;
+    const float* g_rgb;  // [n,3] d rgb_map (may be null)
+    const float* g_fg;   // [n,3] d rgb_fg  (may be null)
+    const float* g_lw;   // [n]   d last_weight (may be null)
+    const float* g_acc;  // [n]   d acc_map (may be null)
+    float* d_rgb; int ld_rgb;    // row p = ray*S+s: d raw_rgb at d_rgb[p*ld_rgb + 0..2]
+    float* d_sig; int ld_sig;    // d raw_sigma at d_sig[p*ld_sig]
+    long n_rays; int S;
+    float* d_norm; int ld_norm;  // kNorm kernels only: dL / d |rays_d| = sum_{s < S-1} (dL / d dist_s) (z_{s+1} - z_s) at d_norm[ray*ld_norm]
+};
+// S outside [2, 512]: IDN_EUNSUPPORTED.  d_norm null: the kernels without the |rays_d| gradient.
+int launch_composite_bwd(const CompBwdArgs& a, hipStream_t s);
 // ray_grad.hip: d_x [n_rays * S, pts_ch + views_ch] (the input-row gradient of the pass's points) -> d_rays [n_rays, 11];
 // column 6 of d_rays holds dL / d |rays_d| on entry
 int launch_ray_grad(const float* d_x, int pts_ch, int views_ch, const float* rays, const float* z, int64_t n_rays, int S,

@@ -30,24 +30,18 @@ __device__ __forceinline__ double shfl_up_dd(double v, int delta) {
     hi = __shfl_up(hi, delta, 64);
     return __hiloint2double(hi, lo);
 }
+__device__ __forceinline__ double shfl_down_dd(double v, int delta) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl_down(lo, delta, 64);
+    hi = __shfl_down(hi, delta, 64);
+    return __hiloint2double(hi, lo);
+}
 __device__ __forceinline__ double shfl_xor_dd(double v, int mask) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __shfl_xor(lo, mask, 64);
     hi = __shfl_xor(hi, mask, 64);
     return __hiloint2double(hi, lo);
 }
-
-struct CompBwdArgs {
-    const float4* raw; const float* z; const float* rays; const float* bc;
-    const float* g_rgb;  // [n,3] d rgb_map (may be null)
-    const float* g_fg;   // [n,3] d rgb_fg  (may be null)
-    const float* g_lw;   // [n]   d last_weight (may be null)
-    const float* g_acc;  // [n]   d acc_map (may be null)
-    float* d_rgb; int ld_rgb;    // row p = ray*S+s: d raw_rgb at d_rgb[p*ld_rgb + 0..2]
-    float* d_sig; int ld_sig;    // d raw_sigma at d_sig[p*ld_sig]
-    long n_rays; int S;
-    float* d_norm; int ld_norm;  // kNorm kernels only: dL / d |rays_d| = sum_{s < S-1} (dL / d dist_s) (z_{s+1} - z_s) at d_norm[ray*ld_norm]
-};
 
 // kNorm: also the per-ray gradient of dists = dz * |rays_d| with respect to the norm (baseline.py:341-343; the ray's last
 // sample is left out: across its 1e10 spacing alpha is saturated).  The other outputs are the same instructions either way.
@@ -122,25 +116,29 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
             lsum += (double)dw[i] * (double)w[i];
         }
     }
-    // suffix sums of dw*w: total - inclusive prefix
-    double pin = lsum;
+    // suffix sums of dw*w, added up from the ray's far end: sum_{t > s} dw_t w_t then keeps its own relative precision however small
+    // it is beside the ray's total (as total - inclusive prefix it carried 1e-16 of the total, and a sample behind an opaque one
+    // got a d sigma of that size times dist instead of one that vanishes with its transmittance)
+    double lsfx = lsum;   // inclusive suffix over the lanes
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const double o = shfl_up_dd(pin, d);
-        if (lane >= d) pin += o;
+        const double o = shfl_down_dd(lsfx, d);
+        if (lane + d < 64) lsfx += o;
     }
-    double total = lsum;
+    double after = shfl_down_dd(lsfx, 1);  // sum over later lanes
+    if (lane == 63) after = 0.0;
+    double sfx[SPL];                       // sum_{t > s} dw_t w_t
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) total += shfl_xor_dd(total, m);
-    double before = pin - lsum;  // sum over earlier lanes
+    for (int i = SPL - 1; i >= 0; --i) {
+        sfx[i] = after;
+        after += (double)dw[i] * (double)w[i];   // (zero beyond the ray's end)
+    }
     double nsum = 0.0;           // kNorm: this lane's share of dL / d |rays_d|
 #pragma unroll
     for (int i = 0; i < SPL; ++i) {
         const int s = lane * SPL + i;
         if (s < S) {
-            before += (double)dw[i] * (double)w[i];          // inclusive up to s
-            const double suffix = total - before;            // sum_{t > s} dw_t w_t
-            const float dalpha = dw[i] * T[i] - (float)(suffix / (double)tf[i]);
+            const float dalpha = dw[i] * T[i] - (float)(sfx[i] / (double)tf[i]);
             const float dsig = (rw[i].w > 0.f) ? dalpha * ex[i] * dist[i] : 0.f;
             if constexpr (kNorm) {
                 if (s < S - 1)
@@ -442,9 +440,9 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
 static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, int64_t Pp, float* d_x, hipStream_t s);
 
 template <bool kNorm>
-static void launch_composite_bwd(const CompBwdArgs& a, int64_t n_rays, int S, hipStream_t s) {
-    const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-    switch ((S + 63) / 64) {
+static void launch_composite_bwd_spl(const CompBwdArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.n_rays + 3) / 4)), block(256);
+    switch ((a.S + 63) / 64) {
         case 1: hipLaunchKernelGGL((composite_bwd_kernel<1, kNorm>), grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL((composite_bwd_kernel<2, kNorm>), grid, block, 0, s, a); break;
         case 3: hipLaunchKernelGGL((composite_bwd_kernel<3, kNorm>), grid, block, 0, s, a); break;
@@ -454,6 +452,16 @@ static void launch_composite_bwd(const CompBwdArgs& a, int64_t n_rays, int S, hi
         case 7: hipLaunchKernelGGL((composite_bwd_kernel<7, kNorm>), grid, block, 0, s, a); break;
         default: hipLaunchKernelGGL((composite_bwd_kernel<8, kNorm>), grid, block, 0, s, a); break;
     }
+}
+
+// The compositing backward of a pass, and of idealnerf_composite_bwd: the bucket SPL = ceil(S / 64), the kNorm kernels where
+// a.d_norm is given.
+int launch_composite_bwd(const CompBwdArgs& a, hipStream_t s) {
+    if (a.S < 2 || a.S > 64 * kMaxSpl) return fail(IDN_EUNSUPPORTED, "composite_bwd: n_samples %d outside [2, %d]", a.S, 64 * kMaxSpl);
+    if (a.d_norm) launch_composite_bwd_spl<true>(a, s);
+    else launch_composite_bwd_spl<false>(a, s);
+    IDN_HIP_CHECK(hipGetLastError());
+    return IDN_OK;
 }
 
 // d_rays != nullptr (idealnerf_pass_bwd_rays): after the backward, the input-row gradient of the pass's points (into the
@@ -481,9 +489,7 @@ int launch_pass_bwd(const PassBwd& b, hipStream_t s) {
     {
         CompBwdArgs a{reinterpret_cast<const float4*>(b.raw), b.z, b.rays, b.bc, b.g_rgb, b.g_fg, b.g_lw, b.g_acc,
                       w.dRGB, 64, w.dV0 + kSigmaChannel, 256, (long)n_rays, S, d_rays ? d_rays + 6 : nullptr, IDN_RAY_FLOATS};
-        if (d_rays) launch_composite_bwd<true>(a, n_rays, S, s);
-        else launch_composite_bwd<false>(a, n_rays, S, s);
-        IDN_HIP_CHECK(hipGetLastError());
+        if (int e = launch_composite_bwd(a, s)) return e;
     }
     if (int e = bwd_tail(p, b.grads, b.cond, b.acts, P, Pp, w, s)) return e;
     if (d_rays) {

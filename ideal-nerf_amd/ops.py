@@ -702,6 +702,52 @@ def delta_chain(p, pipe, acts, d_rgb, dv0, max_blocks=0, dv21=None, da=None):
     return dv21, da, blocks.value
 
 
+def composite_bwd(raw, z, rays, bc, g_rgb=None, g_fg=None, g_lw=None, g_acc=None, d_rgb=None, d_sig=None, sig_col=0, d_norm=None,
+                  norm_col=0):
+    """Test aid: the compositing backward of a training pass alone (idealnerf_composite_bwd), through the dispatch a pass runs.
+        raw [n, S, 4], z [n, S], rays [n, 11], bc [n, 3];  g_* = dL/d (rgb_map [n, 3], rgb_fg [n, 3], last_weight [n], acc_map [n]),
+        each may be None
+        d_rgb [rows >= n S, ld_rgb >= 3]: columns 0..2 of row ray * S + s are WRITTEN with d raw rgb
+        d_sig [rows >= n S, ld_sig]: column sig_col of that row is WRITTEN with d raw sigma (d_sig may be d_rgb itself)
+        d_norm [n, ld_norm]: optional; column norm_col of row r is WRITTEN with dL / d |rays_d| (given: the kernels of a pass with
+        a ray gradient; None: the others)
+    With neither d_rgb nor d_sig, both go into one new [n, S, 4] tensor (pitches 4 and 4).  A pass itself runs d_rgb [p_pad, 64],
+    d_sig [p_pad, 256] at sig_col 128 and d_norm = d_rays [n, 11] at norm_col 6.  Returns (d_rgb, d_sig, d_norm) as given, or the
+    new tensor twice."""
+    lib = _lib.load()
+    E = IdealNerfError
+    if z is None:
+        raise E("composite_bwd: z is None")
+    _shape(z, "z", None, None)
+    n, S = z.shape
+    for t, name, shape in ((raw, "raw", (n, S, 4)), (rays, "rays", (n, RAY_FLOATS)), (bc, "bc_rgb", (n, 3)), (g_rgb, "g_rgb_map", (n, 3)),
+                           (g_fg, "g_rgb_fg", (n, 3)), (g_lw, "g_last_weight", (n,)), (g_acc, "g_acc", (n,)), (d_rgb, "d_rgb", (None, None)),
+                           (d_sig, "d_sig", (None, None)), (d_norm, "d_norm", (n, None))):
+        if t is None and name in ("raw", "rays", "bc_rgb"):
+            raise E(f"composite_bwd: {name} is None")
+        _shape(t, name, *shape)
+    if not 2 <= S <= 512:
+        raise E(f"composite_bwd: n_samples {S} outside [2, 512]")
+    if (d_rgb is None) != (d_sig is None):
+        raise E("composite_bwd: d_rgb and d_sig come together")
+    for t, name, col in ((d_sig, "sig_col", sig_col), (d_norm, "norm_col", norm_col)):
+        if isinstance(col, bool) or not isinstance(col, int) or col < 0 or (t is None and col != 0) or (t is not None and col >= t.shape[1]):
+            raise E(f"composite_bwd: {name} {col} is not a column of its matrix")
+    if d_rgb is not None and (d_rgb.shape[0] < n * S or d_sig.shape[0] < n * S or d_rgb.shape[1] < 3):
+        raise E(f"composite_bwd: d_rgb {list(d_rgb.shape)} / d_sig {list(d_sig.shape)} hold fewer than {n * S} rows or d_rgb fewer than 3 columns")
+    with _Launch(raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_rgb, d_sig, d_norm) as L:
+        ptrs = [_ptr(t, name) for t, name in ((raw, "raw"), (z, "z"), (rays, "rays"), (bc, "bc_rgb"))]   # raises for CPU tensors
+        grad_ptrs = [_ptr(t, name) for t, name in ((g_rgb, "g_rgb_map"), (g_fg, "g_rgb_fg"), (g_lw, "g_last_weight"), (g_acc, "g_acc"))]
+        if d_rgb is None:
+            d_rgb = d_sig = torch.empty((n, S, 4), dtype=torch.float32, device=L.device)
+            out = (d_rgb.data_ptr(), 4, d_rgb.data_ptr() + 12, 4)
+        else:
+            out = (_ptr(d_rgb, "d_rgb"), d_rgb.shape[1], _ptr(d_sig, "d_sig") + 4 * sig_col, d_sig.shape[1])
+        norm = (None, 0) if d_norm is None else (_ptr(d_norm, "d_norm") + 4 * norm_col, d_norm.shape[1])
+        check(lib.idealnerf_composite_bwd(*ptrs, n, S, *grad_ptrs, *out, *norm, L.stream))
+    return d_rgb, d_sig, d_norm
+
+
 AUDIO_NET_MAX_BWD_WINDOWS = 8
 
 

@@ -670,6 +670,25 @@ int idealnerf_delta_chain(const idn_facenerf_params* p, int pipe, const float* a
                           size_t workspace_bytes, void* stream);
 
 /*
+ * Test aid (no reference counterpart): the compositing backward of a training pass alone -- the first launch of
+ * idealnerf_pass_bwd*, through the same dispatch (one kernel per ceil(n_samples / 64) = 1..8, each with and without the
+ * |rays_d| gradient) -- so that tests/ can hold every element of d raw to fp64.
+ *   raw [n_rays, n_samples, 4] (16-byte aligned), z [n_rays, n_samples], rays [n_rays, 11], bc_rgb [n_rays, 3]: as idealnerf_pass_bwd.
+ *   g_rgb_map [n_rays, 3], g_rgb_fg [n_rays, 3], g_last_weight [n_rays], g_acc [n_rays]: dL / d output; each may be NULL (= zeros).
+ *   d_rgb, ld_rgb: WRITTEN, d raw rgb of point p = ray * n_samples + s at d_rgb[p * ld_rgb + 0..2] (ld_rgb >= 3);
+ *   d_sig, ld_sig: WRITTEN, d raw sigma of point p at d_sig[p * ld_sig] (ld_sig >= 1).  A pass runs ld_rgb = 64 and ld_sig = 256,
+ *           d_sig at column 128 of its [p_pad, 256] delta matrix; (4, 4) with d_sig = d_rgb + 3 fills one [n_rays, n_samples, 4] tensor.
+ *   d_norm, ld_norm: NULL, or WRITTEN with dL / d |rays_d| of ray r at d_norm[r * ld_norm] (a pass: column 6 of d_rays, pitch 11).
+ *           d_rgb and d_sig are the same bits either way.
+ * Nothing else is written.  n_rays == 0 writes nothing.  Argument errors are found before any HIP call: IDN_EINVAL (a NULL
+ * operand, a pitch below 3 / 1 / 1, raw unaligned), IDN_EUNSUPPORTED (n_samples outside [2, 512]).  Additive entry: the ABI version is unchanged.
+ */
+int idealnerf_composite_bwd(const float* raw, const float* z, const float* rays, const float* bc_rgb, int64_t n_rays,
+                            int n_samples, const float* g_rgb_map, const float* g_rgb_fg, const float* g_last_weight,
+                            const float* g_acc, float* d_rgb, int ld_rgb, float* d_sig, int ld_sig, float* d_norm, int ld_norm,
+                            void* stream);
+
+/*
  * AudioNet.forward (models/audio_net.py:43-69: the per-frame audio latent of audio_exp_nerf.py:258-259, or of the eight windows
  * under the attention smoother, :235-257) as ONE kernel, and its backward as one: windows [n, 16, 29] (win_size 16) ->
  * out [n, dim_aud].  Parameters in nn.Conv1d / nn.Linear layout ([C_out, C_in, 3] / [out, in], fp32, contiguous):

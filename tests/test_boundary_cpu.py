@@ -266,6 +266,29 @@ def test_c_abi_argument_errors_without_gpu(idn):
     for kw in (dict(nbytes=dc_bytes - 1), dict(nbytes=0), dict(ws=None)):
         rc, msg = chain(pipe=1, p_pad=1 << 24, **kw)
         assert rc == -4 and b"workspace" in msg, kw
+    # the compositing backward alone: n_rays, then NULL operands, alignment, pitches, n_samples; the four gradients may be NULL
+    def comp(raw=4096, z=8192, rays=12288, bc=16384, n=4, S=64, g=(None, None, None, None), d_rgb=20480, ld_rgb=4, d_sig=20492, ld_sig=4,
+             d_norm=None, ld_norm=0):
+        rc = lib.idealnerf_composite_bwd(raw, z, rays, bc, n, S, *g, d_rgb, ld_rgb, d_sig, ld_sig, d_norm, ld_norm, None)
+        return rc, lib.idealnerf_last_error()
+
+    rc, msg = comp(n=-1)
+    assert rc == -1 and b"n_rays < 0" in msg
+    assert comp(n=0)[0] == 0 and comp(n=0, raw=None, d_rgb=None, S=0)[0] == 0          # nothing to do: OK, as idealnerf_pass_bwd
+    for name in ("raw", "z", "rays", "bc", "d_rgb", "d_sig"):
+        rc, msg = comp(**{name: None})
+        assert rc == -1 and b"composite_bwd: NULL" in msg, name
+    rc, msg = comp(raw=4096 + 4)
+    assert rc == -1 and b"aligned" in msg
+    for kw in (dict(ld_rgb=2), dict(ld_rgb=0), dict(ld_sig=0), dict(ld_sig=-4), dict(d_norm=24576, ld_norm=0), dict(d_norm=24576, ld_norm=-11)):
+        rc, msg = comp(**kw)
+        assert rc == -1 and b"row pitch" in msg, kw
+    rc, msg = comp(n=1 << 31)
+    assert rc == -2 and b"2^31-1" in msg
+    for S in (-1, 0, 1, 513, 1024):     # with and without d_norm, with and without gradients: refused before the launch
+        for kw in ({}, dict(d_norm=24576, ld_norm=11), dict(g=(4096, 4096, 4096, 4096), ld_rgb=64, ld_sig=256)):
+            rc, msg = comp(S=S, **kw)
+            assert rc == -2 and b"n_samples" in msg and b"[2, 512]" in msg, (S, kw)
 
 
 def test_product_path_refuses_cpu_tensors(idn):
@@ -1007,3 +1030,27 @@ def test_ops_validate_shapes_before_the_c_call(idn):
             ({}, "must live on the GPU"), (dict(dv21=torch.zeros(256, 256), da=torch.zeros(8, 256, 256)), "must live on the GPU")):
         with pytest.raises(E, match=match):
             chain(**kw)
+    # the compositing backward alone: every shape, column and device, on CPU tensors
+    def comp(n=4, S=64, **kw):
+        args = dict(raw=torch.zeros(n, S, 4), z=torch.zeros(n, S), rays=torch.zeros(n, 11), bc=torch.zeros(n, 3))
+        args.update(kw)
+        return ops.composite_bwd(**args)
+
+    m4, m64, m256 = torch.zeros(256, 4), torch.zeros(256, 64), torch.zeros(256, 256)
+    for kw, match in (
+            (dict(z=torch.zeros(4 * 64)), r"z must be \[\*, \*\]"), (dict(raw=torch.zeros(4, 64, 3)), r"raw must be \[4, 64, 4\]"),
+            (dict(raw=None), "raw is None"), (dict(z=None), "z is None"), (dict(rays=torch.zeros(4, 8)), r"rays must be \[4, 11\]"), (dict(bc=torch.zeros(3, 3)), r"bc_rgb must be \[4, 3\]"),
+            (dict(g_rgb=torch.zeros(4)), r"g_rgb_map must be \[4, 3\]"), (dict(g_fg=torch.zeros(4, 4)), r"g_rgb_fg must be \[4, 3\]"),
+            (dict(g_lw=torch.zeros(4, 1)), r"g_last_weight must be \[4\]"), (dict(g_acc=torch.zeros(5)), r"g_acc must be \[4\]"),
+            (dict(S=1), "outside"), (dict(S=513), "outside"),
+            (dict(d_rgb=m4), "come together"), (dict(d_sig=m4), "come together"),
+            (dict(d_rgb=torch.zeros(4, 64, 4), d_sig=m4), r"d_rgb must be \[\*, \*\]"),
+            (dict(d_rgb=torch.zeros(255, 4), d_sig=m4), "fewer than 256 rows"), (dict(d_rgb=m4, d_sig=torch.zeros(255, 4)), "fewer than 256 rows"),
+            (dict(d_rgb=torch.zeros(256, 2), d_sig=m4), "fewer than 3 columns"),
+            (dict(d_rgb=m4, d_sig=m4, sig_col=4), "sig_col 4"), (dict(d_rgb=m64, d_sig=m256, sig_col=256), "sig_col 256"),
+            (dict(d_rgb=m4, d_sig=m4, sig_col=-1), "sig_col -1"), (dict(sig_col=3), "sig_col 3"), (dict(norm_col=6), "norm_col 6"),
+            (dict(d_norm=torch.zeros(3, 11)), r"d_norm must be \[4, \*\]"), (dict(d_norm=torch.zeros(4, 11), norm_col=11), "norm_col 11"),
+            ({}, "must live on the GPU"), (dict(d_rgb=m64, d_sig=m256, sig_col=128, d_norm=torch.zeros(4, 11), norm_col=6), "must live on the GPU"),
+            (dict(raw=torch.zeros(4, 64, 4, dtype=torch.float64)), "must live on the GPU")):
+        with pytest.raises(E, match=match):
+            comp(**kw)
