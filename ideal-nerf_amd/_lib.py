@@ -151,6 +151,7 @@ PROTOTYPES = {
     "idealnerf_audio_net_bwd": (C.c_int, [C.POINTER(AudioNetParams), C.POINTER(AudioNetGrads), fp, fp, fp, C.c_int, fp]),
     "idealnerf_train_acts_floats": (C.c_size_t, [C.c_int64]),
     "idealnerf_query_rays_train_fwd": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int64, C.c_int, fp, fp, fp]),
+    "idealnerf_query_rays_train_fwd_ch": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int64, C.c_int, C.c_int, C.c_int, fp, fp, fp]),
     "idealnerf_pass_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "idealnerf_pass_bwd": (C.c_int, [C.POINTER(FaceNerfParams), C.POINTER(FaceNerfGrads), fp, fp, fp, fp, fp, fp, fp,
                                      fp, C.c_int64, C.c_int, fp, fp, fp, fp, fp, fp, fp, C.c_size_t, fp]),

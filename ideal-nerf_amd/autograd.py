@@ -42,7 +42,7 @@ def _train_code():
 
 def _train_query(net, folded, rays, z):
     prec_name, code = _train_code()
-    return ops.query_rays_train_fwd(net.packed_weights(prec_name), folded, rays, z, code)
+    return ops.query_rays_train_fwd(net.packed_weights(prec_name), folded, rays, z, code, net.input_xyz_ch, net.input_views_ch)
 
 
 def _pass_bwd(net, aud, expr, latent, acts, raw, z, rays, bc, g_rgb, g_fg, g_lw, g_acc, d_aud, d_latent, frozen=False,

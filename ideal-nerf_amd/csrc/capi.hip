@@ -337,15 +337,23 @@ size_t idealnerf_train_acts_floats(int64_t n_points) {
 int idealnerf_query_rays_train_fwd(const float* packed, const float* folded, int precision, const float* rays,
                                    const float* z, int64_t n_rays, int n_samples, float* raw, float* acts,
                                    void* stream) {
+    return idealnerf_query_rays_train_fwd_ch(packed, folded, precision, rays, z, n_rays, n_samples, IDN_PTS_CH, IDN_VIEWS_CH, raw, acts,
+                                             stream);
+}
+
+int idealnerf_query_rays_train_fwd_ch(const float* packed, const float* folded, int precision, const float* rays,
+                                      const float* z, int64_t n_rays, int n_samples, int pts_ch, int views_ch, float* raw,
+                                      float* acts, void* stream) {
     if (int e = check_precision_train(precision)) return e;
+    if (int e = check_widths(pts_ch, views_ch)) return e;
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes");
     if (n_rays == 0) return IDN_OK;
     if (!packed || !folded || !rays || !z || !raw || !acts) return fail(IDN_EINVAL, "NULL pointer");
     const int64_t p_pad = (n_rays * n_samples + 127) / 128 * 128;
     // (both activation-saving kernels write every row of the slab, the p_pad - n padding rows included -- they repeat the last
     //  point, and their deltas are zero: tests/test_hip_parity.py::test_train_forward_defines_every_row_of_the_activation_slab)
-    return launch_mlp(precision, mlp_saving(mlp_rays(packed, folded, rays, z, n_rays, n_samples, raw), acts, p_pad), (hipStream_t)stream,
-                      MlpGate{});
+    return launch_mlp(precision, mlp_saving(mlp_rays(packed, folded, rays, z, n_rays, n_samples, raw), acts, p_pad, pts_ch, views_ch),
+                      (hipStream_t)stream, MlpGate{});
 }
 
 size_t idealnerf_pass_bwd_workspace_bytes(int64_t n_rays, int n_samples) {

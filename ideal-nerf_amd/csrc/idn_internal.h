@@ -228,7 +228,8 @@ struct MlpArgs {
     float* raw;         // [n_points, 4]
     float* acts;        // training only: activation slab (act_off() matrices of p_pad rows), else null
     long p_pad;
-    int x_pts_ch, x_views_ch;   // kModeX: the network's encoding widths (3..63, 3..27); the other modes do not read them
+    int x_pts_ch, x_views_ch;   // the network's encoding widths (3..63, 3..27): kModeX reads rows of them; a saving launch of the
+                                // other modes stores zeros in the slab's x0 / dir columns beyond them; else they are not read
 };
 // the colour-gated fp32 rays kernel's arguments (the other kernels' stay as they are)
 struct MlpGateArgs : MlpArgs {
@@ -265,6 +266,11 @@ inline MlpArgs mlp_points(const float* packed, const float* folded, const float*
 inline MlpArgs mlp_saving(MlpArgs a, float* acts, int64_t p_pad) {
     a.acts = acts; a.p_pad = (long)p_pad;
     return a;
+}
+// ... of a rays- or pts-mode record for a network of these widths (mlp_rows carries its own)
+inline MlpArgs mlp_saving(MlpArgs a, float* acts, int64_t p_pad, int pts_ch, int views_ch) {
+    a.x_pts_ch = pts_ch; a.x_views_ch = views_ch;
+    return mlp_saving(a, acts, p_pad);
 }
 // fp32 rays-mode inference only: the colour-gated kernel; counters: device int64 [2] (tiles, skipped) it adds to, or null
 struct MlpGate { int on; int64_t* counters; };

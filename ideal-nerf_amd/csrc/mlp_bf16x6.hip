@@ -150,11 +150,16 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x6_kernel(MlpArgs a) {
             if constexpr (SAVE) {   // every row of the slab, padding rows included (they repeat the last point)
                 float* x0 = a.acts + act_off(kActX0) * a.p_pad + P * 64 + 4 * h;
                 float* dr = a.acts + act_off(kActDir) * a.p_pad + P * 64 + 4 * h;
+                const int pch = a.x_pts_ch - 4 * h, vch = a.x_views_ch - 4 * h;
                 static_for<8>([&](auto G) {
                     constexpr int g = decltype(G)::value;
-                    *reinterpret_cast<f32x4*>(x0 + 8 * g) = f32x4{pe_f[g][0], pe_f[g][1], pe_f[g][2], pe_f[g][3]};
+                    *reinterpret_cast<f32x4*>(x0 + 8 * g) =
+                        f32x4{slab_col<MODE, 8 * g + 0>(pe_f[g][0], pch), slab_col<MODE, 8 * g + 1>(pe_f[g][1], pch),
+                              slab_col<MODE, 8 * g + 2>(pe_f[g][2], pch), slab_col<MODE, 8 * g + 3>(pe_f[g][3], pch)};
                     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (g < 4) v = f32x4{pd_f[g][0], pd_f[g][1], pd_f[g][2], pd_f[g][3]};
+                    if constexpr (g < 4)
+                        v = f32x4{slab_col<MODE, 8 * g + 0>(pd_f[g][0], vch), slab_col<MODE, 8 * g + 1>(pd_f[g][1], vch),
+                                  slab_col<MODE, 8 * g + 2>(pd_f[g][2], vch), slab_col<MODE, 8 * g + 3>(pd_f[g][3], vch)};
                     *reinterpret_cast<f32x4*>(dr + 8 * g) = v;
                 });
             }

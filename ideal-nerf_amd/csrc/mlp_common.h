@@ -248,7 +248,8 @@ struct NoSide {
 // The phase frac(x_a / 2pi) is kept as 64-bit fixed point (from fp64, once per axis); band b is
 // a funnel shift (v_alignbit), cos is a quarter-turn offset, the reduction to the nearest half
 // turn and the sign are integer operations, and ONE odd polynomial on |x| <= pi/2 serves every
-// feature (max |diff| to torch.sin/cos on CPU 1.2e-7 on every band, <= 2 ulp at 1.0).  K0 + 4 has
+// feature (max |diff| to torch.sin/cos on CPU 1.2e-7 on every band, <= 2 ulp at 1.0; tests/test_pe_gpu.py holds every
+// element to 2^-22 + 2^b |x| 2^-51 of fp64 sin / cos, measured worst 1.09e-7).  K0 + 4 has
 // axis (a + 1) % 3, so the upper half stores its axes rotated by one and both halves index axis
 // K0 % 3; band and sc of the two halves enter as per-lane shift / offset operands.
 // ---------------------------------------------------------------------------
@@ -423,6 +424,15 @@ __device__ __forceinline__ void input_features(const MlpArgs& a, long Pc, int h,
         use([&](auto K) { return pe_slot<decltype(K)::value, 10>(axp, pln); },
             [&](auto K) { return pe_slot<decltype(K)::value, 4>(axd, pln); });
     }
+}
+
+// Column K0 + 4h of the slab's x0 / dir matrix for an encoding of `ch` columns (ch_h = ch - 4h): the feature where the network
+// has the column, +0.0 beyond it -- a narrow network's slab is the same whichever mode filled it (kModeX reads rows that end
+// at `ch` and has the zeros already).
+template <int MODE, int K0>
+__device__ __forceinline__ float slab_col(float v, int ch_h) {
+    if constexpr (MODE == kModeX) return v;
+    else return K0 < ch_h ? v : 0.0f;
 }
 
 // "Unit off" bits of a tile's 16 pre-activations pushed into mask dword T / 2 (idn_internal.h "ReLU masks"): a unit is off

@@ -188,15 +188,19 @@ __global__ __launch_bounds__(256, 1) void mlp_f32_kernel(std::conditional_t<GATE
             {   // every row of the slab, padding included (see SaveSide)
                 float* x0 = a.acts + act_off(kActX0) * a.p_pad + P * 64 + 4 * h;
                 float* dr = a.acts + act_off(kActDir) * a.p_pad + P * 64 + 4 * h;
+                const int pch = a.x_pts_ch - 4 * h, vch = a.x_views_ch - 4 * h;
                 static_for<8>([&](auto G) {
                     constexpr int g = decltype(G)::value;
-                    f32x4 v = {pe[g][0], pe[g][1], pe[g][2], pe[g][3]};
+                    f32x4 v = {slab_col<MODE, 8 * g + 0>(pe[g][0], pch), slab_col<MODE, 8 * g + 1>(pe[g][1], pch),
+                               slab_col<MODE, 8 * g + 2>(pe[g][2], pch), slab_col<MODE, 8 * g + 3>(pe[g][3], pch)};
                     *reinterpret_cast<f32x4*>(x0 + 8 * g) = v;
                 });
                 static_for<8>([&](auto G) {
                     constexpr int g = decltype(G)::value;
                     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (g < 4) v = f32x4{pd[g][0], pd[g][1], pd[g][2], pd[g][3]};
+                    if constexpr (g < 4)
+                        v = f32x4{slab_col<MODE, 8 * g + 0>(pd[g][0], vch), slab_col<MODE, 8 * g + 1>(pd[g][1], vch),
+                                  slab_col<MODE, 8 * g + 2>(pd[g][2], vch), slab_col<MODE, 8 * g + 3>(pd[g][3], vch)};
                     *reinterpret_cast<f32x4*>(dr + 8 * g) = v;
                 });
             }

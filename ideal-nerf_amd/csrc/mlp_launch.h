@@ -36,7 +36,7 @@ inline int launch_mlp_kernels(const MlpKernels& k, LaunchSetup& setup, const Mlp
     const bool saving = a.acts != nullptr;
     if (gate.on && (saving || mode != kModeRays || !k.gated))
         return fail(IDN_EUNSUPPORTED, "the colour gate is built for the rays-mode inference launch");
-    if (mode == kModeX && !widths_ok(a.x_pts_ch, a.x_views_ch))
+    if ((mode == kModeX || saving) && !widths_ok(a.x_pts_ch, a.x_views_ch))
         return fail(IDN_EINVAL, "row widths %d / %d outside 3 + 6 L, L <= %d / %d", a.x_pts_ch, a.x_views_ch, IDN_MAX_MULTIRES, IDN_MAX_MULTIRES_VIEWS);
     const MlpKernels::Cell& c = k.cell[mode][saving];
     if (!c.kernel) return fail(IDN_EUNSUPPORTED, "%s", k.no_saving);

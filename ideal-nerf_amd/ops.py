@@ -236,18 +236,20 @@ def facenerf_bwd(p, grads, aud, expr, latent, acts, g_out, d_x=None, d_aud=None,
     return grads
 
 
-def query_rays_train_fwd(packed, folded, rays, z, precision=_lib.IDN_PREC_BF16X6):
-    """query_rays_fwd that also records the backward's activation slab (idealnerf_query_rays_train_fwd):
-    -> (raw [n, S, 4], acts [idealnerf_train_acts_floats(n * S)])."""
+def query_rays_train_fwd(packed, folded, rays, z, precision=_lib.IDN_PREC_BF16X6, pts_ch=PTS_CH, views_ch=VIEWS_CH):
+    """query_rays_fwd that also records the backward's activation slab (idealnerf_query_rays_train_fwd_ch):
+    -> (raw [n, S, 4], acts [idealnerf_train_acts_floats(n * S)]).  pts_ch / views_ch: the widths of the network `packed`
+    is the stream of; the slab's x0 / dir matrices hold zeros beyond them."""
     lib = _lib.load()
+    check_input_channels(pts_ch, views_ch)
     _shape(z, "z", None, None)
     n, S = z.shape
     _shape(rays, "rays", n, RAY_FLOATS)
     with _Launch(packed, folded, rays, z) as L:
         raw = torch.empty((n, S, 4), dtype=torch.float32, device=z.device)
         acts = torch.empty(lib.idealnerf_train_acts_floats(n * S), dtype=torch.float32, device=z.device)
-        check(lib.idealnerf_query_rays_train_fwd(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(rays, "rays"),
-                                                 _ptr(z, "z"), n, S, raw.data_ptr(), acts.data_ptr(), L.stream))
+        check(lib.idealnerf_query_rays_train_fwd_ch(_ptr(packed, "packed"), _ptr(folded, "folded"), precision, _ptr(rays, "rays"),
+                                                    _ptr(z, "z"), n, S, pts_ch, views_ch, raw.data_ptr(), acts.data_ptr(), L.stream))
     return raw, acts
 
 

@@ -446,6 +446,12 @@ size_t idealnerf_train_acts_floats(int64_t n_points);
 int idealnerf_query_rays_train_fwd(const float* packed, const float* folded, int precision, const float* rays,
                                    const float* z, int64_t n_rays, int n_samples, float* raw, float* acts,
                                    void* stream);
+/* The same for a network of pts_ch / views_ch input columns (3 + 6 multires each, as idealnerf_facenerf_fwd_ch takes them):
+ * the slab's x0 / dir matrices hold the network's own columns and zeros beyond them, as idealnerf_facenerf_train_fwd_ch
+ * leaves them.  raw is the same either way (the stream holds zeros in those columns); the entry above is this one at 63 / 27. */
+int idealnerf_query_rays_train_fwd_ch(const float* packed, const float* folded, int precision, const float* rays,
+                                      const float* z, int64_t n_rays, int n_samples, int pts_ch, int views_ch, float* raw,
+                                      float* acts, void* stream);
 
 /* Gradient tensors, same shapes/layout as idn_facenerf_params (every entry is overwritten,
  * including the conditioning columns). */
