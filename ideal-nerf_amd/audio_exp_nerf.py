@@ -29,6 +29,25 @@ def init_weights(m):
         m.bias.data.fill_(0.01)
 
 
+def reference_keys(out, with_fg, Ni, retraw, taps):
+    """ops.render_rays_fwd's dict under the reference's key names, in the order its render_rays fills them (``with_fg``: the
+    torso variant's rgb_map_fg / rgb_map_fg0 / last_weight0, NeRFs/TorsoNeRF/train_torso.py:326-345)."""
+    ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
+    if with_fg:
+        ret['rgb_map_fg'] = out['rgb_fg']
+    if retraw:
+        ret['raw'] = out['tap_raw_fine'] if Ni > 0 else out['tap_raw_coarse']
+    if Ni > 0:
+        for k in ('rgb0', 'disp0', 'acc0', 'z_std', 'last_weight'):
+            ret[k] = out[k]
+        if with_fg:
+            ret['last_weight0'] = out['last_weight0']
+            ret['rgb_map_fg0'] = out['rgb_fg0']
+    if taps:
+        ret.update({k: v for k, v in out.items() if k.startswith('tap_')})
+    return ret
+
+
 class Network(nn.Module):
     # True: perturb > 0 renders without autograd (the reference's default flags, also in eval) draw their random offsets inside
     # the kernels instead of as torch.rand tensors (same distribution, this library's own numbers; see _render).  Opt-in:
@@ -184,15 +203,7 @@ class Network(nn.Module):
         else:
             n, dev = frame.nrows * frame.W, bc_rgb.device
         S, Ni = args.N_samples, args.N_importance
-        draws = None
-        if self.in_kernel_draws and perturb > 0. and not pytest:
-            # the frame's stratified offsets and importance draws are made INSIDE the kernels (idn_render_args.rng_mode): one seed
-            # per call from torch's CPU generator (so torch.manual_seed governs it, and equally seeded ranks rendering row bands of
-            # one frame draw from one table: a ray's row in it is its pixel index); no [n, S] / [n, Ni] random tensors exist
-            draws = (int(torch.randint(0, 2 ** 62, (1,)).item()), 0 if frame is None else frame.row0 * frame.W)
-            t_rand, u = None, None
-        else:
-            t_rand, u = self.draw_randoms(n, S, Ni, perturb, pytest, dev)
+        draws, t_rand, u = self._draws(n, S, Ni, perturb, pytest, dev, 0 if frame is None else frame.row0 * frame.W)
         from .helper import draw_sigma_noise
         # raw2outputs draws its noise per call, the coarse one first (baseline.py:353-361; numpy re-seeded each time under pytest)
         noise_c = draw_sigma_noise((n, S), raw_noise_std, pytest, dev)
@@ -209,20 +220,7 @@ class Network(nn.Module):
                                       precision=coarse.prec_code, precision_fine=fine.prec_code if Ni > 0 else None,
                                       lindisp=lindisp, white_bkgd=white_bkgd, noise_coarse=noise_c, noise_fine=noise_f, frame=frame,
                                       draws=draws)
-        ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
-        if with_fg:
-            ret['rgb_map_fg'] = out['rgb_fg']
-        if retraw:
-            ret['raw'] = out['tap_raw_fine'] if Ni > 0 else out['tap_raw_coarse']
-        if Ni > 0:
-            for k in ('rgb0', 'disp0', 'acc0', 'z_std', 'last_weight'):
-                ret[k] = out[k]
-            if with_fg:
-                ret['last_weight0'] = out['last_weight0']
-                ret['rgb_map_fg0'] = out['rgb_fg0']
-        if taps:
-            ret.update({k: v for k, v in out.items() if k.startswith('tap_')})
-        return ret
+        return reference_keys(out, with_fg, Ni, retraw, taps)
 
     # ---- ray cull (cull.py): opt-in empty-space skipping of full-frame inference renders ----
     def set_cull(self, head=None, torso=None):
@@ -253,11 +251,7 @@ class Network(nn.Module):
             names += ['rgb_fg'] + (['last_weight0', 'rgb_fg0'] if Ni > 0 else [])
 
         def render_live(rays, bc_live, n):
-            if self.in_kernel_draws and perturb > 0. and not pytest:
-                draws, t_rand, u = (int(torch.randint(0, 2 ** 62, (1,)).item()), 0), None, None
-            else:
-                draws = None
-                t_rand, u = self.draw_randoms(n, S, Ni, perturb, pytest, dev)
+            draws, t_rand, u = self._draws(n, S, Ni, perturb, pytest, dev, 0)
             fc = coarse.folded_bias(aud_para, expr, latent_code)
             ff = fine.folded_bias(aud_para, expr, latent_code) if Ni > 0 else None
             return ops.render_rays_fwd(rays, bc_live, coarse.packed_weights(), fc, fine.packed_weights() if Ni > 0 else None, ff,
@@ -266,16 +260,16 @@ class Network(nn.Module):
 
         with torch.no_grad():
             out = cull.render_culled(grid, frame, bc_rgb, render_live, names)
-        ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
-        if with_fg:
-            ret['rgb_map_fg'] = out['rgb_fg']
-        if Ni > 0:
-            for k in ('rgb0', 'disp0', 'acc0', 'z_std', 'last_weight'):
-                ret[k] = out[k]
-            if with_fg:
-                ret['last_weight0'] = out['last_weight0']
-                ret['rgb_map_fg0'] = out['rgb_fg0']
-        return ret
+        return reference_keys(out, with_fg, Ni, retraw=False, taps=False)   # (cull.refuse: neither is rendered culled)
+
+    def _draws(self, n, S, Ni, perturb, pytest, dev, ray0):
+        """-> (draws, t_rand, u) of one ops.render_rays_fwd call: either `draws = (seed, ray0)` or draw_randoms' tensors."""
+        if self.in_kernel_draws and perturb > 0. and not pytest:
+            # the call's stratified offsets and importance draws are made INSIDE the kernels (idn_render_args.rng_mode): one seed
+            # per call from torch's CPU generator (so torch.manual_seed governs it, and equally seeded ranks rendering row bands of
+            # one frame draw from one table: a ray's row in it is its pixel index); no [n, S] / [n, Ni] random tensors exist
+            return (int(torch.randint(0, 2 ** 62, (1,)).item()), ray0), None, None
+        return (None,) + self.draw_randoms(n, S, Ni, perturb, pytest, dev)
 
     @staticmethod
     def draw_randoms(n, S, Ni, perturb, pytest, dev):
@@ -326,29 +320,30 @@ class Network(nn.Module):
                             rows=None):
         if ndc or not use_viewdirs:
             raise NotImplementedError("ndc=True / use_viewdirs=False are dead in the reference (SURVEY 8 a1)")
-        dev = self.face_nerf_coarse.alpha_linear.weight.device
-        if render_poses is not None:
-            # get_rays + the [o, d, near, far, viewdir] records (:396-427) happen on the device inside the render call
-            # (idealnerf_render_frame_fwd): the camera travels as 12 floats, no [H W, 11] tensor exists
-            row0, nrows = (0, H) if rows is None else (rows[0], rows[1] - rows[0])
-            frame = ops.make_frame(render_poses.detach().cpu(), H, W, focal, near, far, row0, nrows)
-            bc = bc_rgb[row0:row0 + nrows].reshape(-1, 3)
-            sh = (nrows, W, 3)
-            all_ret = self._batchify(None, bc, aud_para, latent_code, expr, self.face_nerf_coarse, self.face_nerf_fine, False, chunk,
-                                     frame=frame)
-        else:
-            rays_o, rays_d = rays
-            sh = rays_d.shape
-            rays_o = rays_o.reshape(-1, 3).float()
-            rays_d = rays_d.reshape(-1, 3).float()
-            viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
-            rec = torch.cat([rays_o, rays_d, near * torch.ones_like(rays_d[..., :1]),
-                             far * torch.ones_like(rays_d[..., :1]), viewdirs], -1)
-            # (batchify_rays' body, called by that name: a variant's batchify_rays has upstream's signature of its own class)
-            all_ret = self._batchify(rec, bc_rgb, aud_para, latent_code, expr, self.face_nerf_coarse, self.face_nerf_fine, False, chunk)
+        rec, frame, bc, sh = self._ray_inputs(H, W, focal, near, far, render_poses, rays, bc_rgb, rows)
+        # (batchify_rays' body, called by that name: a variant's batchify_rays has upstream's signature of its own class)
+        all_ret = self._batchify(rec, bc, aud_para, latent_code, expr, self.face_nerf_coarse, self.face_nerf_fine, False, chunk, frame=frame)
         for k in all_ret:
             all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
         k_extract = ['rgb_map', 'disp_map', 'acc_map', 'last_weight']
         ret_list = [all_ret[k] for k in k_extract]  # KeyError('last_weight') when N_importance == 0, as upstream (:437)
         ret_dict = {k: all_ret[k] for k in all_ret if k not in k_extract}
         return ret_list + [ret_dict]
+
+    @staticmethod
+    def _ray_inputs(H, W, focal, near, far, render_poses, rays, bc_rgb, rows):
+        """What a full-frame or a ray-batch render call feeds `_batchify` -> (rec or None, frame or None, bc, sh); sh[:-1] is
+        the shape the outputs are given."""
+        if render_poses is not None:
+            # get_rays + the [o, d, near, far, viewdir] records (:396-427) happen on the device inside the render call
+            # (idealnerf_render_frame_fwd): the camera travels as 12 floats, no [H W, 11] tensor exists
+            row0, nrows = (0, H) if rows is None else (rows[0], rows[1] - rows[0])
+            frame = ops.make_frame(render_poses.detach().cpu(), H, W, focal, near, far, row0, nrows)
+            return None, frame, bc_rgb[row0:row0 + nrows].reshape(-1, 3), (nrows, W, 3)
+        rays_o, rays_d = rays
+        sh = rays_d.shape
+        rays_o, rays_d = rays_o.reshape(-1, 3).float(), rays_d.reshape(-1, 3).float()
+        viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
+        rec = torch.cat([rays_o, rays_d, near * torch.ones_like(rays_d[..., :1]),
+                         far * torch.ones_like(rays_d[..., :1]), viewdirs], -1)
+        return rec, None, bc_rgb, sh

@@ -90,6 +90,23 @@ ProfScope::~ProfScope() {
     if (slot >= 0) (void)hipEventRecord(g_prof_ev[slot][1], s);
 }
 
+template <class T> static T* off(T* p, int64_t elems) { return p ? p + elems : p; }
+// Where one compositing of the internal pass starting at ray r0 writes.  kCoarseFinal: the only compositing of a render without
+// importance samples, into the render's maps; kCoarse: the one in front of a fine pass, into the *0 maps; kFine: the last one.
+enum PassLevel { kCoarseFinal, kCoarse, kFine };
+static idn_composite_out pass_out(const idn_render_args* a, int64_t r0, PassLevel level) {
+    const bool c0 = level == kCoarse;
+    idn_composite_out o = {};
+    o.rgb_map = off(c0 ? a->rgb0 : a->rgb_map, r0 * 3);
+    o.disp_map = off(c0 ? a->disp0 : a->disp_map, r0);
+    o.acc_map = off(c0 ? a->acc0 : a->acc_map, r0);
+    o.depth_map = c0 ? nullptr : off(a->depth_map, r0);
+    o.weights = level == kFine ? off(a->tap_weights_fine, r0 * (a->n_samples + a->n_importance)) : off(a->tap_weights_coarse, r0 * a->n_samples);
+    o.rgb_fg = off(c0 ? a->rgb_fg0 : a->rgb_fg, r0 * 3);
+    o.last_weight = off(c0 ? a->last_weight0 : a->last_weight, r0);
+    return o;
+}
+
 }  // namespace idn
 
 using namespace idn;
@@ -174,7 +191,7 @@ int idealnerf_frame_rays(const float* c2w, int H, int W, float focal, float cx, 
     if (!c2w || !rays_out) return fail(IDN_EINVAL, "NULL pointer");
     if (H <= 0 || W <= 0 || row0 < 0 || nrows < 0 || row0 + nrows > H) return fail(IDN_EINVAL, "bad frame/rows");
     if (nrows == 0) return IDN_OK;
-    return launch_frame_rays(c2w, H, W, focal, cx, cy, near_, far_, row0, nrows, rays_out, (hipStream_t)stream);
+    return launch_frame_rays_pixels(c2w, H, W, focal, cx, cy, near_, far_, (int64_t)row0 * W, nrows * W, rays_out, (hipStream_t)stream);
 }
 
 int idealnerf_philox_uniform(uint64_t seed, int which, int64_t row0, int64_t n_rows, int n_cols, float* out, void* stream) {
@@ -250,7 +267,7 @@ int idealnerf_coarse_depths(const float* rays, const float* t_vals, const float*
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes");
     if (n_rays == 0) return IDN_OK;
     if (!rays || !t_vals || !z) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_coarse_depths(rays, t_vals, t_rand, n_rays, n_samples, lindisp, z, (hipStream_t)stream);
+    return launch_coarse_depths(rays, t_vals, t_rand, n_rays, n_samples, lindisp, z, Draws{}, (hipStream_t)stream);
 }
 
 size_t idealnerf_audio_net_saved_floats(int n_windows) { return audio_net_saved_floats(n_windows); }
@@ -285,7 +302,7 @@ int idealnerf_composite_fwd(const float* raw, const float* z, const float* rays,
     if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
     if (n_rays == 0) return IDN_OK;
     if (!raw || !z || !rays || !bc_rgb || !out) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_composite(raw, z, rays, bc_rgb, n_rays, n_samples, sigma_noise, white_bkgd, *out, (hipStream_t)stream);
+    return launch_composite(CompositeIn{raw, z, rays, bc_rgb, sigma_noise, white_bkgd, n_rays, n_samples}, *out, (hipStream_t)stream);
 }
 
 int idealnerf_sample_pdf_fwd(const float* z, const float* weights, const float* u, int u_per_ray, int64_t n_rays,
@@ -295,8 +312,9 @@ int idealnerf_sample_pdf_fwd(const float* z, const float* weights, const float* 
     if (n_rays == 0) return IDN_OK;
     if (!z || !weights || !u) return fail(IDN_EINVAL, "NULL pointer");
     if (n_samples < 3) return fail(IDN_EUNSUPPORTED, "sample_pdf needs n_samples >= 3");
-    return launch_sample_pdf(z, weights, nullptr, nullptr, u, u_per_ray, n_rays, n_samples, n_importance, z_samples,
-                             inds, cdf, z_fine, z_std, (hipStream_t)stream);
+    SampleArgs s = sample_depths(z, weights, u, u_per_ray, n_rays, n_samples, n_importance);
+    s.z_samples = z_samples; s.inds = inds; s.cdf_out = cdf; s.z_fine = z_fine; s.z_std = z_std;
+    return launch_sample_pdf(s, (hipStream_t)stream);
 }
 
 int idealnerf_march_fwd(const float* raw, const float* z, const float* rays, const float* bc_rgb, const float* sigma_noise,
@@ -306,8 +324,10 @@ int idealnerf_march_fwd(const float* raw, const float* z, const float* rays, con
     if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
     if (n_rays == 0) return IDN_OK;
     if (!raw || !z || !rays || !bc_rgb || !u || !out) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_march(raw, z, rays, bc_rgb, sigma_noise, white_bkgd, *out, u, u_per_ray, n_rays, n_samples, n_importance,
-                        z_samples, inds, cdf, z_fine, z_std, (hipStream_t)stream);
+    const CompositeIn in = {raw, z, rays, bc_rgb, sigma_noise, white_bkgd, n_rays, n_samples};
+    SampleArgs s = sample_march(in, u, u_per_ray, n_importance, Draws{});
+    s.z_samples = z_samples; s.inds = inds; s.cdf_out = cdf; s.z_fine = z_fine; s.z_std = z_std;
+    return launch_march(in, *out, s, (hipStream_t)stream);
 }
 
 int idealnerf_sample_pdf_bins_fwd(const float* bins, const float* weights, const float* u, int u_per_ray,
@@ -316,8 +336,9 @@ int idealnerf_sample_pdf_bins_fwd(const float* bins, const float* weights, const
     if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
     if (n_rays == 0) return IDN_OK;
     if (!bins || !weights || !u) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_sample_pdf(nullptr, weights, nullptr, bins, u, u_per_ray, n_rays, n_bins + 1, n_importance, z_samples,
-                             inds, cdf, nullptr, nullptr, (hipStream_t)stream);
+    SampleArgs s = sample_bins(bins, weights, u, u_per_ray, n_rays, n_bins, n_importance);
+    s.z_samples = z_samples; s.inds = inds; s.cdf_out = cdf;
+    return launch_sample_pdf(s, (hipStream_t)stream);
 }
 
 int idealnerf_invert_cdf(const float* cdf, const float* bins, const float* u, int u_per_ray, int64_t n_rays,
@@ -325,8 +346,9 @@ int idealnerf_invert_cdf(const float* cdf, const float* bins, const float* u, in
     if (n_rays < 0) return fail(IDN_EINVAL, "n_rays < 0");
     if (n_rays == 0) return IDN_OK;
     if (!cdf || !bins || !u) return fail(IDN_EINVAL, "NULL pointer");
-    return launch_sample_pdf(nullptr, nullptr, cdf, bins, u, u_per_ray, n_rays, n_bins + 1, n_importance, z_samples,
-                             inds, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    SampleArgs s = sample_cdf(cdf, bins, u, u_per_ray, n_rays, n_bins, n_importance);
+    s.z_samples = z_samples; s.inds = inds;
+    return launch_sample_pdf(s, (hipStream_t)stream);
 }
 
 size_t idealnerf_train_acts_floats(int64_t n_points) {
@@ -661,7 +683,6 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, const i
     hipStream_t st = (hipStream_t)stream_;
     const RenderWs w = carve(reinterpret_cast<char*>(a->workspace), n, S, Ni);
 
-    auto off = [](auto* p, int64_t elems) { return p ? p + elems : p; };
     auto tap = [&](void* dst, const void* src, size_t bytes) -> int {
         if (!dst) return IDN_OK;
         IDN_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
@@ -681,66 +702,53 @@ static int render_impl(const idn_render_args* a, const idn_frame* frame, const i
         }
         const float* bc = a->bc_rgb + r0 * 3;
         const Draws draws{(unsigned long long)a->rng_seed, (long)(a->rng_ray0 + r0), a->rng_mode};   // this pass's rows of the draw table
-        if (int e = launch_coarse_depths(rays, a->t_vals, off(a->t_rand, r0 * S), c, S, a->lindisp, w.z_c, st, draws)) return e;
+        // this pass's rows of u and of every tap
+        const float* const u = a->u_per_ray ? off(a->u, r0 * Ni) : a->u;
+        float* const tap_z_c = off(a->tap_z_coarse, r0 * S);
+        float* const tap_raw_c = off(a->tap_raw_coarse, r0 * S * 4);
+        float* const tap_z_samples = off(a->tap_z_samples, r0 * Ni);
+        int64_t* const tap_inds = off(a->tap_inds, r0 * Ni);
+        float* const tap_cdf = off(a->tap_cdf, r0 * (S - 1));
+        float* const z_std = off(a->z_std, r0);
+        float* const tap_z_f = off(a->tap_z_fine, r0 * Sf);
+        float* const tap_raw_f = off(a->tap_raw_fine, r0 * Sf * 4);
+        if (int e = launch_coarse_depths(rays, a->t_vals, off(a->t_rand, r0 * S), c, S, a->lindisp, w.z_c, draws, st)) return e;
         if (!a->fused_march)
             if (int e = launch_mlp(a->precision, mlp_rays(a->packed_coarse, a->folded_coarse, rays, w.z_c, c, S, w.raw_c), st, MlpGate{gate_c, gate_counters}))
                 return e;
-        idn_composite_out co = {};
         const bool fine = Ni > 0;
-        co.rgb_map = off(fine ? a->rgb0 : a->rgb_map, r0 * 3);
-        co.disp_map = off(fine ? a->disp0 : a->disp_map, r0);
-        co.acc_map = off(fine ? a->acc0 : a->acc_map, r0);
-        co.depth_map = fine ? nullptr : off(a->depth_map, r0);
-        co.weights = off(a->tap_weights_coarse, r0 * S);
-        co.rgb_fg = off(fine ? a->rgb_fg0 : a->rgb_fg, r0 * 3);
-        co.last_weight = off(fine ? a->last_weight0 : a->last_weight, r0);
-        if (int e = tap(off(a->tap_z_coarse, r0 * S), w.z_c, (size_t)c * S * 4)) return e;
+        const idn_composite_out co = pass_out(a, r0, fine ? kCoarse : kCoarseFinal);
+        if (int e = tap(tap_z_c, w.z_c, (size_t)c * S * 4)) return e;
         if (a->fused_march) {   // one kernel from the coarse depths to the pixels; raw, weights, cdf and the fine depths stay in LDS
-            idn_composite_out fo = {};
-            fo.rgb_map = off(a->rgb_map, r0 * 3);
-            fo.disp_map = off(a->disp_map, r0);
-            fo.acc_map = off(a->acc_map, r0);
-            fo.depth_map = off(a->depth_map, r0);
-            fo.weights = off(a->tap_weights_fine, r0 * Sf);
-            fo.rgb_fg = off(a->rgb_fg, r0 * 3);
-            fo.last_weight = off(a->last_weight, r0);
-            const float* u = a->u_per_ray ? off(a->u, r0 * Ni) : a->u;
             const bool split = a->fused_march == 2;   // two launches: the fine depths cross HBM (w.z_f), everything else stays on chip
-            if (int e = launch_render_fused(a->fused_march, a->packed_coarse, a->folded_coarse, a->packed_fine, a->folded_fine, rays, bc, w.z_c,
-                                            split ? w.z_f : nullptr, u, a->u_per_ray, c, a->white_bkgd, co, fo, off(a->z_std, r0),
-                                            off(a->tap_raw_coarse, r0 * S * 4), off(a->tap_raw_fine, r0 * Sf * 4),
-                                            split ? nullptr : off(a->tap_z_fine, r0 * Sf), off(a->tap_inds, r0 * Ni), off(a->tap_z_samples, r0 * Ni),
-                                            off(a->tap_cdf, r0 * (S - 1)), st, draws))
-                return e;
+            FusedArgs f = {};
+            f.wstream_c = a->packed_coarse; f.bias_c = a->folded_coarse; f.wstream_f = a->packed_fine; f.bias_f = a->folded_fine;
+            f.rays = rays; f.bc = bc; f.z_c = w.z_c; f.u = u; f.u_per_ray = a->u_per_ray; f.n_rays = (long)c; f.white_bkgd = a->white_bkgd;
+            f.co = co; f.fo = pass_out(a, r0, kFine); f.z_std = z_std; f.draws = draws;
+            f.tap_raw_c = tap_raw_c; f.tap_raw_f = tap_raw_f; f.tap_inds = tap_inds; f.tap_z_samples = tap_z_samples; f.tap_cdf = tap_cdf;
+            if (split) f.z_f = w.z_f;
+            else f.tap_z_fine = tap_z_f;
+            if (int e = launch_render_fused(a->fused_march, f, st)) return e;
             if (split)
-                if (int e = tap(off(a->tap_z_fine, r0 * Sf), w.z_f, (size_t)c * Sf * 4)) return e;
+                if (int e = tap(tap_z_f, w.z_f, (size_t)c * Sf * 4)) return e;
             continue;
         }
-        if (int e = tap(off(a->tap_raw_coarse, r0 * S * 4), w.raw_c, (size_t)c * S * 16)) return e;
+        if (int e = tap(tap_raw_c, w.raw_c, (size_t)c * S * 16)) return e;
+        const CompositeIn in_c = {w.raw_c, w.z_c, rays, bc, off(a->noise_coarse, r0 * S), a->white_bkgd, c, S};
         if (!fine) {
-            if (int e = launch_composite(w.raw_c, w.z_c, rays, bc, c, S, off(a->noise_coarse, r0 * S), a->white_bkgd, co, st)) return e;
+            if (int e = launch_composite(in_c, co, st)) return e;
             continue;
         }
         // the march between the passes: coarse compositing, inverse-CDF sampling and the merge in one kernel
-        const float* u = a->u_per_ray ? off(a->u, r0 * Ni) : a->u;
-        if (int e = launch_march(w.raw_c, w.z_c, rays, bc, off(a->noise_coarse, r0 * S), a->white_bkgd, co, u, a->u_per_ray, c, S, Ni,
-                                 off(a->tap_z_samples, r0 * Ni), off(a->tap_inds, r0 * Ni), off(a->tap_cdf, r0 * (S - 1)),
-                                 w.z_f, off(a->z_std, r0), st, draws))
-            return e;
+        SampleArgs sm = sample_march(in_c, u, a->u_per_ray, Ni, draws);
+        sm.z_samples = tap_z_samples; sm.inds = tap_inds; sm.cdf_out = tap_cdf; sm.z_fine = w.z_f; sm.z_std = z_std;
+        if (int e = launch_march(in_c, co, sm, st)) return e;
         if (int e = launch_mlp(prec_fine, mlp_rays(a->packed_fine, a->folded_fine, rays, w.z_f, c, Sf, w.raw_f), st,
                                MlpGate{gate_f, gate_counters ? gate_counters + 2 : nullptr}))
             return e;
-        idn_composite_out fo = {};
-        fo.rgb_map = off(a->rgb_map, r0 * 3);
-        fo.disp_map = off(a->disp_map, r0);
-        fo.acc_map = off(a->acc_map, r0);
-        fo.depth_map = off(a->depth_map, r0);
-        fo.weights = off(a->tap_weights_fine, r0 * Sf);
-        fo.rgb_fg = off(a->rgb_fg, r0 * 3);
-        fo.last_weight = off(a->last_weight, r0);
-        if (int e = launch_composite(w.raw_f, w.z_f, rays, bc, c, Sf, off(a->noise_fine, r0 * Sf), a->white_bkgd, fo, st)) return e;
-        if (int e = tap(off(a->tap_z_fine, r0 * Sf), w.z_f, (size_t)c * Sf * 4)) return e;
-        if (int e = tap(off(a->tap_raw_fine, r0 * Sf * 4), w.raw_f, (size_t)c * Sf * 16)) return e;
+        if (int e = launch_composite(CompositeIn{w.raw_f, w.z_f, rays, bc, off(a->noise_fine, r0 * Sf), a->white_bkgd, c, Sf}, pass_out(a, r0, kFine), st)) return e;
+        if (int e = tap(tap_z_f, w.z_f, (size_t)c * Sf * 4)) return e;
+        if (int e = tap(tap_raw_f, w.raw_f, (size_t)c * Sf * 16)) return e;
     }
     return IDN_OK;
 }

@@ -19,19 +19,7 @@ __global__ void frame_rays_kernel(C2W c, int W, float focal, float cx, float cy,
     frame_ray_record(c, W, focal, cx, cy, near_, far_, pix0 + idx, out + (long)idx * IDN_RAY_FLOATS);
 }
 
-int launch_frame_rays(const float* c2w_host, int H, int W, float focal, float cx, float cy, float near_, float far_,
-                      int row0, int nrows, float* rays_out, hipStream_t s) {
-    C2W c;
-    for (int i = 0; i < 12; ++i) c.m[i] = c2w_host[i];
-    if (cx < 0) cx = W * 0.5f;
-    if (cy < 0) cy = H * 0.5f;
-    const int npix = nrows * W;
-    hipLaunchKernelGGL(frame_rays_kernel, dim3((npix + 255) / 256), dim3(256), 0, s, c, W, focal, cx, cy, near_, far_,
-                       (long)row0 * W, npix, rays_out);
-    IDN_HIP_CHECK(hipGetLastError());
-    return IDN_OK;
-}
-// the records of the pixels [pix0, pix0 + npix) of the frame (row-major), for the frame mode of the render call
+// the records of the pixels [pix0, pix0 + npix) of the frame (row-major): a band of whole rows, or one pass of a frame-mode render
 int launch_frame_rays_pixels(const float* c2w_host, int H, int W, float focal, float cx, float cy, float near_, float far_,
                              int64_t pix0, int npix, float* rays_out, hipStream_t s) {
     C2W c;
@@ -71,7 +59,7 @@ __global__ void coarse_depths_kernel(const float* rays, const float* t_vals, con
 }
 
 int launch_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays, int S,
-                         int lindisp, float* z, hipStream_t s, Draws draws) {
+                         int lindisp, float* z, Draws draws, hipStream_t s) {
     const long total = (long)n_rays * S;
     if (total <= 0) return IDN_OK;
     hipLaunchKernelGGL(coarse_depths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rays, t_vals,
@@ -242,23 +230,21 @@ __global__ __launch_bounds__(256) void composite_kernel(const float4* raw, const
     composite_ray<SPL>(raw + ray * S, z + ray * S, rays, bc, ray, lane, S, noise, white_bkgd, out, w);
 }
 
-int launch_composite(const float* raw, const float* z, const float* rays, const float* bc, int64_t n_rays, int S,
-                     const float* noise, int white_bkgd, const idn_composite_out& out, hipStream_t s) {
-    if (n_rays <= 0) return IDN_OK;
-    if (S < 2 || S > 64 * kMaxSpl) return fail(IDN_EUNSUPPORTED, "composite: n_samples %d outside [2, %d]", S, 64 * kMaxSpl);
-    const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-    const float4* r4 = reinterpret_cast<const float4*>(raw);
-    const int spl = (S + 63) / 64;
-    switch (spl) {
-        case 1: hipLaunchKernelGGL(composite_kernel<1>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        case 2: hipLaunchKernelGGL(composite_kernel<2>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        case 3: hipLaunchKernelGGL(composite_kernel<3>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        case 4: hipLaunchKernelGGL(composite_kernel<4>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        case 5: hipLaunchKernelGGL(composite_kernel<5>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        case 6: hipLaunchKernelGGL(composite_kernel<6>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        case 7: hipLaunchKernelGGL(composite_kernel<7>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-        default: hipLaunchKernelGGL(composite_kernel<8>, grid, block, 0, s, r4, z, rays, bc, (long)n_rays, S, noise, white_bkgd, out); break;
-    }
+// f(std::integral_constant<int, SPL>{}), SPL = min(spl, MAX) samples per lane (counting down emits the kernels in the order 1..MAX)
+template <int MAX, class F>
+static void dispatch_spl(int spl, F&& f) {
+    if constexpr (MAX > 1)
+        if (spl < MAX) return dispatch_spl<MAX - 1>(spl, f);
+    f(std::integral_constant<int, MAX>{});
+}
+
+int launch_composite(const CompositeIn& in, const idn_composite_out& out, hipStream_t s) {
+    if (in.n_rays <= 0) return IDN_OK;
+    if (in.S < 2 || in.S > 64 * kMaxSpl) return fail(IDN_EUNSUPPORTED, "composite: n_samples %d outside [2, %d]", in.S, 64 * kMaxSpl);
+    dispatch_spl<kMaxSpl>((in.S + 63) / 64, [&](auto spl) {
+        hipLaunchKernelGGL(composite_kernel<decltype(spl)::value>, dim3((unsigned)((in.n_rays + 3) / 4)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(in.raw), in.z, in.rays, in.bc, (long)in.n_rays, in.S, in.noise, in.white_bkgd, out);
+    });
     IDN_HIP_CHECK(hipGetLastError());
     return IDN_OK;
 }
@@ -299,38 +285,27 @@ __global__ __launch_bounds__(256) void march_kernel(const float4* raw, const flo
     sample_pdf_ray(a, ray, lane, s_cdf[wv], s_bins[wv], s_val[wv], s_w[wv]);
 }
 
-int launch_march(const float* raw, const float* z, const float* rays, const float* bc, const float* noise, int white_bkgd,
-                 const idn_composite_out& out, const float* u, int u_per_ray, int64_t n_rays, int S, int Ni,
-                 float* z_samples, int64_t* inds, float* cdf_out, float* z_fine, float* z_std, hipStream_t s, Draws draws) {
-    if (n_rays <= 0) return IDN_OK;
-    const int nb = S - 1;
-    if (S < 3 || S > 64 * kMaxSpl || nb > kMaxBins - 1) return fail(IDN_EUNSUPPORTED, "march: n_samples %d outside [3, %d]", S, kMaxBins);
+int launch_march(const CompositeIn& in, const idn_composite_out& out, const SampleArgs& a, hipStream_t s) {
+    if (a.n_rays <= 0) return IDN_OK;
+    const int S = a.S, Ni = a.Ni;
+    if (S < 3 || S > 64 * kMaxSpl || a.nb > kMaxBins - 1) return fail(IDN_EUNSUPPORTED, "march: n_samples %d outside [3, %d]", S, kMaxBins);
     if (Ni < 1 || Ni > kMaxNi) return fail(IDN_EUNSUPPORTED, "march: n_importance %d outside [1, %d]", Ni, kMaxNi);
     if (S + Ni > kMaxFine) return fail(IDN_EUNSUPPORTED, "march: n_samples + n_importance > %d", kMaxFine);
-    SampleArgs a{z, nullptr, nullptr, nullptr, u, u_per_ray, (long)n_rays, S, Ni, nb, z_samples, inds, cdf_out, z_fine, z_std, draws};
-    const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-    const float4* r4 = reinterpret_cast<const float4*>(raw);
-    switch ((S + 63) / 64) {
-        case 1: hipLaunchKernelGGL(march_kernel<1>, grid, block, 0, s, r4, rays, bc, noise, white_bkgd, out, a); break;
-        case 2: hipLaunchKernelGGL(march_kernel<2>, grid, block, 0, s, r4, rays, bc, noise, white_bkgd, out, a); break;
-        case 3: hipLaunchKernelGGL(march_kernel<3>, grid, block, 0, s, r4, rays, bc, noise, white_bkgd, out, a); break;
-        default: hipLaunchKernelGGL(march_kernel<4>, grid, block, 0, s, r4, rays, bc, noise, white_bkgd, out, a); break;
-    }
+    dispatch_spl<4>((S + 63) / 64, [&](auto spl) {
+        hipLaunchKernelGGL(march_kernel<decltype(spl)::value>, dim3((unsigned)((a.n_rays + 3) / 4)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(in.raw), in.rays, in.bc, in.noise, in.white_bkgd, out, a);
+    });
     IDN_HIP_CHECK(hipGetLastError());
     return IDN_OK;
 }
 
-int launch_sample_pdf(const float* z, const float* weights, const float* cdf_in, const float* bins_in,
-                      const float* u, int u_per_ray, int64_t n_rays, int S, int Ni, float* z_samples,
-                      int64_t* inds, float* cdf_out, float* z_fine, float* z_std, hipStream_t s) {
-    if (n_rays <= 0) return IDN_OK;
-    const int nb = S - 1;
-    if (nb < 2 || nb > kMaxBins - 1) return fail(IDN_EUNSUPPORTED, "sample_pdf: %d bins outside [2, %d]", nb, kMaxBins - 1);
-    if (Ni < 1 || Ni > kMaxNi) return fail(IDN_EUNSUPPORTED, "sample_pdf: n_importance %d outside [1, %d]", Ni, kMaxNi);
-    if (S + Ni > kMaxFine) return fail(IDN_EUNSUPPORTED, "sample_pdf: n_samples + n_importance > %d", kMaxFine);
-    if (z_fine && !z) return fail(IDN_EINVAL, "sample_pdf: the merged depths need the coarse depths z");
-    SampleArgs a{z, weights, cdf_in, bins_in, u, u_per_ray, (long)n_rays, S, Ni, nb, z_samples, inds, cdf_out, z_fine, z_std, Draws{0, 0, 0}};
-    hipLaunchKernelGGL(sample_pdf_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, s, a);
+int launch_sample_pdf(const SampleArgs& a, hipStream_t s) {
+    if (a.n_rays <= 0) return IDN_OK;
+    if (a.nb < 2 || a.nb > kMaxBins - 1) return fail(IDN_EUNSUPPORTED, "sample_pdf: %d bins outside [2, %d]", a.nb, kMaxBins - 1);
+    if (a.Ni < 1 || a.Ni > kMaxNi) return fail(IDN_EUNSUPPORTED, "sample_pdf: n_importance %d outside [1, %d]", a.Ni, kMaxNi);
+    if (a.S + a.Ni > kMaxFine) return fail(IDN_EUNSUPPORTED, "sample_pdf: n_samples + n_importance > %d", kMaxFine);
+    if (a.z_fine && !a.z) return fail(IDN_EINVAL, "sample_pdf: the merged depths need the coarse depths z");
+    hipLaunchKernelGGL(sample_pdf_kernel, dim3((unsigned)((a.n_rays + 3) / 4)), dim3(256), 0, s, a);
     IDN_HIP_CHECK(hipGetLastError());
     return IDN_OK;
 }

@@ -283,8 +283,6 @@ int launch_mlp_bf16(const MlpArgs& a, hipStream_t s);
 int launch_mlp_bf16x6(const MlpArgs& a, hipStream_t s);
 int launch_mlp(int precision, const MlpArgs& a, hipStream_t s, MlpGate gate);
 
-int launch_frame_rays(const float* c2w, int H, int W, float focal, float cx, float cy, float near_, float far_,
-                      int row0, int nrows, float* rays_out, hipStream_t s);
 int launch_frame_rays_pixels(const float* c2w_host, int H, int W, float focal, float cx, float cy, float near_, float far_,
                              int64_t pix0, int npix, float* rays_out, hipStream_t s);
 size_t audio_net_saved_floats(int n);
@@ -301,6 +299,92 @@ struct Draws {
     int on;
 };
 int launch_philox_uniform(unsigned long long seed, int which, int64_t row0, int64_t n_rows, int n_cols, float* out, hipStream_t s);
+
+// Render forward (composite.hip, render_fused.hip): as for the network, the kernels' argument records ARE the launchers'
+// parameters, filled by name (SampleArgs and FusedArgs are copied into the kernarg segment as they are); the four input modes
+// of the importance sampling have a builder each.
+struct SampleArgs {
+    const float* z;        // [n,S] coarse depths (null when bins_in is given)
+    const float* weights;  // [n,S] (the kernel uses [:,1:-1]) or, with bins_in, [n,nb-1] as helper.sample_pdf takes them
+    const float* cdf_in;   // [n,nb] optional: skip the pdf/cdf stage (bit-exact boundary)
+    const float* bins_in;  // [n,nb]
+    const float* u;
+    int u_per_ray;
+    long n_rays;
+    int S, Ni, nb;
+    float* z_samples;      // the outputs: a call site sets the ones it has, any may stay null
+    int64_t* inds;
+    float* cdf_out;
+    float* z_fine;
+    float* z_std;
+    Draws draws;           // on: u is drawn here, row draws.ray0 + ray of the table (a.u is not read)
+};
+// what a compositing kernel reads; its outputs are the public idn_composite_out
+struct CompositeIn {
+    const float *raw, *z, *rays, *bc, *noise;   // noise [n,S]: added to sigma, or null
+    int white_bkgd;
+    int64_t n_rays;
+    int S;
+};
+// the fused ray kernel (fp32, S = 64, Ni = 128)
+struct FusedArgs {
+    const float *wstream_c, *bias_c, *wstream_f, *bias_f;   // the packed weights and folded biases of the two networks
+    const float *rays, *bc, *z_c, *u;   // [n, 11], [n, 3], [n, 64] coarse depths (coarse_depths_kernel), the importance draws
+    int u_per_ray;
+    long n_rays;
+    int white_bkgd;
+    idn_composite_out co, fo;   // outputs of the coarse / fine compositing, indexed by ray
+    float* z_std;
+    float *tap_raw_c, *tap_raw_f, *tap_z_fine;   // debug taps (any may be null)
+    int64_t* tap_inds;
+    float *tap_z_samples, *tap_cdf;
+    float* z_f;          // [n, 192] fine depths in HBM: written by the coarse half, read by the fine half (split arrangement only)
+    Draws draws;         // on: the importance draws come from the Philox table instead of `u`
+};
+static_assert(sizeof(SampleArgs) == 136 && std::is_trivially_copyable<SampleArgs>::value, "kernel argument layout");
+static_assert(sizeof(FusedArgs) == 288 && std::is_trivially_copyable<FusedArgs>::value, "kernel argument layout");
+
+// what every sampling mode sets: S - 1 bins, the inputs of the modes null, no in-kernel draws
+inline SampleArgs sample_no_input(const float* u, int u_per_ray, int64_t n_rays, int S, int Ni) {
+    SampleArgs a = {};
+    a.u = u; a.u_per_ray = u_per_ray; a.n_rays = (long)n_rays; a.S = S; a.Ni = Ni; a.nb = S - 1;
+    return a;
+}
+// bins = the midpoints of the coarse depths, weights[:, 1:-1] (idealnerf_sample_pdf_fwd)
+inline SampleArgs sample_depths(const float* z, const float* weights, const float* u, int u_per_ray, int64_t n_rays, int S, int Ni) {
+    SampleArgs a = sample_no_input(u, u_per_ray, n_rays, S, Ni);
+    a.z = z; a.weights = weights;
+    return a;
+}
+// the caller's own bins [n, n_bins] and interior weights [n, n_bins - 1] (idealnerf_sample_pdf_bins_fwd)
+inline SampleArgs sample_bins(const float* bins, const float* weights, const float* u, int u_per_ray, int64_t n_rays, int n_bins, int Ni) {
+    SampleArgs a = sample_no_input(u, u_per_ray, n_rays, n_bins + 1, Ni);
+    a.bins_in = bins; a.weights = weights;
+    return a;
+}
+// a given cdf [n, n_bins] over the bins: the inversion alone (idealnerf_invert_cdf)
+inline SampleArgs sample_cdf(const float* cdf, const float* bins, const float* u, int u_per_ray, int64_t n_rays, int n_bins, int Ni) {
+    SampleArgs a = sample_no_input(u, u_per_ray, n_rays, n_bins + 1, Ni);
+    a.cdf_in = cdf; a.bins_in = bins;
+    return a;
+}
+// the march: the rays and depths of `in`, whose compositing weights reach the sampling through LDS (weights stays null)
+inline SampleArgs sample_march(const CompositeIn& in, const float* u, int u_per_ray, int Ni, Draws draws) {
+    SampleArgs a = sample_no_input(u, u_per_ray, in.n_rays, in.S, Ni);
+    a.z = in.z; a.draws = draws;
+    return a;
+}
+int launch_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays, int S,
+                         int lindisp, float* z, Draws draws, hipStream_t s);
+int launch_composite(const CompositeIn& in, const idn_composite_out& out, hipStream_t s);
+// coarse raw2outputs + sample_pdf + merge in one kernel (the weights stay on chip); sample = sample_march(in, ...), which carries
+// the depths, the ray count and S of `in`
+int launch_march(const CompositeIn& in, const idn_composite_out& out, const SampleArgs& sample, hipStream_t s);
+int launch_sample_pdf(const SampleArgs& sample, hipStream_t s);
+// arrangement 1: coarse network -> march -> fine network -> compositing in ONE kernel;
+// 2: coarse network + march | fine network + compositing (two launches, the fine depths a.z_f[n, 192] cross HBM between them)
+int launch_render_fused(int arrangement, const FusedArgs& a, hipStream_t s);
+
 // sampler.hip: the training loader's region-weighted pixel draw and the gather of the drawn pixels' rays / colours
 int launch_sample_pixels(const unsigned char* map, int H, int W, const int counts[4], unsigned long long seed, unsigned long long draw,
                          int* population, long long* sel, hipStream_t s);
@@ -323,25 +407,6 @@ int launch_cull_scatter(const long long* sel, int64_t n_live, int64_t npix, cons
 size_t frame_scores_workspace_bytes(int H, int W);
 int launch_frame_scores(const float* pred, const unsigned char* truth, const unsigned char* regions, int H, int W, double* out,
                         double* partial, hipStream_t s);
-int launch_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays, int S,
-                         int lindisp, float* z, hipStream_t s, Draws draws = Draws{0, 0, 0});
-int launch_composite(const float* raw, const float* z, const float* rays, const float* bc, int64_t n_rays, int S,
-                     const float* noise, int white_bkgd, const idn_composite_out& out, hipStream_t s);
-// coarse raw2outputs + sample_pdf + merge in one kernel (the weights stay on chip)
-int launch_march(const float* raw, const float* z, const float* rays, const float* bc, const float* noise, int white_bkgd,
-                 const idn_composite_out& out, const float* u, int u_per_ray, int64_t n_rays, int S, int Ni,
-                 float* z_samples, int64_t* inds, float* cdf_out, float* z_fine, float* z_std, hipStream_t s,
-                 Draws draws = Draws{0, 0, 0});
-// render_fused.hip (fp32, S = 64, Ni = 128).  arrangement 1: coarse network -> march -> fine network -> compositing in ONE kernel;
-// 2: coarse network + march | fine network + compositing (two launches, the fine depths z_f[n, 192] cross HBM between them)
-int launch_render_fused(int arrangement, const float* packed_c, const float* folded_c, const float* packed_f, const float* folded_f,
-                        const float* rays, const float* bc, const float* z_c, float* z_f, const float* u, int u_per_ray, int64_t n_rays,
-                        int white_bkgd, const idn_composite_out& co, const idn_composite_out& fo, float* z_std, float* tap_raw_c,
-                        float* tap_raw_f, float* tap_z_fine, int64_t* tap_inds, float* tap_z_samples, float* tap_cdf, hipStream_t s,
-                        Draws draws = Draws{0, 0, 0});
-int launch_sample_pdf(const float* z, const float* weights, const float* cdf_in, const float* bins_in,
-                      const float* u, int u_per_ray, int64_t n_rays, int S, int Ni, float* z_samples,
-                      int64_t* inds, float* cdf_out, float* z_fine, float* z_std, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Backward delta chain (mlp_f32_bwd.hip): the transposed weights as a second fragment stream.

@@ -217,23 +217,6 @@ constexpr int kMaxBins = 256;   // S - 1 <= 255
 constexpr int kMaxNi = 256;
 constexpr int kMaxFine = 512;
 
-struct SampleArgs {
-    const float* z;        // [n,S] coarse depths (null when bins_in is given)
-    const float* weights;  // [n,S] (the kernel uses [:,1:-1]) or, with bins_in, [n,nb-1] as helper.sample_pdf takes them
-    const float* cdf_in;   // [n,nb] optional: skip the pdf/cdf stage (bit-exact boundary)
-    const float* bins_in;  // [n,nb]
-    const float* u;
-    int u_per_ray;
-    long n_rays;
-    int S, Ni, nb;
-    float* z_samples;
-    int64_t* inds;
-    float* cdf_out;
-    float* z_fine;
-    float* z_std;
-    Draws draws;           // on: u is drawn here, row draws.ray0 + ray of the table (a.u is not read)
-};
-
 // torch.sum(x, -1) of a contiguous fp32 row as PyTorch's CPU kernel evaluates it (ATen
 // native/cpu/SumKernel.cpp: vectorized_inner_sum -> row_sum -> multi_row_sum, the AVX2 build that
 // is dispatched on AVX2 and AVX512 hosts alike): 8-lane vectors; vector i goes to accumulator i&3

@@ -40,30 +40,6 @@ constexpr int kFBiasPadFloats = kFBiasPerThread * 256;
 constexpr int kFusedLds = kRingFrags * kFragBytes + kFBiasPadFloats * 4 + kFG * kFSf * 4 + kFUnionBytes;
 static_assert(kFusedLds <= 160 * 1024, "LDS per CU");
 
-struct FusedArgs {
-    const float* wstream_c;
-    const float* bias_c;
-    const float* wstream_f;
-    const float* bias_f;
-    const float* rays;   // [n, 11]
-    const float* bc;     // [n, 3]
-    const float* z_c;    // [n, 64] coarse depths (coarse_depths_kernel)
-    const float* u;
-    int u_per_ray;
-    long n_rays;
-    int white_bkgd;
-    idn_composite_out co, fo;   // outputs of the coarse / fine compositing, indexed by ray
-    float* z_std;
-    float* tap_raw_c;    // debug taps (any may be null)
-    float* tap_raw_f;
-    float* tap_z_fine;
-    int64_t* tap_inds;
-    float* tap_z_samples;
-    float* tap_cdf;
-    float* z_f;          // [n, 192] fine depths in HBM: written by the coarse half, read by the fine half (split arrangement only)
-    Draws draws;         // on: the importance draws come from the Philox table instead of `u`
-};
-
 using WStreamDual = WStreamT<4, kSliceFrags, kRingSlots, true>;
 
 // PHASE: kFusedWhole = the whole ray in one launch; kFusedCoarse = coarse network + march (fine depths -> a.z_f);
@@ -245,14 +221,11 @@ __global__ __launch_bounds__(256, 1) void render_fused_kernel(FusedArgs a) {
     __syncthreads();
 }
 
-int launch_render_fused(int arrangement, const float* packed_c, const float* folded_c, const float* packed_f, const float* folded_f,
-                        const float* rays, const float* bc, const float* z_c, float* z_f, const float* u, int u_per_ray, int64_t n_rays,
-                        int white_bkgd, const idn_composite_out& co, const idn_composite_out& fo, float* z_std, float* tap_raw_c,
-                        float* tap_raw_f, float* tap_z_fine, int64_t* tap_inds, float* tap_z_samples, float* tap_cdf, hipStream_t s,
-                        Draws draws) {
+int launch_render_fused(int arrangement, const FusedArgs& a, hipStream_t s) {
+    const int64_t n_rays = a.n_rays;
     if (n_rays <= 0) return IDN_OK;
     if (arrangement != 1 && arrangement != 2) return fail(IDN_EINVAL, "fused march: arrangement %d (1 = one kernel, 2 = coarse + march | fine + compositing)", arrangement);
-    if (arrangement == 2 && !z_f) return fail(IDN_EINVAL, "fused march: the two-launch arrangement needs the fine-depth buffer z_f[n, 192]");
+    if (arrangement == 2 && !a.z_f) return fail(IDN_EINVAL, "fused march: the two-launch arrangement needs the fine-depth buffer z_f[n, 192]");
     static LaunchSetup setup;
     int num_cu = 0;
     if (int e = setup.get([]() -> int {
@@ -264,8 +237,6 @@ int launch_render_fused(int arrangement, const float* packed_c, const float* fol
         return e;
     const int64_t ngroups = (n_rays + kFG - 1) / kFG;
     const int grid = (int)(ngroups < num_cu ? ngroups : num_cu);
-    FusedArgs a{packed_c, folded_c, packed_f, folded_f, rays, bc, z_c, u, u_per_ray, (long)n_rays, white_bkgd, co, fo, z_std,
-                tap_raw_c, tap_raw_f, tap_z_fine, tap_inds, tap_z_samples, tap_cdf, z_f, draws};
     if (arrangement == 1) {
         ProfScope prof(s, n_rays * (kFS + kFSf), IDN_PROF_MLP_FWD);
         hipLaunchKernelGGL(render_fused_kernel<kFusedWhole>, dim3(grid), dim3(256), fused_lds<kFusedWhole>(), s, a);

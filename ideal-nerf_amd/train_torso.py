@@ -98,23 +98,8 @@ class Network(HeadNetwork):
                     rays=None, bc_rgb=None, aud_para=None, network_nerf=None, rows=None):
         """train_torso.py::render_dynamic_face (:381-426): [rgb_map, disp_map, acc_map, last_weight,
         rgb_map_fg, {rest}] for one coarse/fine pair."""
-        from . import ops
-        dev = self.face_nerf_coarse.alpha_linear.weight.device
         coarse, fine = network_nerf['coarse'], network_nerf['fine']
-        frame = None
-        if render_poses is not None:   # full frame: the rays are derived on the device inside the render call
-            row0, nrows = (0, H) if rows is None else (rows[0], rows[1] - rows[0])
-            frame, rec = ops.make_frame(render_poses.detach().cpu(), H, W, focal, near, far, row0, nrows), None
-            bc = bc_rgb[row0:row0 + nrows].reshape(-1, 3)
-            sh = (nrows, W, 3)
-        else:
-            rays_o, rays_d = rays
-            sh = rays_d.shape
-            rays_o, rays_d = rays_o.reshape(-1, 3).float(), rays_d.reshape(-1, 3).float()
-            viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
-            rec = torch.cat([rays_o, rays_d, near * torch.ones_like(rays_d[..., :1]),
-                             far * torch.ones_like(rays_d[..., :1]), viewdirs], -1)
-            bc = bc_rgb
+        rec, frame, bc, sh = self._ray_inputs(H, W, focal, near, far, render_poses, rays, bc_rgb, rows)
         all_ret = self._batchify(rec, bc, aud_para, latent_code, expr, coarse, fine, True, chunk, frame=frame)
         for k in all_ret:
             all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))

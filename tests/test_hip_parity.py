@@ -1635,6 +1635,49 @@ def test_fused_ray_kernel_equals_the_unfused_path(idn, dev, n_rays, jitter, with
         idn.ops.render_rays_fwd(r, bc, pk_c, fold_c(*cond), pk_f, fold_f(*cond), torch.linspace(0.0, 1.0, 32).to(dev), u, 128, fused=True)
 
 
+def test_render_across_the_internal_pass_boundary_equals_two_calls(idn, dev):
+    """The render call walks its rays in internal passes of 32 768 (csrc/capi.hip: kRenderChunk); everything a later pass reads
+    or writes is offset by its first ray r0.  One call on 32 768 + 37 rays -- a second pass, ragged against the fused kernel's
+    groups of four rays -- against the same rays as two calls, [:32768] and [32768:], whose passes both start at r0 = 0: every
+    output and every tap BIT FOR BIT, with per-ray u and t_rand and the torso variant's outputs, in the three kernel
+    arrangements, with per-ray density noise on both passes, and with the colour gate on (no taps), whose tile counters of
+    the one call are the sums of the two calls'."""
+    n, cut = 32768 + 37, 32768
+    dims, pc, pf, (pk_c, fold_c), (pk_f, fold_f) = _nets(idn, dev)
+    syn = oracle.synthetic_frame(48, 48, seed=7, dims=dims)
+    rays = idn.ops.frame_rays(syn["c2w"], 48, 48, syn["focal"], NEAR, FAR, device=dev)
+    sel = torch.from_numpy(np.random.RandomState(n).choice(48 * 48, n, replace=True))
+    r = rays[sel.to(dev)].contiguous()
+    bc = syn["bc"].reshape(-1, 3)[sel].contiguous().to(dev)
+    cond = (syn["aud"], syn["expr"], syn["latent"])
+    nets = (pk_c, fold_c(*cond), pk_f, fold_f(*cond), torch.linspace(0.0, 1.0, 64).to(dev))
+    g = torch.Generator().manual_seed(n)
+    u, t_rand = torch.rand((n, 128), generator=g).to(dev), torch.rand((n, 64), generator=g).to(dev)
+    noise = dict(noise_coarse=torch.randn((n, 64), generator=g).to(dev), noise_fine=torch.randn((n, 192), generator=g).to(dev))
+
+    def render(rows, per_ray, **kw):
+        return idn.ops.render_rays_fwd(r[rows], bc[rows], *nets, u[rows], 128, t_rand=t_rand[rows], with_fg=True,
+                                       **{k: v[rows] for k, v in per_ray.items()}, **kw)
+
+    def check(per_ray, gate=None, **kw):   # gate: int64 [3, 2, 2], the colour gate's counters of the one call and of the two
+        whole, head, tail = (render(rows, per_ray, **kw, **({} if gate is None else dict(colour_gate=True, gate_counters=gate[i])))
+                             for i, rows in enumerate((slice(0, n), slice(0, cut), slice(cut, n))))
+        assert list(whole) == list(head) == list(tail)
+        for k in whole:
+            two = torch.cat([head[k], tail[k]])
+            if not torch.equal(whole[k], two):
+                row = int((whole[k] != two).reshape(n, -1).any(1).nonzero()[0])
+                raise AssertionError(f"{k} ({kw}, {sorted(per_ray)}): one call != two calls, first at ray {row}")
+
+    for how in (False, True, "split"):
+        check({}, fused=how, taps=True)
+    check(noise, fused=False, taps=True)
+    counters = torch.zeros((3, 2, 2), dtype=torch.int64, device=dev)
+    check({}, gate=counters, fused=False, taps=False)
+    assert (counters[0, :, 0] > 0).all(), "the gated kernels did not run"
+    assert torch.equal(counters[0], counters[1] + counters[2]), counters.tolist()
+
+
 def test_philox_table_matches_the_cpu_restatement(idn, dev):
     """The table the in-kernel draws come from (idealnerf_philox_uniform) against oracle/philox.py -- itself pinned by
     Philox4x32-10's published known-answer vectors -- bit for bit: both tables, ragged widths, a row offset beyond 32 bits."""
