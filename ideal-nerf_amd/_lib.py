@@ -174,6 +174,11 @@ PROTOTYPES = {
     "idealnerf_delta_chain": (C.c_int, [C.POINTER(FaceNerfParams), C.c_int, fp, C.c_int64, fp, fp, fp, fp, C.c_int,
                                         C.POINTER(C.c_int), fp, C.c_size_t, fp]),
     "idealnerf_composite_bwd": (C.c_int, [fp, fp, fp, fp, C.c_int64, C.c_int, fp, fp, fp, fp, fp, C.c_int, fp, C.c_int, fp, C.c_int, fp]),
+    "idealnerf_input_grad": (C.c_int, [C.POINTER(FaceNerfParams), fp, fp, fp, C.c_int64, C.c_int64, fp, C.c_int, C.POINTER(C.c_int), fp]),
+    "idealnerf_ray_grad": (C.c_int, [fp, C.c_int, C.c_int, fp, fp, C.c_int64, C.c_int, fp, fp]),
+    "idealnerf_fold_bwd": (C.c_int, [C.POINTER(FaceNerfParams), fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp]),
+    "idealnerf_cond_colsums_workspace_bytes": (C.c_size_t, []),
+    "idealnerf_cond_colsums": (C.c_int, [fp, fp, fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_cull_mark": (C.c_int, [fp, C.c_int64, C.c_float, fp, fp]),
     "idealnerf_cull_cells": (C.c_int, [fp, C.c_int, C.c_int, fp, fp]),
     "idealnerf_cull_classify_workspace_bytes": (C.c_size_t, [C.c_int64]),

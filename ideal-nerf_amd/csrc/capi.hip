@@ -555,6 +555,61 @@ int idealnerf_composite_bwd(const float* raw, const float* z, const float* rays,
     return launch_composite_bwd(a, (hipStream_t)stream);
 }
 
+int idealnerf_input_grad(const idn_facenerf_params* p, const float* dA0, const float* dA5, const float* dV0, int64_t n,
+                         int64_t p_pad, float* d_x, int max_blocks, int* blocks_out, void* stream) {
+    if (int e = check_params(p)) return e;
+    if (!dA0 || !dA5 || !dV0 || !d_x) return fail(IDN_EINVAL, "input_grad: NULL pointer");
+    if (p_pad <= 0 || p_pad % 128) return fail(IDN_EINVAL, "input_grad: p_pad %lld is not a positive multiple of 128", (long long)p_pad);
+    if (p_pad > (1LL << 24)) return fail(IDN_EUNSUPPORTED, "input_grad: p_pad %lld exceeds 2^24", (long long)p_pad);
+    if (n < 1 || n > p_pad) return fail(IDN_EINVAL, "input_grad: n %lld outside [1, p_pad = %lld]", (long long)n, (long long)p_pad);
+    if (max_blocks < 0) return fail(IDN_EINVAL, "input_grad: max_blocks %d < 0", max_blocks);
+    if (((uintptr_t)dA0 | (uintptr_t)dA5 | (uintptr_t)dV0) & 15) return fail(IDN_EINVAL, "input_grad: the delta matrices are not 16-byte aligned");
+    return launch_dx(*p, dA0, dA5, dV0, n, p_pad, d_x, max_blocks, blocks_out, (hipStream_t)stream);
+}
+
+int idealnerf_ray_grad(const float* d_x, int pts_ch, int views_ch, const float* rays, const float* z, int64_t n_rays, int n_samples,
+                       float* d_rays, void* stream) {
+    if (n_rays < 0) return fail(IDN_EINVAL, "ray_grad: n_rays < 0");
+    if (n_rays == 0) return IDN_OK;
+    if (!d_x || !rays || !z || !d_rays) return fail(IDN_EINVAL, "ray_grad: NULL pointer");
+    if (!widths_ok(pts_ch, views_ch)) return fail(IDN_EINVAL, "ray_grad: row widths %d / %d", pts_ch, views_ch);
+    if (n_samples < 2 || n_samples > 512) return fail(IDN_EUNSUPPORTED, "ray_grad: n_samples %d outside [2, 512]", n_samples);
+    return launch_ray_grad(d_x, pts_ch, views_ch, rays, z, n_rays, n_samples, d_rays, (hipStream_t)stream);
+}
+
+int idealnerf_fold_bwd(const idn_facenerf_params* p, const float* aud, const float* expr, const float* latent, const float* db0,
+                       const float* db5, const float* dbv, float* gW0, float* gW5, float* gWv0, float* d_aud, float* d_expr,
+                       float* d_latent, void* stream) {
+    if (int e = check_params(p)) return e;
+    if ((p->dim_aud > 0) != (aud != nullptr) || (p->dim_expr > 0) != (expr != nullptr) || (p->dim_latent > 0) != (latent != nullptr))
+        return fail(IDN_EINVAL, "fold_bwd: conditioning pointers do not match the widths");
+    const int given = (gW0 != nullptr) + (gW5 != nullptr) + (gWv0 != nullptr);
+    if (given != 0 && given != 3) return fail(IDN_EINVAL, "fold_bwd: %d of the three gradient tensors (all three, or none for the d cond range alone)", given);
+    if ((d_aud && !p->dim_aud) || (d_expr && !p->dim_expr) || (d_latent && !p->dim_latent))
+        return fail(IDN_EINVAL, "fold_bwd: a gradient for a conditioning vector the network does not have");
+    if (p->dim_aud + p->dim_expr + p->dim_latent == 0) return IDN_OK;   // nothing to fold
+    if (!db0 || !db5) return fail(IDN_EINVAL, "fold_bwd: NULL bias gradient");
+    if (!dbv && p->dim_expr > 0 && (given || d_expr)) return fail(IDN_EINVAL, "fold_bwd: NULL bias gradient of views_linears.0");
+    const FoldBwdArgs f{*p, aud, expr, latent, db0, db5, dbv, gW0, gW5, gWv0, d_aud, d_latent, d_expr};
+    return launch_fold_bwd(f, given == 0, (hipStream_t)stream);
+}
+
+size_t idealnerf_cond_colsums_workspace_bytes(void) { return cond_colsums_workspace_bytes(); }
+
+int idealnerf_cond_colsums(const float* dA0, const float* dA5, const float* dV0, int64_t P, int64_t p_pad, float* db, float* dbv,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    const int pts = (dA0 != nullptr) + (dA5 != nullptr) + (db != nullptr), views = (dV0 != nullptr) + (dbv != nullptr);
+    if ((pts != 0 && pts != 3) || (views != 0 && views != 2))
+        return fail(IDN_EINVAL, "cond_colsums: NULL pointer inside a pair (dA0, dA5, db come together, and dV0 with dbv)");
+    if (p_pad <= 0 || p_pad % 128) return fail(IDN_EINVAL, "cond_colsums: p_pad %lld is not a positive multiple of 128", (long long)p_pad);
+    if (p_pad > (1LL << 24)) return fail(IDN_EUNSUPPORTED, "cond_colsums: p_pad %lld exceeds 2^24", (long long)p_pad);
+    if (P < 1 || P > p_pad) return fail(IDN_EINVAL, "cond_colsums: P %lld outside [1, p_pad = %lld]", (long long)P, (long long)p_pad);
+    if (!pts && !views) return IDN_OK;
+    if (!workspace || workspace_bytes < cond_colsums_workspace_bytes() || ((uintptr_t)workspace & 7))
+        return fail(IDN_EWORKSPACE, "cond_colsums: workspace %zu < %zu (or not 8-byte aligned)", workspace_bytes, cond_colsums_workspace_bytes());
+    return launch_cond_colsums(dA0, dA5, dV0, P, p_pad, db, dbv, reinterpret_cast<double*>(workspace), (hipStream_t)stream);
+}
+
 void idealnerf_profile_begin(void) {
     g_prof_n = 0;
     g_prof_on = true;

@@ -500,6 +500,27 @@ int launch_composite_bwd(const CompBwdArgs& a, hipStream_t s);
 // column 6 of d_rays holds dL / d |rays_d| on entry
 int launch_ray_grad(const float* d_x, int pts_ch, int views_ch, const float* rays, const float* z, int64_t n_rays, int S,
                     float* d_rays, hipStream_t s);
+// train.hip: the stages of a backward that follow the delta chain, each as the pass launches it and as its test aid does
+// (idealnerf_input_grad, idealnerf_fold_bwd, idealnerf_cond_colsums).
+// d_x [n, pts_ch + views_ch] from the three [Pp, 256] delta matrices dA[0], dA[5], dV0.  max_blocks 0: the grid of a pass;
+// k > 0 caps it at k workgroups; blocks_out (may be null): the grid that ran
+int launch_dx(const idn_facenerf_params& p, const float* dA0, const float* dA5, const float* dV0, int64_t n, int64_t Pp, float* d_x,
+              int max_blocks, int* blocks_out, hipStream_t s);
+struct FoldBwdArgs {
+    idn_facenerf_params p;
+    const float* aud; const float* expr; const float* latent;
+    const float* db0; const float* db5; const float* dbv;  // [256], [256], [128]
+    float* gW0; float* gW5; float* gWv0;                    // gradient tensors (full nn.Linear layout)
+    float* d_aud; float* d_latent;                          // accumulated (+=), may be null
+    float* d_expr;                                          // accumulated (+=), may be null (the expression takes no gradient)
+};
+// cond_only: the d cond range alone, gW0 / gW5 / gWv0 are not touched (a frozen network)
+int launch_fold_bwd(const FoldBwdArgs& f, bool cond_only, hipStream_t s);
+// db [2][256] = column sums of dA0 | dA5 over Pp rows (dA0 null: left out), dbv [128] = those of dV0[:, 0:128] over the first
+// P rows (dV0 null: left out); part: cond_colsums_workspace_bytes() bytes
+size_t cond_colsums_workspace_bytes();
+int launch_cond_colsums(const float* dA0, const float* dA5, const float* dV0, int64_t P, int64_t Pp, float* db, float* dbv,
+                        double* part, hipStream_t s);
 // FaceNeRF.forward's backward on pre-embedded rows: head deltas from g_out [n, 4], the same tail as launch_pass_bwd, d expr
 // from the fold and (d_x != null) the input-row gradient d_x [n, pts_ch + views_ch]
 int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& gr, const BwdCond& cond, const float* acts,

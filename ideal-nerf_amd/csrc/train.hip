@@ -171,14 +171,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompBwdArgs a) {
 //   d expr[e] = (d cond[dim_aud+e] + sum_n Wv0[n][283+e] dbv'[n]) / 3   (expr * 1 / 3 enters all three layers, face_nerf.py:49)
 // (63 and 283 at the default widths: the network's pts_ch and 256 + views_ch, idn_internal.h)
 // ---------------------------------------------------------------------------
-struct FoldBwdArgs {
-    idn_facenerf_params p;
-    const float* aud; const float* expr; const float* latent;
-    const float* db0; const float* db5; const float* dbv;  // [256], [256], [128]
-    float* gW0; float* gW5; float* gWv0;                    // gradient tensors (full nn.Linear layout)
-    float* d_aud; float* d_latent;                          // accumulated (+=), may be null
-    float* d_expr;                                          // accumulated (+=), may be null (the expression takes no gradient)
-};
+// (FoldBwdArgs: idn_internal.h)
 __device__ __forceinline__ float cond_val(const FoldBwdArgs& d, int c) {
     if (c < d.p.dim_aud) return d.aud[c];
     c -= d.p.dim_aud;
@@ -267,6 +260,50 @@ __global__ __launch_bounds__(256) void colsum_finish_kernel(const double* part, 
 }
 constexpr int kCondColsumBlocks = 512;   // row blocks at the most: their fp64 partial sums and the 512 results fit the cpart pool
 static_assert(512 + (size_t)kCondColsumBlocks * 512 * 2 <= kCpartPoolFloats, "the conditioning-only column sums fit the cpart pool");
+size_t cond_colsums_workspace_bytes() { return (size_t)kCondColsumBlocks * 512 * sizeof(double); }
+
+// The two column-sum steps of a frozen pass (bwd_tail without gradient tensors), and all of idealnerf_cond_colsums:
+//   db [2][256] = the column sums of dA0 | dA5 over all Pp rows (dA0 null: the step is left out);
+//   dbv [128]   = the column sums of dV0[:, 0:128] over the first P rows (dV0 null: left out).
+// part: kCondColsumBlocks x 512 doubles, free again between the two steps (the stream orders them).
+int launch_cond_colsums(const float* dA0, const float* dA5, const float* dV0, int64_t P, int64_t Pp, float* db, float* dbv,
+                        double* part, hipStream_t s) {
+    const int64_t chunks = Pp / 128;
+    const int64_t rows_per_block = (chunks + kCondColsumBlocks - 1) / kCondColsumBlocks * 128;
+    if (dA0) {
+        const int blocks = (int)((Pp + rows_per_block - 1) / rows_per_block);
+        hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 2), dim3(256), 0, s, dA0, dA5, (long)Pp, (long)rows_per_block, part);
+        IDN_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3(2), dim3(256), 0, s, (const double*)part, blocks, db);
+        IDN_HIP_CHECK(hipGetLastError());
+    }
+    // dbv' [128]: the same two kernels, 128 threads wide, on dV0's delta columns and the real rows alone
+    if (dV0) {
+        const int blocks = (int)((P + rows_per_block - 1) / rows_per_block);
+        hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 1), dim3(128), 0, s, dV0, dV0, (long)P, (long)rows_per_block, part);
+        IDN_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(128), 0, s, (const double*)part, blocks, dbv);
+        IDN_HIP_CHECK(hipGetLastError());
+    }
+    return IDN_OK;
+}
+
+// The conditioning fold's backward, both launches of bwd_tail and all of idealnerf_fold_bwd.  cond_only: the d cond range
+// alone (fold_bwd_kernel<true>: a wavefront per conditioning column); else the whole index range, the outer products into
+// the gradient tensors first.  A network without conditioning launches nothing.
+int launch_fold_bwd(const FoldBwdArgs& f, bool cond_only, hipStream_t s) {
+    const int C = f.p.dim_aud + f.p.dim_expr + f.p.dim_latent;
+    if (cond_only) {
+        if (C == 0) return IDN_OK;
+        hipLaunchKernelGGL(fold_bwd_kernel<true>, dim3((C * 64 + 255) / 256), dim3(256), 0, s, f);
+    } else {
+        const int total = IDN_W * C + (IDN_W / 2) * f.p.dim_expr + C * 64;   // one wavefront per conditioning column at the end
+        if (total == 0) return IDN_OK;
+        hipLaunchKernelGGL(fold_bwd_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, s, f);
+    }
+    IDN_HIP_CHECK(hipGetLastError());
+    return IDN_OK;
+}
 
 // ---------------------------------------------------------------------------
 // host orchestration
@@ -345,33 +382,12 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
         if (C == 0 && !want_dbv) return IDN_OK;
         float* db = w.cpart;                                        // [2][256]: db0', db5'
         double* part = reinterpret_cast<double*>(w.cpart + 512);    // [blocks][2][256] (the pool is 256-byte aligned)
-        const int64_t chunks = Pp / 128;
-        const int64_t rows_per_block = (chunks + kCondColsumBlocks - 1) / kCondColsumBlocks * 128;
-        if (C > 0) {
-            const int blocks = (int)((Pp + rows_per_block - 1) / rows_per_block);
-            hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 2), dim3(256), 0, s, (const float*)w.dA[0], (const float*)w.dA[5], (long)Pp,
-                               (long)rows_per_block, part);
-            IDN_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(colsum_finish_kernel, dim3(2), dim3(256), 0, s, (const double*)part, blocks, db);
-            IDN_HIP_CHECK(hipGetLastError());
-        }
-        // dbv' [128]: the same two kernels, 128 threads wide, on dV0's delta columns and the real rows alone; `part` is free
-        // again (the stream orders it behind the finish above), the result goes to the caller's buffer or, with none, to the
-        // partial-product pool this plan never uses
+        // dbv' [128] over the real rows alone; the result goes to the caller's buffer or, with none, to the partial-product
+        // pool this plan never uses
         float* dbv = cond.d_vb ? cond.d_vb : w.part;
-        if (want_dbv) {
-            const int blocks = (int)((P + rows_per_block - 1) / rows_per_block);
-            hipLaunchKernelGGL(colsum_rows_kernel, dim3(blocks, 1), dim3(128), 0, s, (const float*)w.dV0, (const float*)w.dV0, (long)P,
-                               (long)rows_per_block, part);
-            IDN_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(128), 0, s, (const double*)part, blocks, dbv);
-            IDN_HIP_CHECK(hipGetLastError());
-        }
-        if (C == 0) return IDN_OK;
-        FoldBwdArgs f{p, cond.aud, cond.expr, cond.latent, db, db + 256, dbv, nullptr, nullptr, nullptr, cond.d_aud, cond.d_latent, cond.d_expr};
-        hipLaunchKernelGGL(fold_bwd_kernel<true>, dim3((C * 64 + 255) / 256), dim3(256), 0, s, f);
-        IDN_HIP_CHECK(hipGetLastError());
-        return IDN_OK;
+        TRY(launch_cond_colsums(C > 0 ? w.dA[0] : nullptr, w.dA[5], want_dbv ? w.dV0 : nullptr, P, Pp, db, dbv, part, s));
+        const FoldBwdArgs f{p, cond.aud, cond.expr, cond.latent, db, db + 256, dbv, nullptr, nullptr, nullptr, cond.d_aud, cond.d_latent, cond.d_expr};
+        return launch_fold_bwd(f, true, s);
     }
     const idn_facenerf_grads& gr = *grads;
     // weight and bias gradients: dW_l = delta_l^T a_{l-1} (contraction over the points), db_l = column sums.  The products in
@@ -422,22 +438,15 @@ static int bwd_tail(const idn_facenerf_params& p, const idn_facenerf_grads* grad
     TRY(q.take_colsum(h, 0, 256, gr.pts_b[0]));
     TRY(q.take(h, 0, 0, 256, PC, gr.pts_w[0], ld0));
     TRY(q.finish());
+    const FoldBwdArgs f{p, cond.aud, cond.expr, cond.latent, gr.pts_b[0], gr.pts_b[5], gr.views_b[0], gr.pts_w[0], gr.pts_w[5],
+                        gr.views_w[0], cond.d_aud, cond.d_latent, cond.d_expr};
+    TRY(launch_fold_bwd(f, false, s));
 #undef TRY
-    {
-        FoldBwdArgs f{p, cond.aud, cond.expr, cond.latent, gr.pts_b[0], gr.pts_b[5], gr.views_b[0], gr.pts_w[0], gr.pts_w[5],
-                      gr.views_w[0], cond.d_aud, cond.d_latent, cond.d_expr};
-        const int total = IDN_W * C + (IDN_W / 2) * p.dim_expr + C * 64;   // one wavefront per conditioning column at the end
-        if (total > 0) {
-            hipLaunchKernelGGL(fold_bwd_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, s, f);
-            IDN_HIP_CHECK(hipGetLastError());
-        }
-    }
     return IDN_OK;
 }
 
 // d_x [n, pts_ch + views_ch] = dL / d (input rows) from the deltas of pts_linears.0 / .5 and views_linears.0 a backward has left in `w`
-// (dx_kernel, below)
-static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, int64_t Pp, float* d_x, hipStream_t s);
+// (dx_kernel, below; launch_dx: idn_internal.h)
 
 template <bool kNorm>
 static void launch_composite_bwd_spl(const CompBwdArgs& a, hipStream_t s) {
@@ -495,7 +504,7 @@ int launch_pass_bwd(const PassBwd& b, hipStream_t s) {
     if (d_rays) {
         float* d_x = w.dA[1];
         static_assert(IDN_PTS_CH + IDN_VIEWS_CH <= 256, "the input-row gradient fits a delta matrix");
-        if (int e = launch_dx(p, w, P, Pp, d_x, s)) return e;
+        if (int e = launch_dx(p, w.dA[0], w.dA[5], w.dV0, P, Pp, d_x, 0, nullptr, s)) return e;
         return launch_ray_grad(d_x, pts_ch_of(p), views_ch_of(p), b.rays, b.z, n_rays, S, d_rays, s);
     }
     return IDN_OK;
@@ -617,7 +626,9 @@ __global__ __launch_bounds__(64 * kDxWaves, 1) void dx_kernel(DxArgs a) {
     }
 }
 
-static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, int64_t Pp, float* d_x, hipStream_t s) {
+// max_blocks: 0 = the grid of a pass, min(ceil(Pp / 512), CUs); k > 0 caps it at k workgroups.  blocks_out (may be null): the grid that ran.
+int launch_dx(const idn_facenerf_params& p, const float* dA0, const float* dA5, const float* dV0, int64_t n, int64_t Pp, float* d_x,
+              int max_blocks, int* blocks_out, hipStream_t s) {
     static LaunchSetup setup;
     int num_cu = 0;
     if (int e = setup.get([]() -> int {
@@ -628,11 +639,13 @@ static int launch_dx(const idn_facenerf_params& p, const BwdWs& w, int64_t n, in
     const int C = p.dim_aud + p.dim_expr + p.dim_latent;
     const int PC = pts_ch_of(p), VC = views_ch_of(p);
     const DxArgs da{p.pts_w[0], PC + C, p.pts_w[5], PC + C + IDN_W, p.views_w[0], IDN_W + VC + p.dim_expr,
-                    w.dA[0], w.dA[5], w.dV0, (long)n, (long)Pp, d_x, PC, VC};
+                    dA0, dA5, dV0, (long)n, (long)Pp, d_x, PC, VC};
     const int64_t groups = (Pp / 32 + kDxWaves - 1) / kDxWaves;
-    const int grid = (int)(groups < num_cu ? groups : num_cu);
+    int grid = (int)(groups < num_cu ? groups : num_cu);
+    if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
     hipLaunchKernelGGL(dx_kernel, dim3(grid), dim3(64 * kDxWaves), kDxLds, s, da);
     IDN_HIP_CHECK(hipGetLastError());
+    if (blocks_out) *blocks_out = grid;
     return IDN_OK;
 }
 
@@ -648,7 +661,7 @@ int launch_facenerf_bwd(const idn_facenerf_params& p, const idn_facenerf_grads& 
         IDN_HIP_CHECK(hipGetLastError());
     }
     if (int e = bwd_tail(p, &gr, cond, acts, n, Pp, w, s)) return e;
-    if (d_x) return launch_dx(p, w, n, Pp, d_x, s);
+    if (d_x) return launch_dx(p, w.dA[0], w.dA[5], w.dV0, n, Pp, d_x, 0, nullptr, s);
     return IDN_OK;
 }
 

@@ -750,6 +750,153 @@ def composite_bwd(raw, z, rays, bc, g_rgb=None, g_fg=None, g_lw=None, g_acc=None
     return d_rgb, d_sig, d_norm
 
 
+def _all_f32(*named):
+    for t, name in named:
+        if t is not None and t.dtype != torch.float32:
+            raise IdealNerfError(f"{name} must be {torch.float32} (got {t.dtype})")
+
+
+def input_grad(p, dA0, dA5, dV0, n, d_x=None, max_blocks=0):
+    """Test aid: the input-row gradient of a backward alone (idealnerf_input_grad: dx_kernel through the launch of a pass).
+        p: params_struct of the network -- only pts_linears.0 / .5's encoding columns and views_linears.0's direction columns are read
+        dA0, dA5, dV0 [p_pad, 256]: the deltas of pts_linears.0, pts_linears.5 and views_linears.0 (dV0: columns 0..127 are read)
+        n: the rows that get a gradient, 1 <= n <= p_pad;  d_x [n, pts_ch + views_ch]: optional output to write into
+        max_blocks: 0 = the grid of a pass (min(ceil(p_pad / 512), CUs)); k > 0: at most k workgroups
+    p_pad = dA0.shape[0], a positive multiple of 128.  Returns (d_x, blocks): the gradient and the grid that ran."""
+    lib = _lib.load()
+    E = IdealNerfError
+    if not isinstance(p, _lib.FaceNerfParams):
+        raise E("input_grad: p must be a params_struct")
+    if isinstance(max_blocks, bool) or not isinstance(max_blocks, int) or max_blocks < 0:
+        raise E(f"input_grad: max_blocks {max_blocks} < 0")
+    _shape(dA0, "dA0", None, 256)
+    p_pad = dA0.shape[0]
+    if p_pad <= 0 or p_pad % 128 or p_pad > 1 << 24:
+        raise E(f"input_grad: p_pad {p_pad} is not a positive multiple of 128 up to 2^24")
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= p_pad:
+        raise E(f"input_grad: n {n} outside [1, p_pad = {p_pad}]")
+    _shape(dA5, "dA5", p_pad, 256)
+    _shape(dV0, "dV0", p_pad, 256)
+    _shape(d_x, "d_x", n, sum(widths(p)))
+    _all_f32((dA0, "dA0"), (dA5, "dA5"), (dV0, "dV0"), (d_x, "d_x"))
+    with _Launch(dA0, dA5, dV0, d_x) as L:
+        ptrs = [_ptr(t, name) for t, name in ((dA0, "dA0"), (dA5, "dA5"), (dV0, "dV0"))]   # raises for CPU tensors
+        if any(q % 16 for q in ptrs):
+            raise E("input_grad: the delta matrices are not 16-byte aligned")
+        if d_x is None:
+            d_x = torch.empty((n, sum(widths(p))), dtype=torch.float32, device=L.device)
+        blocks = C.c_int(0)
+        check(lib.idealnerf_input_grad(C.byref(p), *ptrs, n, p_pad, _ptr(d_x, "d_x"), int(max_blocks), C.byref(blocks), L.stream))
+    return d_x, blocks.value
+
+
+def ray_grad(d_x, pts_ch, views_ch, rays, z, d_rays):
+    """Test aid: the encoding backward and the per-ray reduction of a pass alone (idealnerf_ray_grad).
+        d_x [n * S, pts_ch + views_ch]: the input-row gradient of the pass's points;  rays [n, 11], z [n, S]
+        d_rays [n, 11]: column 6 holds dL / d |rays_d| on entry; columns 0:3 d rays_o, 3:6 d rays_d, 8:11 d viewdirs are WRITTEN,
+        6:8 with zeros
+    S in [2, 512].  Returns d_rays."""
+    lib = _lib.load()
+    E = IdealNerfError
+    for ch, name, limit in ((pts_ch, "pts_ch", PTS_CH), (views_ch, "views_ch", VIEWS_CH)):
+        if isinstance(ch, bool) or not isinstance(ch, int) or ch < 3 or ch > limit or ch % 6 != 3:
+            raise E(f"ray_grad: {name} {ch} is not 3 + 6 L up to {limit}")
+    if z is None or d_rays is None:
+        raise E("ray_grad: z / d_rays is None")
+    _shape(z, "z", None, None)
+    n, S = z.shape
+    if not 2 <= S <= 512:
+        raise E(f"ray_grad: n_samples {S} outside [2, 512]")
+    for t, name, shape in ((d_x, "d_x", (n * S, pts_ch + views_ch)), (rays, "rays", (n, RAY_FLOATS)), (d_rays, "d_rays", (n, RAY_FLOATS))):
+        if t is None:
+            raise E(f"ray_grad: {name} is None")
+        _shape(t, name, *shape)
+    _all_f32((d_x, "d_x"), (rays, "rays"), (z, "z"), (d_rays, "d_rays"))
+    with _Launch(d_x, rays, z, d_rays) as L:
+        ptrs = [_ptr(t, name) for t, name in ((d_x, "d_x"), (rays, "rays"), (z, "z"), (d_rays, "d_rays"))]
+        check(lib.idealnerf_ray_grad(ptrs[0], pts_ch, views_ch, ptrs[1], ptrs[2], n, S, ptrs[3], L.stream))
+    return d_rays
+
+
+def fold_bwd(p, aud, expr, latent, db0, db5, dbv, gW0=None, gW5=None, gWv0=None, d_aud=None, d_expr=None, d_latent=None):
+    """Test aid: the conditioning fold's backward alone (idealnerf_fold_bwd).
+        p: params_struct of the network -- only the conditioning columns of pts_linears.0 / .5 and the expression columns of
+        views_linears.0 are read;  aud / expr / latent: the vectors the forward was folded with (None where the width is 0)
+        db0, db5 [256], dbv [128]: the bias gradients of pts_linears.0 / .5 and views_linears.0
+        gW0 [256, pts_ch + C], gW5 [256, pts_ch + C + 256], gWv0 [128, 256 + views_ch + dim_expr]: the three layers' gradient
+        tensors, whose conditioning columns are WRITTEN.  All three None: the launch of a frozen network (d cond alone);
+        dbv is then read only with d_expr
+        d_aud / d_expr / d_latent: ACCUMULATED, each may be None."""
+    lib = _lib.load()
+    E = IdealNerfError
+    if not isinstance(p, _lib.FaceNerfParams):
+        raise E("fold_bwd: p must be a params_struct")
+    given = sum(t is not None for t in (gW0, gW5, gWv0))
+    if given not in (0, 3):
+        raise E(f"fold_bwd: {given} of the three gradient tensors (all three, or none)")
+    pc, vc = widths(p)
+    Cc = p.dim_aud + p.dim_expr + p.dim_latent
+    for t, name, dim in ((aud, "aud", p.dim_aud), (expr, "expr", p.dim_expr), (latent, "latent", p.dim_latent)):
+        if (t is None) != (dim == 0):
+            raise E(f"fold_bwd: {name} is {'None' if t is None else 'given'} but the network's width is {dim}")
+        _shape(t, name, dim)
+    for t, name, dim in ((d_aud, "d_aud", p.dim_aud), (d_expr, "d_expr", p.dim_expr), (d_latent, "d_latent", p.dim_latent)):
+        if t is not None and dim == 0:
+            raise E(f"fold_bwd: {name} for a width of 0")
+        _shape(t, name, dim)
+    if db0 is None or db5 is None or (dbv is None and p.dim_expr > 0 and (given or d_expr is not None)):
+        raise E("fold_bwd: db0 / db5 / dbv is None")
+    for t, name, shape in ((db0, "db0", (W_HID,)), (db5, "db5", (W_HID,)), (dbv, "dbv", (W_HID // 2,)), (gW0, "gW0", (W_HID, pc + Cc)),
+                           (gW5, "gW5", (W_HID, pc + Cc + W_HID)), (gWv0, "gWv0", (W_HID // 2, W_HID + vc + p.dim_expr))):
+        _shape(t, name, *shape)
+    named = ((aud, "aud"), (expr, "expr"), (latent, "latent"), (db0, "db0"), (db5, "db5"), (dbv, "dbv"), (gW0, "gW0"), (gW5, "gW5"),
+             (gWv0, "gWv0"), (d_aud, "d_aud"), (d_expr, "d_expr"), (d_latent, "d_latent"))
+    _all_f32(*named)
+    with _Launch(*(t for t, _ in named)) as L:
+        check(lib.idealnerf_fold_bwd(C.byref(p), *(_ptr(t, name) for t, name in named), L.stream))
+
+
+_cond_colsums_ws = {}
+
+
+def cond_colsums(dA0, dA5, dV0, P, db=None, dbv=None):
+    """Test aid: the column sums a frozen network's backward feeds the fold with (idealnerf_cond_colsums).
+        dA0, dA5 [p_pad, 256] -> db [2, 256]: their column sums over all p_pad rows (both None: left out)
+        dV0 [p_pad, 256] -> dbv [128]: the sums of its columns 0..127 over the first P rows (None: left out)
+    p_pad a positive multiple of 128, 1 <= P <= p_pad.  Returns (db, dbv); an output is None where its matrices are."""
+    lib = _lib.load()
+    E = IdealNerfError
+    if (dA0 is None) != (dA5 is None):
+        raise E("cond_colsums: dA0 and dA5 come together")
+    first = dA0 if dA0 is not None else dV0
+    if first is None:
+        raise E("cond_colsums: no matrix")
+    _shape(first, "dA0" if dA0 is not None else "dV0", None, 256)
+    p_pad = first.shape[0]
+    if p_pad <= 0 or p_pad % 128 or p_pad > 1 << 24:
+        raise E(f"cond_colsums: p_pad {p_pad} is not a positive multiple of 128 up to 2^24")
+    if isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= p_pad:
+        raise E(f"cond_colsums: P {P} outside [1, p_pad = {p_pad}]")
+    if (db is not None and dA0 is None) or (dbv is not None and dV0 is None):
+        raise E("cond_colsums: an output without its matrices")
+    for t, name, shape in ((dA5, "dA5", (p_pad, 256)), (dV0, "dV0", (p_pad, 256)), (db, "db", (2, 256)), (dbv, "dbv", (128,))):
+        _shape(t, name, *shape)
+    named = ((dA0, "dA0"), (dA5, "dA5"), (dV0, "dV0"), (db, "db"), (dbv, "dbv"))
+    _all_f32(*named)
+    with _Launch(*(t for t, _ in named)) as L:
+        ptrs = [_ptr(t, name) for t, name in named[:3]]   # raises for CPU tensors
+        if db is None and dA0 is not None:
+            db = torch.empty((2, 256), dtype=torch.float32, device=L.device)
+        if dbv is None and dV0 is not None:
+            dbv = torch.empty((128,), dtype=torch.float32, device=L.device)
+        key = (str(L.device), int(L.stream))
+        ws = _cond_colsums_ws.get(key)
+        if ws is None:
+            ws = _cond_colsums_ws[key] = torch.zeros(lib.idealnerf_cond_colsums_workspace_bytes(), dtype=torch.uint8, device=L.device)
+        check(lib.idealnerf_cond_colsums(*ptrs, P, p_pad, _ptr(db, "db"), _ptr(dbv, "dbv"), ws.data_ptr(), ws.numel(), L.stream))
+    return db, dbv
+
+
 AUDIO_NET_MAX_BWD_WINDOWS = 8
 
 

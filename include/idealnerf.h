@@ -695,6 +695,41 @@ int idealnerf_composite_bwd(const float* raw, const float* z, const float* rays,
                             void* stream);
 
 /*
+ * Test aids (no reference counterpart): what a training backward runs after the delta chain, stage by stage, on the caller's
+ * matrices -- the same kernels through the same launch functions as idealnerf_pass_bwd* / idealnerf_facenerf_bwd -- so that
+ * tests/ can hold every element to fp64.  Argument errors are found before any HIP call.  Additive entries: the ABI version
+ * is unchanged.
+ *
+ * idealnerf_input_grad: the input-row gradient alone.  dA0 / dA5 / dV0 [p_pad, 256] (16-byte aligned): the deltas of
+ *   pts_linears.0, pts_linears.5 and views_linears.0 (dV0: columns 0..127; columns 128..255 are not read).  d_x
+ *   [n, pts_ch + views_ch] of the network `p` describes is WRITTEN; nothing else is.  p_pad: a positive multiple of 128, at most
+ *   2^24; 1 <= n <= p_pad.  Of the weights only pts_linears.0 / .5's encoding columns and views_linears.0's direction columns
+ *   are read.  max_blocks: 0 = the grid of a pass, min(ceil(p_pad / 512), CUs); k > 0 caps it at k workgroups.  blocks_out
+ *   (may be NULL): the grid that ran.
+ * idealnerf_ray_grad: the encoding backward and the per-ray reduction alone.  d_x [n_rays * n_samples, pts_ch + views_ch],
+ *   rays [n_rays, 11], z [n_rays, n_samples]; d_rays [n_rays, 11]: column 6 is READ (dL / d |rays_d|), columns 0..10 are WRITTEN
+ *   (6 and 7 with zeros).  IDN_EINVAL for widths that are not 3 + 6 L, IDN_EUNSUPPORTED for n_samples outside [2, 512].
+ * idealnerf_fold_bwd: the conditioning fold's backward alone.  db0 / db5 [256], dbv [128]: the bias gradients of pts_linears.0 / .5
+ *   and views_linears.0.  With gW0, gW5, gWv0 (the three layers' gradient tensors in nn.Linear layout) their conditioning
+ *   columns are WRITTEN; with all three NULL the launch covers d cond alone, as the frozen plan of idealnerf_pass_bwd_ex
+ *   (one or two NULL: IDN_EINVAL).  d_aud / d_expr / d_latent: ACCUMULATED, each may be NULL; dbv is read only for the
+ *   expression columns of gWv0 and for d_expr.  A network without conditioning writes nothing.
+ * idealnerf_cond_colsums: the column sums the frozen plan feeds that fold with.  db [2][256] = the sums of dA0 | dA5 over all
+ *   p_pad rows; dbv [128] = the sums of dV0[:, 0:128] over the first P rows.  Either group (dA0, dA5, db) / (dV0, dbv) may be
+ *   NULL as a whole.  workspace: idealnerf_cond_colsums_workspace_bytes() bytes, 8-byte aligned (IDN_EWORKSPACE).
+ */
+int idealnerf_input_grad(const idn_facenerf_params* p, const float* dA0, const float* dA5, const float* dV0, int64_t n,
+                         int64_t p_pad, float* d_x, int max_blocks, int* blocks_out, void* stream);
+int idealnerf_ray_grad(const float* d_x, int pts_ch, int views_ch, const float* rays, const float* z, int64_t n_rays, int n_samples,
+                       float* d_rays, void* stream);
+int idealnerf_fold_bwd(const idn_facenerf_params* p, const float* aud, const float* expr, const float* latent, const float* db0,
+                       const float* db5, const float* dbv, float* gW0, float* gW5, float* gWv0, float* d_aud, float* d_expr,
+                       float* d_latent, void* stream);
+size_t idealnerf_cond_colsums_workspace_bytes(void);
+int idealnerf_cond_colsums(const float* dA0, const float* dA5, const float* dV0, int64_t P, int64_t p_pad, float* db, float* dbv,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * AudioNet.forward (models/audio_net.py:43-69: the per-frame audio latent of audio_exp_nerf.py:258-259, or of the eight windows
  * under the attention smoother, :235-257) as ONE kernel, and its backward as one: windows [n, 16, 29] (win_size 16) ->
  * out [n, dim_aud].  Parameters in nn.Conv1d / nn.Linear layout ([C_out, C_in, 3] / [out, in], fp32, contiguous):

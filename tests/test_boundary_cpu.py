@@ -289,6 +289,105 @@ def test_c_abi_argument_errors_without_gpu(idn):
         for kw in ({}, dict(d_norm=24576, ld_norm=11), dict(g=(4096, 4096, 4096, 4096), ld_rgb=64, ld_sig=256)):
             rc, msg = comp(S=S, **kw)
             assert rc == -2 and b"n_samples" in msg and b"[2, 512]" in msg, (S, kw)
+    # the backward's tail alone.  The input gradient: params, NULL, p_pad, n, max_blocks, alignment
+    def dx(p=fp_, dA0=4096, dA5=8192, dV0=12288, n=100, p_pad=256, d_x=16384, max_blocks=0):
+        blocks = C.c_int(-7)
+        rc = lib.idealnerf_input_grad(None if p is None else C.byref(p), dA0, dA5, dV0, n, p_pad, d_x, max_blocks, C.byref(blocks), None)
+        assert blocks.value == -7         # (nothing ran)
+        return rc, lib.idealnerf_last_error()
+
+    rc, msg = dx(p=None)
+    assert rc == -1 and b"params is NULL" in msg
+    for name in ("dA0", "dA5", "dV0", "d_x"):
+        rc, msg = dx(**{name: None})
+        assert rc == -1 and b"input_grad: NULL" in msg, name
+    for p_pad in (0, -128, 100, 192):
+        rc, msg = dx(p_pad=p_pad, n=1)
+        assert rc == -1 and b"multiple of 128" in msg, p_pad
+    rc, msg = dx(p_pad=(1 << 24) + 128)
+    assert rc == -2 and b"2^24" in msg
+    for n in (257, 0, -1):
+        rc, msg = dx(n=n)
+        assert rc == -1 and b"outside [1, p_pad = 256]" in msg, n
+    rc, msg = dx(max_blocks=-1)
+    assert rc == -1 and b"max_blocks" in msg
+    for name in ("dA0", "dA5", "dV0"):
+        rc, msg = dx(**{name: 4096 + 4})
+        assert rc == -1 and b"aligned" in msg, name
+    # the ray gradient: n_rays, NULL, widths, n_samples
+    def rgrad(d_x=4096, pts_ch=63, views_ch=27, rays=8192, z=12288, n=4, S=64, d_rays=16384):
+        rc = lib.idealnerf_ray_grad(d_x, pts_ch, views_ch, rays, z, n, S, d_rays, None)
+        return rc, lib.idealnerf_last_error()
+
+    rc, msg = rgrad(n=-1)
+    assert rc == -1 and b"n_rays < 0" in msg
+    assert rgrad(n=0)[0] == 0 and rgrad(n=0, d_x=None, S=0, pts_ch=4)[0] == 0
+    for name in ("d_x", "rays", "z", "d_rays"):
+        rc, msg = rgrad(**{name: None})
+        assert rc == -1 and b"ray_grad: NULL" in msg, name
+    for kw in (dict(pts_ch=4), dict(views_ch=4), dict(pts_ch=27, views_ch=4), dict(pts_ch=4, views_ch=27), dict(pts_ch=69), dict(views_ch=33),
+               dict(pts_ch=0), dict(views_ch=-3)):
+        rc, msg = rgrad(**kw)
+        assert rc == -1 and b"row widths" in msg, kw
+    for S in (-1, 0, 1, 513, 1024):
+        for kw in ({}, dict(pts_ch=27, views_ch=15), dict(pts_ch=3, views_ch=3)):
+            rc, msg = rgrad(S=S, **kw)
+            assert rc == -2 and b"n_samples" in msg and b"[2, 512]" in msg, (S, kw)
+    # the fold's backward: params, conditioning pointers against the widths, a partial set of gradient tensors, NULL bias gradients
+    def fold(p=fp_, dims=(64, 76, 32), cond=(4096, 8192, 12288), db=(16384, 20480, 24576), gw=(28672, 32768, 36864), d=(None, None, None)):
+        if p is not None:
+            p.dim_aud, p.dim_expr, p.dim_latent = dims
+        rc = lib.idealnerf_fold_bwd(None if p is None else C.byref(p), *cond, *db, *gw, *d, None)
+        return rc, lib.idealnerf_last_error()
+
+    rc, msg = fold(p=None)
+    assert rc == -1 and b"params is NULL" in msg
+    for cond in ((None, 8192, 12288), (4096, None, 12288), (4096, 8192, None)):
+        rc, msg = fold(cond=cond)
+        assert rc == -1 and b"conditioning pointers" in msg, cond
+    rc, msg = fold(dims=(106, 0, 0))
+    assert rc == -1 and b"conditioning pointers" in msg
+    for gw in ((None, 32768, 36864), (28672, None, 36864), (28672, 32768, None), (28672, None, None), (None, 32768, None), (None, None, 36864)):
+        rc, msg = fold(gw=gw)
+        assert rc == -1 and b"of the three gradient tensors" in msg, gw
+        rc, msg = fold(gw=gw, dims=(0, 0, 0), cond=(None, None, None))
+        assert rc == -1 and b"of the three gradient tensors" in msg, gw
+    rc, msg = fold(dims=(106, 0, 0), cond=(4096, None, None), d=(None, 4096, None))
+    assert rc == -1 and b"does not have" in msg
+    for db in ((None, 20480, 24576), (16384, None, 24576)):
+        for gw in ((28672, 32768, 36864), (None, None, None)):
+            rc, msg = fold(db=db, gw=gw)
+            assert rc == -1 and b"NULL bias gradient" in msg, (db, gw)
+    rc, msg = fold(db=(16384, 20480, None))
+    assert rc == -1 and b"views_linears.0" in msg
+    rc, msg = fold(db=(16384, 20480, None), gw=(None, None, None), d=(None, 4096, None))
+    assert rc == -1 and b"views_linears.0" in msg
+    assert fold(dims=(0, 0, 0), cond=(None, None, None), db=(None, None, None))[0] == 0     # nothing to fold: OK, nothing runs
+    fp_.dim_aud = fp_.dim_expr = fp_.dim_latent = 0
+    # the frozen plan's column sums: a NULL inside a group, p_pad, P, workspace
+    cs_bytes = lib.idealnerf_cond_colsums_workspace_bytes()
+    assert cs_bytes == 512 * 512 * 8      # 512 row blocks x [2][256] fp64 partial sums
+
+    def colsums(dA0=4096, dA5=8192, dV0=12288, P=100, p_pad=256, db=16384, dbv=20480, ws=24576, nbytes=cs_bytes):
+        rc = lib.idealnerf_cond_colsums(dA0, dA5, dV0, P, p_pad, db, dbv, ws, nbytes, None)
+        return rc, lib.idealnerf_last_error()
+
+    for kw in (dict(dA0=None), dict(dA5=None), dict(db=None), dict(dV0=None), dict(dbv=None), dict(dA0=None, dA5=None), dict(dA0=None, db=None)):
+        rc, msg = colsums(**kw)
+        assert rc == -1 and b"NULL pointer inside a pair" in msg, kw
+    for p_pad in (0, -128, 100, 192):
+        rc, msg = colsums(p_pad=p_pad, P=1)
+        assert rc == -1 and b"multiple of 128" in msg, p_pad
+    rc, msg = colsums(p_pad=(1 << 24) + 128)
+    assert rc == -2 and b"2^24" in msg
+    for P in (257, 0, -1):
+        rc, msg = colsums(P=P)
+        assert rc == -1 and b"outside [1, p_pad = 256]" in msg, P
+    assert colsums(dA0=None, dA5=None, db=None, dV0=None, dbv=None, ws=None)[0] == 0         # neither group: nothing runs
+    for kw in (dict(nbytes=cs_bytes - 1), dict(nbytes=0), dict(ws=None), dict(ws=24576 + 4)):
+        for groups in ({}, dict(dA0=None, dA5=None, db=None), dict(dV0=None, dbv=None)):
+            rc, msg = colsums(**kw, **groups)
+            assert rc == -4 and b"workspace" in msg, (kw, groups)
 
 
 def test_product_path_refuses_cpu_tensors(idn):
@@ -1054,3 +1153,86 @@ def test_ops_validate_shapes_before_the_c_call(idn):
             (dict(raw=torch.zeros(4, 64, 4, dtype=torch.float64)), "must live on the GPU")):
         with pytest.raises(E, match=match):
             comp(**kw)
+    # the backward's tail alone: every shape, dtype and device, on CPU tensors
+    def dx(p=pp, dA0=m256, dA5=m256, dV0=m256, n=100, **kw):
+        return ops.input_grad(p, dA0, dA5, dV0, n, **kw)
+
+    narrow = idn._lib.FaceNerfParams()
+    narrow.multires_plus1, narrow.multires_views_plus1 = 5, 3                        # 27 / 15 columns
+    for kw, match in (
+            (dict(p=None), "params_struct"), (dict(max_blocks=-1), "max_blocks"), (dict(max_blocks=True), "max_blocks"),
+            (dict(dA0=torch.zeros(256, 128)), r"dA0 must be \[\*, 256\]"), (dict(dA0=torch.zeros(192, 256)), "multiple of 128"),
+            (dict(dA0=torch.zeros(0, 256)), "multiple of 128"), (dict(dA5=torch.zeros(128, 256)), r"dA5 must be \[256, 256\]"),
+            (dict(dV0=torch.zeros(256, 129)), r"dV0 must be \[256, 256\]"), (dict(n=257), "n 257 outside"), (dict(n=0), "n 0 outside"),
+            (dict(n=2.0), "outside"), (dict(d_x=torch.zeros(100, 63)), r"d_x must be \[100, 90\]"), (dict(d_x=torch.zeros(99, 90)), r"d_x must be \[100, 90\]"),
+            (dict(p=narrow, d_x=torch.zeros(100, 90)), r"d_x must be \[100, 42\]"),
+            (dict(dA0=m256.double()), "dA0 must be torch.float32"), (dict(dV0=m256.half()), "dV0 must be torch.float32"),
+            (dict(d_x=torch.zeros(100, 90, dtype=torch.float64)), "d_x must be torch.float32"),
+            ({}, "must live on the GPU"), (dict(d_x=torch.zeros(100, 90)), "must live on the GPU")):
+        with pytest.raises(E, match=match):
+            dx(**kw)
+
+    def rgrad(n=4, S=64, pts_ch=63, views_ch=27, **kw):
+        args = dict(d_x=torch.zeros(n * S, pts_ch + views_ch), rays=torch.zeros(n, 11), z=torch.zeros(n, S), d_rays=torch.zeros(n, 11))
+        args.update(kw)
+        return ops.ray_grad(args["d_x"], pts_ch, views_ch, args["rays"], args["z"], args["d_rays"])
+
+    for kw, match in (
+            (dict(pts_ch=4), "pts_ch 4"), (dict(views_ch=4), "views_ch 4"), (dict(pts_ch=27, views_ch=4), "views_ch 4"),
+            (dict(pts_ch=4, views_ch=27), "pts_ch 4"), (dict(pts_ch=69), "pts_ch 69"), (dict(views_ch=33), "views_ch 33"),
+            (dict(S=1), "outside"), (dict(S=513), "outside"), (dict(z=None), "is None"), (dict(d_rays=None), "is None"),
+            (dict(d_x=None), "d_x is None"), (dict(rays=None), "rays is None"), (dict(z=torch.zeros(256)), r"z must be \[\*, \*\]"),
+            (dict(d_x=torch.zeros(256, 63)), r"d_x must be \[256, 90\]"), (dict(d_x=torch.zeros(255, 90)), r"d_x must be \[256, 90\]"),
+            (dict(pts_ch=27, views_ch=15, d_x=torch.zeros(256, 90)), r"d_x must be \[256, 42\]"),
+            (dict(rays=torch.zeros(4, 8)), r"rays must be \[4, 11\]"), (dict(d_rays=torch.zeros(4, 3)), r"d_rays must be \[4, 11\]"),
+            (dict(d_x=torch.zeros(256, 90, dtype=torch.float64)), "d_x must be torch.float32"), (dict(z=torch.zeros(4, 64).half()), "z must be torch.float32"),
+            ({}, "must live on the GPU"), (dict(pts_ch=3, views_ch=3, S=2), "must live on the GPU")):
+        with pytest.raises(E, match=match):
+            rgrad(**kw)
+
+    head = idn._lib.FaceNerfParams()
+    head.dim_aud, head.dim_expr, head.dim_latent = 64, 76, 32
+    torso = idn._lib.FaceNerfParams()
+    torso.dim_aud = 106
+    z = torch.zeros
+
+    def fold(p=head, **kw):
+        q = head if p is None else p
+        args = dict(aud=z(q.dim_aud) if q.dim_aud else None, expr=z(q.dim_expr) if q.dim_expr else None,
+                    latent=z(q.dim_latent) if q.dim_latent else None, db0=z(256), db5=z(256), dbv=z(128))
+        args.update(kw)
+        return ops.fold_bwd(p, **args)
+
+    g0, g5, gv = z(256, 235), z(256, 491), z(128, 359)
+    for kw, match in (
+            (dict(p=None), "params_struct"), (dict(gW0=g0), "1 of the three"), (dict(gW5=g5), "1 of the three"), (dict(gWv0=gv), "1 of the three"),
+            (dict(gW0=g0, gW5=g5), "2 of the three"), (dict(gW0=g0, gWv0=gv), "2 of the three"), (dict(gW5=g5, gWv0=gv), "2 of the three"),
+            (dict(aud=None), "aud is None"), (dict(expr=None), "expr is None"), (dict(latent=None), "latent is None"),
+            (dict(p=torso, expr=z(76)), "expr is given"), (dict(aud=z(63)), r"aud must be \[64\]"), (dict(expr=z(79)), r"expr must be \[76\]"),
+            (dict(p=torso, d_expr=z(76)), "d_expr for a width of 0"), (dict(p=torso, d_latent=z(32)), "d_latent for a width of 0"),
+            (dict(d_aud=z(65)), r"d_aud must be \[64\]"), (dict(d_expr=z(3, 76)), r"d_expr must be \[76\]"),
+            (dict(db0=None), "is None"), (dict(db5=None), "is None"), (dict(dbv=None, gW0=g0, gW5=g5, gWv0=gv), "is None"),
+            (dict(dbv=None, d_expr=z(76)), "is None"), (dict(db0=z(255)), r"db0 must be \[256\]"), (dict(db5=z(1, 256)), r"db5 must be \[256\]"),
+            (dict(dbv=z(256)), r"dbv must be \[128\]"), (dict(gW0=z(256, 234), gW5=g5, gWv0=gv), r"gW0 must be \[256, 235\]"),
+            (dict(gW0=g0, gW5=z(256, 235), gWv0=gv), r"gW5 must be \[256, 491\]"), (dict(gW0=g0, gW5=g5, gWv0=z(128, 283)), r"gWv0 must be \[128, 359\]"),
+            (dict(p=torso, gW0=g0, gW5=g5, gWv0=gv), r"gW0 must be \[256, 169\]"),
+            (dict(db0=z(256).double()), "db0 must be torch.float32"), (dict(d_aud=z(64).half()), "d_aud must be torch.float32"),
+            ({}, "must live on the GPU"), (dict(gW0=g0, gW5=g5, gWv0=gv, d_aud=z(64), d_expr=z(76), d_latent=z(32)), "must live on the GPU"),
+            (dict(p=torso, dbv=None, d_aud=z(106)), "must live on the GPU")):
+        with pytest.raises(E, match=match):
+            fold(**kw)
+
+    def colsums(dA0=m256, dA5=m256, dV0=m256, P=100, **kw):
+        return ops.cond_colsums(dA0, dA5, dV0, P, **kw)
+
+    for kw, match in (
+            (dict(dA0=None), "come together"), (dict(dA5=None), "come together"), (dict(dA0=None, dA5=None, dV0=None), "no matrix"),
+            (dict(dA0=torch.zeros(256, 128)), r"dA0 must be \[\*, 256\]"), (dict(dA0=None, dA5=None, dV0=torch.zeros(256, 128)), r"dV0 must be \[\*, 256\]"),
+            (dict(dA0=torch.zeros(192, 256)), "multiple of 128"), (dict(dA5=torch.zeros(128, 256)), r"dA5 must be \[256, 256\]"),
+            (dict(dV0=torch.zeros(384, 256)), r"dV0 must be \[256, 256\]"), (dict(P=257), "P 257 outside"), (dict(P=0), "P 0 outside"),
+            (dict(dA0=None, dA5=None, db=torch.zeros(2, 256)), "without its matrices"), (dict(dV0=None, dbv=torch.zeros(128)), "without its matrices"),
+            (dict(db=torch.zeros(512)), r"db must be \[2, 256\]"), (dict(dbv=torch.zeros(256)), r"dbv must be \[128\]"),
+            (dict(dA5=m256.double()), "dA5 must be torch.float32"), (dict(dbv=torch.zeros(128, dtype=torch.float64)), "dbv must be torch.float32"),
+            ({}, "must live on the GPU"), (dict(dA0=None, dA5=None), "must live on the GPU"), (dict(dV0=None, db=torch.zeros(2, 256)), "must live on the GPU")):
+        with pytest.raises(E, match=match):
+            colsums(**kw)
