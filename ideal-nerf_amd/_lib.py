@@ -185,6 +185,9 @@ PROTOTYPES = {
     "idealnerf_cull_classify": (C.c_int, [C.POINTER(CullGridStruct), C.POINTER(Frame), C.c_float, C.c_int, fp, fp, fp, C.c_size_t, fp]),
     "idealnerf_cull_gather": (C.c_int, [fp, C.c_int64, C.POINTER(Frame), fp, fp, fp, fp]),
     "idealnerf_cull_scatter": (C.c_int, [fp, C.c_int64, C.c_int64, fp, C.POINTER(CullOutput), C.c_int, fp]),
+    "idealnerf_cull_sample_classify": (C.c_int, [C.POINTER(CullGridStruct), fp, fp, C.c_int64, C.c_int, fp, fp, fp, C.c_size_t, fp]),
+    "idealnerf_cull_sample_gather": (C.c_int, [fp, C.c_int64, fp, fp, C.c_int64, C.c_int, fp, fp, fp]),
+    "idealnerf_cull_sample_scatter": (C.c_int, [fp, C.c_int64, fp, C.c_int64, fp, fp]),
     "idealnerf_profile_begin": (None, []),
     "idealnerf_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "idealnerf_profile_end_kinds": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -240,7 +240,9 @@ class Network(nn.Module):
                        perturb, white_bkgd, raw_noise_std, pytest, taps):
         """`_render` of a full frame with a cull grid: the live pixels through the same ops.render_rays_fwd (rays mode, same
         options), the others filled.  perturb > 0: the draws are made for the live rays -- [n_live, .] tensors, or in-kernel
-        with the row within the live list as the ray index -- so the numbers differ from the unculled frame's."""
+        with the row within the live list as the ray index -- so the numbers differ from the unculled frame's.  With
+        `grid.samples` the live rays go through ops.render_rays_sparse_fwd, which evaluates a network only at the samples the grid
+        cannot rule out: the same outputs and the same draws."""
         from . import cull
         cull.refuse(grid_name, taps, retraw, white_bkgd, raw_noise_std, lindisp)
         args = self.args
@@ -254,6 +256,10 @@ class Network(nn.Module):
             draws, t_rand, u = self._draws(n, S, Ni, perturb, pytest, dev, 0)
             fc = coarse.folded_bias(aud_para, expr, latent_code)
             ff = fine.folded_bias(aud_para, expr, latent_code) if Ni > 0 else None
+            if grid.samples:   # the live rays' empty samples are not evaluated either: same outputs (ops.render_rays_sparse_fwd)
+                return ops.render_rays_sparse_fwd(grid, rays, bc_live, coarse.packed_weights(), fc, fine.packed_weights() if Ni > 0 else None,
+                                                  ff, linspace01(S, dev), u, Ni, t_rand=t_rand, with_fg=with_fg, precision=coarse.prec_code,
+                                                  precision_fine=fine.prec_code if Ni > 0 else None, draws=draws)
             return ops.render_rays_fwd(rays, bc_live, coarse.packed_weights(), fc, fine.packed_weights() if Ni > 0 else None, ff,
                                        linspace01(S, dev), u, Ni, t_rand=t_rand, with_fg=with_fg, precision=coarse.prec_code,
                                        precision_fine=fine.prec_code if Ni > 0 else None, fused=0, draws=draws)

@@ -196,7 +196,8 @@ def render_head_clip(network, dataset, path, global_step, *, latent_code, frames
     ``stills_as_rgb``: the stills are written the way ``imageio.imwrite`` writes the frame's bytes -- taken as RGB, quality 75
     -- where the sink writes them as cv2 does (taken as BGR, quality 95): test_nerf.py:184-189 hands ONE array to both
     writers.  Each still is then written by the rank that rendered the frame.
-    ``cull``: None, or ``dict(G=, dilate=, sigma_min=, frame_stride=)`` (any subset; cull.DEFAULTS) -- before the first frame every
+    ``cull``: None, or ``dict(G=, dilate=, sigma_min=, frame_stride=, samples=)`` (any subset; cull.DEFAULTS; ``samples=True`` also
+    skips the live rays' samples in empty cells, same bytes, and adds ``evaluated_share`` to the result's ``cull``) -- before the first frame every
     rank builds the head pair's occupancy grid from the WHOLE clip (it reads every frame's item once more for it), installs
     it (``network.set_cull``) and removes it at the end; the result gains ``cull = dict(build_seconds, network_seconds,
     occupied_share, live_share)``.

@@ -881,4 +881,48 @@ int idealnerf_cull_scatter(const int64_t* sel, int64_t n_live, int64_t n_pixels,
     return launch_cull_scatter((const long long*)sel, n_live, n_pixels, bc, outputs, n_outputs, (hipStream_t)stream);
 }
 
+// ---- sample cull of the live rays (cull.hip) ----------------------------------------------
+static int check_cull_points(int64_t n, int S) {
+    if (n < 0 || S < 1) return fail(IDN_EINVAL, "bad sizes n=%lld S=%d", (long long)n, S);
+    if (n * (int64_t)S > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "more than 2^31-1 points in one call (n = %lld, S = %d)", (long long)n, S);
+    return IDN_OK;
+}
+
+int idealnerf_cull_sample_classify(const idn_cull_grid* grid, const float* rays, const float* z, int64_t n, int S, int64_t* sel,
+                                   int32_t* n_live, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!grid) return fail(IDN_EINVAL, "grid is NULL");
+    if (int e = check_cull_G(grid->G)) return e;
+    if (int e = check_cull_points(n, S)) return e;
+    if (!(grid->cell > 0.0f)) return fail(IDN_EINVAL, "cell must be positive");
+    if (!grid->bits || !n_live) return fail(IDN_EINVAL, "NULL pointer");
+    const int64_t n_points = n * S;
+    if (n_points == 0) {
+        IDN_HIP_CHECK(hipMemsetAsync(n_live, 0, sizeof(int32_t), (hipStream_t)stream));
+        return IDN_OK;
+    }
+    if (!rays || !z || !sel || !workspace) return fail(IDN_EINVAL, "NULL pointer");
+    if (workspace_bytes < cull_classify_workspace_bytes(n_points))
+        return fail(IDN_EWORKSPACE, "workspace of %zu bytes, the classification of %lld points needs %zu", workspace_bytes,
+                    (long long)n_points, cull_classify_workspace_bytes(n_points));
+    return launch_cull_sample_classify(*grid, rays, z, n_points, S, (long long*)sel, n_live, workspace, (hipStream_t)stream);
+}
+
+int idealnerf_cull_sample_gather(const int64_t* sel, int64_t m, const float* rays, const float* z, int64_t n, int S, float* pts,
+                                 float* dirs, void* stream) {
+    if (int e = check_cull_points(n, S)) return e;
+    if (m < 0 || m > n * S) return fail(IDN_EINVAL, "m = %lld is not in 0..n S", (long long)m);
+    if (m == 0) return IDN_OK;
+    if (!sel || !rays || !z || !pts || !dirs) return fail(IDN_EINVAL, "NULL pointer");
+    return launch_cull_sample_gather((const long long*)sel, m, rays, z, n * S, S, pts, dirs, (hipStream_t)stream);
+}
+
+int idealnerf_cull_sample_scatter(const int64_t* sel, int64_t m, const float* raw_live, int64_t n_points, float* raw, void* stream) {
+    if (n_points < 0 || m < 0 || m > n_points) return fail(IDN_EINVAL, "bad sizes m=%lld n_points=%lld", (long long)m, (long long)n_points);
+    if (n_points > 0x7fffffffLL) return fail(IDN_EUNSUPPORTED, "more than 2^31-1 points in one call");
+    if (n_points == 0) return IDN_OK;
+    if (!raw || (m > 0 && (!sel || !raw_live))) return fail(IDN_EINVAL, "NULL pointer");
+    if (((uintptr_t)raw | (uintptr_t)raw_live) & 15) return fail(IDN_EINVAL, "raw and raw_live must be 16-byte aligned (rows of four floats)");
+    return launch_cull_sample_scatter((const long long*)sel, m, raw_live, n_points, raw, (hipStream_t)stream);
+}
+
 }  // extern "C"

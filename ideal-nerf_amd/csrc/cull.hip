@@ -210,6 +210,120 @@ int launch_cull_classify(const idn_cull_grid& grid, const idn_frame& frame, floa
 }
 
 // ---------------------------------------------------------------------------
+// sample cull: the same count / scan / write over the points P = ray S + s of a depth array z [n, S].  A point is SKIPPABLE
+// when its cell is clear and raw2outputs cannot tell its network output from (0, 0, 0, 0): it is its ray's last sample (the
+// colour is replaced by the background pixel, and sigma_raw <= 0 gives the alpha of sigma_raw = 0), or the spacing to the
+// next sample is so short that alpha is +0.0f (the colour gate's fact, mlp_common.h: gate_point_dead).  Every other point
+// is LIVE; so is one with a NaN in its position (cull_point_occupied) or its spacing (the comparison is false).
+// ---------------------------------------------------------------------------
+// the point as point_of<kModeRays> forms it (mlp_common.h): product and sum rounded separately
+__device__ __forceinline__ void cull_sample_point(const float* rr, float z, float (&p)[3]) {
+    p[0] = rr[0] + rr[3] * z;
+    p[1] = rr[1] + rr[4] * z;
+    p[2] = rr[2] + rr[5] * z;
+}
+
+__global__ void __launch_bounds__(kCullThreads) cull_sample_count_kernel(CullGridDev g, const float* rays, const float* z, int S,
+                                                                          long n_points, unsigned long long* masks, int* counts) {
+    __shared__ int wave_count[kCullWaves];
+    const long P = (long)blockIdx.x * kCullThreads + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool live = false;
+    if (P < n_points) {
+        const unsigned ray = (unsigned)P / (unsigned)S;   // n_points < 2^31 (checked by the entry)
+        const bool last = (unsigned)P - ray * (unsigned)S == (unsigned)S - 1u;
+        const float* rr = rays + (long)ray * IDN_RAY_FLOATS;
+        const float zc = z[P], zn = z[last ? P : P + 1];   // never past a ray's (and so the array's) end
+        float p[3];
+        cull_sample_point(rr, zc, p);
+        // dist of composite_ray (march.h) and gate_point_dead, same operations in the same order
+        const float dn = sqrtf((rr[3] * rr[3] + rr[4] * rr[4]) + rr[5] * rr[5]);
+        float dist = zn - zc;
+        dist = dist * dn;
+        const bool skippable = !cull_point_occupied(g, p[0], p[1], p[2]) && (last || fabsf(dist) <= kGateMaxDist);
+        live = !skippable;
+    }
+    const unsigned long long ballot = __ballot(live);
+    if (lane == 0) {
+        masks[(long)blockIdx.x * kCullWaves + wave] = ballot;
+        wave_count[wave] = __popcll(ballot);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+#pragma unroll
+        for (int i = 0; i < kCullWaves; ++i) c += wave_count[i];
+        counts[blockIdx.x] = c;
+    }
+}
+
+int launch_cull_sample_classify(const idn_cull_grid& grid, const float* rays, const float* z, int64_t n_points, int S, long long* sel,
+                                int* n_live, void* ws, hipStream_t s) {
+    CullGridDev g;
+    g.bits = grid.bits;
+    g.G = grid.G;
+    for (int i = 0; i < 3; ++i) g.lo[i] = grid.lo[i];
+    g.cell = grid.cell;
+    const int n_blocks = (int)((n_points + kCullThreads - 1) / kCullThreads);
+    unsigned long long* masks = (unsigned long long*)ws;
+    int* counts = (int*)(masks + (size_t)n_blocks * kCullWaves);
+    int* offsets = counts + n_blocks;
+    hipLaunchKernelGGL(cull_sample_count_kernel, dim3(n_blocks), dim3(kCullThreads), 0, s, g, rays, z, S, (long)n_points, masks, counts);
+    IDN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(cull_scan_kernel, dim3(1), dim3(kCullThreads), 0, s, (const int*)counts, n_blocks, offsets, n_live);
+    IDN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(cull_write_kernel, dim3(n_blocks), dim3(kCullThreads), 0, s, (const unsigned long long*)masks,
+                       (const int*)offsets, (int)n_points, sel);
+    IDN_HIP_CHECK(hipGetLastError());
+    return IDN_OK;
+}
+
+// pts[j] = the point sel[j] (recomputed as above), dirs[j] = its ray's view direction: idealnerf_query_points_fwd's inputs, S = 1
+__global__ void cull_sample_gather_kernel(const long long* sel, long m, const float* rays, const float* z, int S, long n_points,
+                                          float* pts, float* dirs) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const long long P0 = sel[j];
+    const long P = (P0 >= 0 && P0 < n_points) ? (long)P0 : 0;   // a foreign index reads nothing outside the arrays
+    const float* rr = rays + (P / S) * IDN_RAY_FLOATS;
+    float p[3];
+    cull_sample_point(rr, z[P], p);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        pts[j * 3 + r] = p[r];
+        dirs[j * 3 + r] = rr[8 + r];
+    }
+}
+
+int launch_cull_sample_gather(const long long* sel, int64_t m, const float* rays, const float* z, int64_t n_points, int S, float* pts,
+                              float* dirs, hipStream_t s) {
+    hipLaunchKernelGGL(cull_sample_gather_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, sel, (long)m, rays, z, S,
+                       (long)n_points, pts, dirs);
+    IDN_HIP_CHECK(hipGetLastError());
+    return IDN_OK;
+}
+
+// raw [n_points, 4]: +0.0f everywhere (a fill), then raw_live[j] at sel[j]; sel holds each point once, so no two threads
+// write one address and the bytes are the same on every run
+__global__ void cull_sample_scatter_kernel(const long long* sel, long m, const float4* raw_live, long n_points, float4* raw) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const long long P = sel[j];
+    if (P < 0 || P >= n_points) return;   // a foreign index writes nothing
+    raw[P] = raw_live[j];
+}
+
+int launch_cull_sample_scatter(const long long* sel, int64_t m, const float* raw_live, int64_t n_points, float* raw, hipStream_t s) {
+    IDN_HIP_CHECK(hipMemsetAsync(raw, 0, (size_t)n_points * 4 * sizeof(float), s));
+    if (m > 0) {
+        hipLaunchKernelGGL(cull_sample_scatter_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, sel, (long)m,
+                           (const float4*)raw_live, (long)n_points, (float4*)raw);
+        IDN_HIP_CHECK(hipGetLastError());
+    }
+    return IDN_OK;
+}
+
+// ---------------------------------------------------------------------------
 // gather: the ray records and background pixels of the live pixels, in the order of `sel`
 // ---------------------------------------------------------------------------
 __global__ void cull_gather_kernel(const long long* sel, int n, CullFrameDev f, const float* bc, float* rays, float* bc_live) {

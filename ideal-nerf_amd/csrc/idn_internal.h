@@ -403,6 +403,12 @@ int launch_cull_gather(const long long* sel, int64_t n, const idn_frame& frame, 
                        hipStream_t s);
 int launch_cull_scatter(const long long* sel, int64_t n_live, int64_t npix, const float* bc, const idn_cull_output* outs, int n_outs,
                         hipStream_t s);
+// the sample cull of the live rays: classify + compact the points of z [n, S], gather their positions, scatter their outputs
+int launch_cull_sample_classify(const idn_cull_grid& grid, const float* rays, const float* z, int64_t n_points, int S, long long* sel,
+                                int* n_live, void* ws, hipStream_t s);
+int launch_cull_sample_gather(const long long* sel, int64_t m, const float* rays, const float* z, int64_t n_points, int S, float* pts,
+                              float* dirs, hipStream_t s);
+int launch_cull_sample_scatter(const long long* sel, int64_t m, const float* raw_live, int64_t n_points, float* raw, hipStream_t s);
 // metrics.hip: squared error and SSIM of a frame against its uint8 ground truth, whole frame and per region -> out [5, 4] fp64
 size_t frame_scores_workspace_bytes(int H, int W);
 int launch_frame_scores(const float* pred, const unsigned char* truth, const unsigned char* regions, int H, int W, double* out,

@@ -21,7 +21,7 @@ from . import ops
 from ._lib import IdealNerfError
 
 RAW_CHUNK_BYTES = 64 << 20   # no more than this much network output `raw` is alive at once while a grid is built
-DEFAULTS = dict(G=128, dilate=1, sigma_min=0.0, frame_stride=1)
+DEFAULTS = dict(G=128, dilate=1, sigma_min=0.0, frame_stride=1, samples=False)
 
 
 def _camera(c2w):
@@ -90,9 +90,11 @@ class CullGrid:
     """The occupancy of one coarse / fine pair over one clip.  bits: int32 [G^3 / 32] on the device, 32 cells per word along
     x; corners: uint8 [(G+1)^3], the marked lattice points (before dilation); lo (fp32 values) / cell: the box.
     `classify_calls` counts the classifications that ran (a frame whose camera and band are those of the call before is
-    answered from the cache: the torso pair's camera never changes within a clip, so it is classified once)."""
+    answered from the cache: the torso pair's camera never changes within a clip, so it is classified once).
+    `samples`: the live rays' network passes skip the samples in clear cells too (ops.render_rays_sparse_fwd), which counts
+    the points it saw and the points it evaluated here."""
 
-    def __init__(self, bits, corners, G, lo, cell, dilate, sigma_min, frame_stride=1, stats=None):
+    def __init__(self, bits, corners, G, lo, cell, dilate, sigma_min, frame_stride=1, stats=None, samples=False):
         self.bits, self.corners, self.G = bits, corners, int(G)
         self.lo = tuple(float(np.float32(v)) for v in lo)
         self.cell = float(np.float32(cell))
@@ -100,6 +102,8 @@ class CullGrid:
         self.stats = dict(stats or {})
         self.classify_calls = 0
         self.live_pixels = self.seen_pixels = 0
+        self.samples = bool(samples)
+        self.points_seen = self.points_evaluated = 0
         self._cache = None
 
     @property
@@ -110,6 +114,11 @@ class CullGrid:
     @property
     def live_share(self):
         return self.live_pixels / self.seen_pixels if self.seen_pixels else float("nan")
+
+    @property
+    def evaluated_share(self):
+        """Of the live rays' samples, the share a network evaluated (1 - the sample cull's saving)."""
+        return self.points_evaluated / self.points_seen if self.points_seen else float("nan")
 
     def check_contains(self, frame):
         """IdealNerfError unless the box holds the frustum of the frame's band (points outside it were never evaluated)."""
@@ -141,17 +150,20 @@ class CullGrid:
         return sel, n
 
 
-def build_grid(nets, conds, cameras, H, W, focal, near, far, *, G=128, dilate=1, sigma_min=0.0, frame_stride=1, cx=None, cy=None):
+def build_grid(nets, conds, cameras, H, W, focal, near, far, *, G=128, dilate=1, sigma_min=0.0, frame_stride=1, cx=None, cy=None,
+               samples=False):
     """The CullGrid of the networks `nets` (the coarse and the fine network of a pair) for a clip.
       conds    one (aud_para, expr, latent_code) per frame of the clip: the tensors the render loop passes to the pair
       cameras  every camera the pair is rendered from ([3, 4] / [4, 4] each; the torso pair: its one torso_pose)
     Every `frame_stride`-th frame's conditioning is folded as `_render` folds it, both networks are evaluated on the
     (G+1)^3 corner lattice of the box in their own arithmetic, and the corners with sigma_raw > sigma_min are marked; marks
     are ORed over frames and networks.  frame_stride > 1 gives up the guarantee: density that only the skipped frames'
-    conditioning produces is not seen.  At most RAW_CHUNK_BYTES (64 MiB) of network output is alive at once."""
+    conditioning produces is not seen.  `samples`: the grid also culls the live rays' samples (CullGrid.samples).  At most RAW_CHUNK_BYTES (64 MiB) of network output is alive at once."""
     ops._cull_G(G)
     if isinstance(frame_stride, bool) or not isinstance(frame_stride, int) or frame_stride < 1:
         raise IdealNerfError(f"frame_stride = {frame_stride!r}: a whole number >= 1")
+    if not isinstance(samples, bool):
+        raise IdealNerfError(f"samples = {samples!r}: True or False")
     if not conds or not len(cameras):
         raise IdealNerfError("a cull grid needs the clip's conditioning (one triple per frame) and its cameras")
     t0 = time.perf_counter()
@@ -186,7 +198,7 @@ def build_grid(nets, conds, cameras, H, W, focal, near, far, *, G=128, dilate=1,
     torch.cuda.synchronize(dev)
     stats = dict(build_seconds=time.perf_counter() - t0, network_seconds=sum(a.elapsed_time(b) for a, b in events) * 1e-3,
                  frames_marked=len(conds[::frame_stride]))
-    return CullGrid(bits, corners, G, lo, cell, dilate, sigma_min, frame_stride, stats)
+    return CullGrid(bits, corners, G, lo, cell, dilate, sigma_min, frame_stride, stats, samples)
 
 
 def options(cull):
@@ -200,9 +212,13 @@ def options(cull):
 
 
 def summary(grids):
-    """The ``cull`` entry of a clip's result: build time, occupied share and live share per pair."""
+    """The ``cull`` entry of a clip's result: build time, occupied share and live share per pair; with the sample cull on, the
+    share of the live rays' samples that a network evaluated."""
     grids = {k: g for k, g in grids.items() if g is not None}
-    return dict(build_seconds=sum(g.stats.get("build_seconds", 0.0) for g in grids.values()),
+    extra = {}
+    if any(g.samples for g in grids.values()):
+        extra["evaluated_share"] = {k: g.evaluated_share for k, g in grids.items() if g.samples}
+    return dict(**extra, build_seconds=sum(g.stats.get("build_seconds", 0.0) for g in grids.values()),
                 network_seconds=sum(g.stats.get("network_seconds", 0.0) for g in grids.values()),
                 occupied_share={k: g.occupied_share for k, g in grids.items()},
                 live_share={k: g.live_share for k, g in grids.items()})

@@ -55,7 +55,8 @@ def drive_head(args, *, out=None, global_step=0, device="cuda", codec="MJPG", st
     (``agg_aud_exp_nerf.Network``; its newest ``{epoch:06d}_head.tar``).  ValueError where the network's expression width --
     ``args.dim_expr``, the agg pair's 79 -- is not the expression track's.  ``learned_background``: render over the
     checkpoint's ``background`` instead of ``bc.jpg`` (it raises if the checkpoint holds none); off: nothing changes.
-    ``cull``: ``render_head_clip``'s (None, or the occupancy grid's options: empty rays are not rendered).
+    ``cull``: ``render_head_clip``'s (None, or the occupancy grid's options: empty rays are not rendered; with ``samples=True`` neither are
+    the live rays' samples in empty cells).
     -> ``render_head_clip``'s dict plus ``path`` on rank 0, None on the other ranks."""
     from .agg_aud_exp_nerf import DIM_EXPR, build_head_network
     frames = dataset.DrivingFrames(args.datadir, args.aud_file, "val", args, skip=args.testskip, device=device)

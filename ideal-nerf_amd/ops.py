@@ -1379,6 +1379,146 @@ def cull_scatter(sel, n_live, bc_rgb, outputs) -> Dict[str, torch.Tensor]:
     return dense
 
 
+# ---- sample cull of the live rays (csrc/cull.hip) ---------------------------------------------------
+def _cull_points(rays, z):
+    _shape(z, "z", None, None)
+    n, S = z.shape
+    _shape(rays, "rays", n, RAY_FLOATS)
+    if n * S >= 2 ** 31:
+        raise IdealNerfError(f"{n} rays of {S} samples: one sample cull takes fewer than 2^31 points")
+    return n, S
+
+
+def cull_sample_classify(bits, G, lo, cell, rays, z, sel=None, n_live=None):
+    """The live points of a network pass over rays [n, 11] / z [n, S] (idealnerf_cull_sample_classify): -> (sel int64 [n S],
+    n_live int32 [1]), both on the device; sel[:n_live] holds the live points P = ray S + s in ascending order, the rest is not
+    written.  A point is skipped when its cell is clear and it is its ray's last sample or its spacing is at most
+    idealnerf_colour_gate_max_dist(); every other point (occupied cell, outside the box, wider spacing, NaN) is live."""
+    lib = _lib.load()
+    n, S = _cull_points(rays, z)
+    _shape(sel, "sel", n * S)
+    _shape(n_live, "n_live", 1)
+    with _Launch(bits, rays, z, sel, n_live) as L:
+        g = _cull_grid_struct(bits, G, lo, cell)
+        ptrs = (_ptr(rays, "rays"), _ptr(z, "z"))
+        if sel is None:
+            sel = torch.empty(n * S, dtype=torch.int64, device=bits.device)
+        if n_live is None:
+            n_live = torch.empty(1, dtype=torch.int32, device=bits.device)
+        ws = _workspace(lib.idealnerf_cull_classify_workspace_bytes(n * S), bits.device, L.stream or 0)
+        check(lib.idealnerf_cull_sample_classify(C.byref(g), *ptrs, n, S, _ptr(sel, "sel", torch.int64),
+                                                 _ptr(n_live, "n_live", torch.int32), ws.data_ptr(), ws.numel(), L.stream))
+    return sel, n_live
+
+
+def cull_sample_gather(sel, rays, z):
+    """(pts [m, 3], dirs [m, 3]) of the points `sel` (int64 [m]) of rays [n, 11] / z [n, S]: the position the network kernels
+    form for the point, bit for bit, and its ray's view direction (idealnerf_cull_sample_gather) -- `query_points_fwd`'s
+    inputs as pts.view(m, 1, 3), dirs."""
+    lib = _lib.load()
+    n, S = _cull_points(rays, z)
+    _shape(sel, "sel", None)
+    m = sel.shape[0]
+    if m > n * S:
+        raise IdealNerfError(f"sel holds {m} points, the pass has {n * S}")
+    with _Launch(sel, rays, z) as L:
+        ptrs = (_ptr(sel, "sel", torch.int64), _ptr(rays, "rays"), _ptr(z, "z"))
+        pts = torch.empty((m, 3), dtype=torch.float32, device=sel.device)
+        dirs = torch.empty((m, 3), dtype=torch.float32, device=sel.device)
+        check(lib.idealnerf_cull_sample_gather(ptrs[0], m, ptrs[1], ptrs[2], n, S, pts.data_ptr(), dirs.data_ptr(), L.stream))
+    return pts, dirs
+
+
+def cull_sample_scatter(sel, m, raw_live, n, S, device=None) -> torch.Tensor:
+    """The dense raw [n, S, 4] of a sparse pass (idealnerf_cull_sample_scatter): row j of raw_live [m, 4] at point sel[j],
+    +0.0 in all four channels elsewhere.  m == 0: zeros on `device` (sel and raw_live may be None)."""
+    lib = _lib.load()
+    m, n, S = int(m), int(n), int(S)
+    if n < 0 or S < 1 or n * S >= 2 ** 31 or not 0 <= m <= n * S or (m and (sel is None or sel.dim() != 1 or sel.shape[0] < m)):
+        raise IdealNerfError(f"m = {m} live points of {n} x {S} with sel {None if sel is None else list(sel.shape)}")
+    if m:
+        _shape(raw_live, "raw_live", m, 4)
+    with _Launch(*((sel, raw_live) if m else ()), device=device) as L:
+        ptrs = (_ptr(sel, "sel", torch.int64), _ptr(raw_live, "raw_live")) if m else (None, None)
+        raw = torch.empty((n, S, 4), dtype=torch.float32, device=L.device)
+        check(lib.idealnerf_cull_sample_scatter(ptrs[0], m, ptrs[1], n * S, raw.data_ptr(), L.stream))
+    return raw
+
+
+def _sparse_pass(grid, packed, folded, rays, z, precision):
+    """One network pass over the live points only: classify, read the count (the pass's one host read), gather, the points
+    mode of the network's kernel, scatter.  -> raw [n, S, 4]."""
+    n, S = z.shape
+    sel, n_dev = cull_sample_classify(grid.bits, grid.G, grid.lo, grid.cell, rays, z)
+    m = int(n_dev.item())
+    grid.points_seen += n * S
+    grid.points_evaluated += m
+    raw_live = None
+    if m:
+        pts, dirs = cull_sample_gather(sel[:m], rays, z)
+        raw_live = query_points_fwd(packed, folded, pts.view(m, 1, 3), dirs, precision).view(m, 4)
+    return cull_sample_scatter(sel if m else None, m, raw_live, n, S, device=z.device)
+
+
+def render_rays_sparse_fwd(grid, rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals, u, n_importance, t_rand=None,
+                           with_fg=False, precision=IDN_PREC_F32, precision_fine=None, draws=None, chunk=32768, taps=False,
+                           lindisp=False, white_bkgd=False, noise_coarse=None, noise_fine=None, fused=None) -> Dict[str, torch.Tensor]:
+    """`render_rays_fwd` (rays mode, kernel sequence) with both network passes evaluated only at the samples the occupancy
+    `grid` (cull.CullGrid) cannot rule out: the same outputs under the same names, bit for bit while
+    sigma_raw <= 0 in the grid's clear cells.  Per `chunk` rays: coarse_depths, sparse coarse pass, march_fwd, sparse fine pass,
+    composite_fwd (n_importance == 0: the coarse pass and composite_fwd); two host reads per chunk (the passes' live counts),
+    which the grid adds to `points_seen` / `points_evaluated`.  `draws=(seed, ray0)`: the rows of the two draw tables are
+    materialised with `philox_uniform`, so the numbers are the in-kernel ones.  taps, density noise, white_bkgd, lindisp and
+    the fused arrangements are refused, as by `cull.refuse`."""
+    bad = [name for name, on in (("taps", taps), ("white_bkgd", white_bkgd), ("lindisp", lindisp),
+                                 ("density noise", noise_coarse is not None or noise_fine is not None),
+                                 ("a fused arrangement", (FUSED_MARCH_DEFAULT if fused is None else _fused_code(fused, "fused=")) != 0)) if on]
+    if bad:
+        raise IdealNerfError(f"{', '.join(bad)} with the sample cull: a skipped sample has no raw output to tap, and its argument "
+                             "holds for the plain kernel sequence without density noise or a white background")
+    if draws is not None and (u is not None or t_rand is not None):
+        raise IdealNerfError("draws=(seed, ray0) replaces BOTH t_rand and u: pass them as None")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise IdealNerfError(f"chunk = {chunk!r}: a whole number of rays >= 1")
+    _shape(t_vals, "t_vals", None)
+    _shape(rays, "rays", None, RAY_FLOATS)
+    n, S, Ni = rays.shape[0], t_vals.shape[0], int(n_importance)
+    _shape(bc_rgb, "bc_rgb", n, 3)
+    _shape(t_rand, "t_rand", n, S)
+    if Ni > 0:
+        if (u is None and draws is None) or packed_f is None or folded_f is None:
+            raise IdealNerfError("n_importance > 0 needs u (or draws=) and the fine network's packed / folded buffers")
+        if u is not None:
+            _u_shape(u, n, Ni)
+    prec_f = precision if precision_fine is None else precision_fine
+    # render_rays_fwd's names: the last compositing's outputs, and in front of a fine pass the march's under their *0 names
+    last = ("rgb_map", "disp_map", "acc_map") + (("last_weight",) if Ni > 0 else ()) + (("rgb_fg",) if with_fg else ())
+    first = dict(rgb_map="rgb0", disp_map="disp0", acc_map="acc0", z_std="z_std") if Ni > 0 else {}
+    if Ni > 0 and with_fg:
+        first.update(rgb_fg="rgb_fg0", last_weight="last_weight0")
+    parts: Dict[str, list] = {k: [] for k in last + tuple(first.values())}
+    for r0 in range(0, n, chunk):
+        r, bc = rays[r0:r0 + chunk], bc_rgb[r0:r0 + chunk]
+        c = r.shape[0]
+        tr, uc = (None if t_rand is None else t_rand[r0:r0 + chunk]), (u[r0:r0 + chunk] if u is not None and u.dim() == 2 else u)
+        if draws is not None:
+            tr = philox_uniform(draws[0], 0, int(draws[1]) + r0, c, S, rays.device)
+            uc = philox_uniform(draws[0], 1, int(draws[1]) + r0, c, Ni, rays.device) if Ni > 0 else None
+        z = coarse_depths(r, t_vals, tr)
+        raw = _sparse_pass(grid, packed_c, folded_c, r, z, precision)
+        if Ni > 0:
+            m = march_fwd(raw, z, r, bc, uc, Ni, with_fg=with_fg)
+            for old, new in first.items():
+                parts[new].append(m[old])
+            z = m["z_fine"]
+            raw = _sparse_pass(grid, packed_f, folded_f, r, z, prec_f)
+        f = composite_fwd(raw, z, r, bc, with_fg=with_fg, with_weights=False)
+        for k in last:
+            parts[k].append(f[k])
+    empty = lambda k: torch.empty((0, 3) if k.startswith("rgb") else (0,), dtype=torch.float32, device=bc_rgb.device)   # (no rays)
+    return {k: (torch.cat(v, 0) if len(v) > 1 else v[0] if v else empty(k)) for k, v in parts.items()}
+
+
 def profile_begin():
     """Start counting the network-kernel launches (idealnerf_profile_begin)."""
     _lib.load().idealnerf_profile_begin()

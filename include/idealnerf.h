@@ -828,6 +828,24 @@ typedef struct idn_cull_output {
 int idealnerf_cull_scatter(const int64_t* sel, int64_t n_live, int64_t n_pixels, const float* bc, const idn_cull_output* outputs,
                            int n_outputs, void* stream);
 
+/* Sample cull of the live rays: a network pass over rays [n, 11] / z [n, S] evaluated only where
+ * raw2outputs could tell the result from raw = (0, 0, 0, 0).  Point P = ray S + s lies at p = o + d z (product and sum
+ * rounded separately, the network kernels' own point) and is SKIPPABLE when p lies inside the grid's box in a cell whose bit
+ * is clear, and it is its ray's last sample (s == S - 1) or |dist| <= idealnerf_colour_gate_max_dist(), with
+ * dist = (z[s + 1] - z[s]) sqrtf((dx dx + dy dy) + dz dz) as the compositing forms it.  Every other point is LIVE (occupied
+ * cell, outside the box, wider spacing, a NaN anywhere).  Under the grid's contract (sigma_raw <= 0 in clear cells) the
+ * compositing of the scattered raw has the bits of the compositing of the full network pass.
+ * classify: sel [n S] int64 receives the live points in ascending order in its first *n_live entries (device int32; the
+ * rest is not written); n S < 2^31; workspace: idealnerf_cull_classify_workspace_bytes(n S).  No atomics.
+ * gather: pts [m, 3] / dirs [m, 3] of the points sel[0..m): idealnerf_query_points_fwd's inputs with n_samples = 1.
+ * scatter: raw [n_points, 4] = +0.0f everywhere, then row j of raw_live [m, 4] at point sel[j] (each point at most once:
+ * the same bytes on every run); both 16-byte aligned. */
+int idealnerf_cull_sample_classify(const idn_cull_grid* grid, const float* rays, const float* z, int64_t n, int S, int64_t* sel,
+                                   int32_t* n_live, void* workspace, size_t workspace_bytes, void* stream);
+int idealnerf_cull_sample_gather(const int64_t* sel, int64_t m, const float* rays, const float* z, int64_t n, int S, float* pts,
+                                 float* dirs, void* stream);
+int idealnerf_cull_sample_scatter(const int64_t* sel, int64_t m, const float* raw_live, int64_t n_points, float* raw, void* stream);
+
 /*
  * Measurement aid (no reference counterpart): between begin and end, every launch of
  * the fused PE+MLP kernel is bracketed by HIP events on its own stream.  end()

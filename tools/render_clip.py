@@ -48,27 +48,33 @@ def parse():
     ap.add_argument("--scene", choices=("xavier", "box"), default="xavier",
                     help="torso: box = the analytic scene of synthetic.box_density_state_dict (a head box and a lower torso box in empty "
                          "space; xavier density is positive in about half the volume and nothing culls there)")
-    ap.add_argument("--timing-json", default=None, help="torso: measure --cull 0 against --cull G (default 128) in this process, alternating, "
-                                                        "three rounds of warmed windows, and write the figures there")
+    ap.add_argument("--timing-json", default=None, help="torso: measure --cull 0 against --cull G (default 128) -- and, with --cull-samples, "
+                                                        "against --cull G --cull-samples -- in this process, alternating, three rounds of "
+                                                        "warmed windows, and write the figures there")
     cull_arguments(ap)
     return ap.parse_args()
 
 
 def cull_arguments(ap):
-    """--cull G and its three options, shared by the clip tools."""
+    """--cull G and its options, shared by the clip tools."""
     ap.add_argument("--cull", type=int, default=0, metavar="G",
                     help="skip empty rays with a per-clip occupancy grid of G^3 cells (a multiple of 32, e.g. 128); 0: off")
     ap.add_argument("--cull-dilate", type=int, default=None, help="cells of dilation (default 1)")
     ap.add_argument("--cull-sigma-min", type=float, default=None, help="a corner is occupied above this sigma_raw (default 0.0)")
     ap.add_argument("--cull-stride", type=int, default=None,
                     help="mark every k-th frame's conditioning only (default 1; k > 1 gives up the bit-exact guarantee)")
+    ap.add_argument("--cull-samples", action="store_true",
+                    help="with --cull G: the live rays' network passes skip the samples in empty cells too (same bytes)")
 
 
 def cull_option(args):
     """The flows' cull= argument from the command line: None when --cull is 0."""
     if not args.cull:
+        if args.cull_samples:
+            sys.exit("--cull-samples culls the samples of the rays the grid leaves live: it needs --cull G")
         return None
-    return dict(G=args.cull, dilate=args.cull_dilate, sigma_min=args.cull_sigma_min, frame_stride=args.cull_stride)
+    return dict(G=args.cull, dilate=args.cull_dilate, sigma_min=args.cull_sigma_min, frame_stride=args.cull_stride,
+                samples=True if args.cull_samples else None)
 
 
 def launch(n, argv, script=None):
@@ -215,21 +221,26 @@ def cull_timing(args, dev, net, track, common, rounds=3):
     each window warmed by --warmup frames and ended by the clip's own end (the last frame's bytes on the host).  The grid is
     built inside each culled window (its time is reported apart and is NOT in the arm's frames/s: a clip pays it once).
     Then, on the head pair's frame 0: the HIP-event times of classify, gather and fill + scatter, and the host cost of the
-    one n_live read."""
+    one n_live read.  With --cull-samples a third arm renders with the sample cull on as well (the grids' `samples`), its
+    `evaluated_share` is reported per pair, and the pieces gain the sample cull's three kernels and its read on the coarse and
+    on the fine pass of one 32 768-ray chunk of that frame's live rays."""
     import time
     import torch
     from idealnerf_amd import clip, cull, ops
-    opts = cull.options(dict(cull_option(args) or {}, G=args.cull or 128))
+    opts = cull.options(dict(cull_option(args) or {}, G=args.cull or 128, samples=None))
     poses, auds, bc = track["poses"], track["auds"], track["bc_img"]
     base = {k: v for k, v in common.items() if k != "cull"}
     n = args.frames
     frames = list(range(n))
     arms = {"cull_0": [], f"cull_{opts['G']}": []}
-    info = {}
+    if args.cull_samples:
+        arms[f"cull_{opts['G']}_samples"] = []
+    info, shares = {}, None
     for r in range(rounds):
         for name in arms:
             on = name != "cull_0"
-            grids = clip._torso_grids(net, poses, auds, bc, base["expr"], base["latent_code"], base["torso_pose"], frames, opts) if on else {}
+            arm_opts = dict(opts, samples=name.endswith("_samples"))
+            grids = clip._torso_grids(net, poses, auds, bc, base["expr"], base["latent_code"], base["torso_pose"], frames, arm_opts) if on else {}
             net.set_cull(**grids)
             try:
                 clip.render_torso_clip(net, poses, auds, bc, None, frames=range(args.warmup or 1), codec="raw", **base)
@@ -238,10 +249,14 @@ def cull_timing(args, dev, net, track, common, rounds=3):
             finally:
                 net.set_cull()
             arms[name].append(res["frames_per_s"])
-            if on:
+            if name.endswith("_samples"):
+                shares = cull.summary(grids)["evaluated_share"]
+            elif on:
                 info = cull.summary(grids)
                 info["frames_marked"] = {k: g.stats["frames_marked"] for k, g in grids.items()}
                 info["torso_classifications"] = grids["torso"].classify_calls
+    if shares is not None:
+        info["evaluated_share"] = shares
     # the pieces, on the head pair at frame 0
     grid = clip._torso_grids(net, poses, auds, bc, base["expr"], base["latent_code"], base["torso_pose"], frames, opts)["head"]
     H, W = int(bc.shape[0]), int(bc.shape[1])
@@ -278,6 +293,8 @@ def cull_timing(args, dev, net, track, common, rounds=3):
         n_dev.item()
         reads.append((time.perf_counter() - t0) * 1e6)
     pieces["n_live_read_idle_queue_us"] = sorted(reads)[len(reads) // 2]
+    if args.cull_samples:
+        pieces["samples"] = sample_pieces(dev, net, grid, rays[:32768].contiguous(), bc_live[:32768].contiguous(), base, timed)
     out = dict(scene=args.scene, size=args.size, dtype=args.precision, frames_per_window=n, rounds=rounds, warmup=args.warmup or 1,
                frames_per_s={k: dict(rounds=v, median=sorted(v)[len(v) // 2]) for k, v in arms.items()}, cull=info, pieces=pieces,
                options=opts, device=torch.cuda.get_device_name(dev))
@@ -285,6 +302,41 @@ def cull_timing(args, dev, net, track, common, rounds=3):
         json.dump(out, f, indent=1)
     return dict(n_frames=n, nonfinite_frames=[], seconds=0.0, frames_per_s=out["frames_per_s"][f"cull_{opts['G']}"]["median"], world=1,
                 timing=out)
+
+
+def sample_pieces(dev, net, grid, rays, bc_live, base, timed):
+    """The sample cull's own kernels and its read, per network pass, on one chunk of live rays of the head pair."""
+    import time
+    import torch
+    from idealnerf_amd import ops
+    from idealnerf_amd.helper import linspace01
+    S, Ni = net.args.N_samples, net.args.N_importance
+    coarse = net.face_nerf_coarse
+    with torch.no_grad():   # (a zero audio feature: the depths only have to be representative of a frame's)
+        folded = coarse.folded_bias(torch.zeros(coarse.dim_aud, device=dev), base["expr"].to(dev), base["latent_code"].to(dev))
+        z_c = ops.coarse_depths(rays, linspace01(S, dev))
+        raw = ops.query_rays_fwd(coarse.packed_weights(), folded, rays, z_c, coarse.prec_code)
+        z_f = ops.march_fwd(raw, z_c, rays, bc_live, linspace01(Ni, dev), Ni)["z_fine"]
+    out = dict(n_rays=int(rays.shape[0]))
+    for name, z in (("coarse", z_c), ("fine", z_f)):
+        n, Sz = z.shape
+        sel, n_dev = ops.cull_sample_classify(grid.bits, grid.G, grid.lo, grid.cell, rays, z)
+        m = int(n_dev.item())
+        pts, dirs = ops.cull_sample_gather(sel[:m], rays, z)
+        raw_live = torch.rand(m, 4, device=dev)
+        reads = []
+        for _ in range(20):
+            ops.cull_sample_classify(grid.bits, grid.G, grid.lo, grid.cell, rays, z, sel, n_dev)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            n_dev.item()
+            reads.append((time.perf_counter() - t0) * 1e6)
+        out[name] = dict(points=n * Sz, live=m,
+                         classify_us=timed(lambda: ops.cull_sample_classify(grid.bits, grid.G, grid.lo, grid.cell, rays, z, sel, n_dev)),
+                         gather_us=timed(lambda: ops.cull_sample_gather(sel[:m], rays, z)),
+                         fill_scatter_us=timed(lambda: ops.cull_sample_scatter(sel, m, raw_live, n, Sz)),
+                         count_read_idle_queue_us=sorted(reads)[len(reads) // 2])
+    return out
 
 
 def tail_timing(dev, sizes=(450, 512), reps=200):
