@@ -102,6 +102,13 @@ class DwProduct(C.Structure):
                 ("splits", C.c_int), ("chunks_per_split", C.c_int)]
 
 
+PATCH_MAX, PATCH_MIN_P, PATCH_MAX_P = 16, 11, 48   # IDN_PATCH_MAX, IDN_PATCH_MIN_P, IDN_PATCH_MAX_P
+
+
+class PatchSet(C.Structure):
+    _fields_ = [("n_patches", C.c_int), ("p", C.c_int), ("oy", C.c_int * PATCH_MAX), ("ox", C.c_int * PATCH_MAX)]   # idn_patch_set
+
+
 ABI_VERSION = 4   # idealnerf_version(): 4 since idn_render_args carries `rng_mode / rng_seed / rng_ray0` (3: `fused_march`)
 
 # name -> (restype, argtypes); mirrors include/idealnerf.h one to one
@@ -132,6 +139,9 @@ PROTOTYPES = {
                                              C.c_float, C.c_float, fp, fp, fp, fp, fp, fp, fp, fp, fp]),
     "idealnerf_frame_scores_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "idealnerf_frame_scores": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
+    "idealnerf_patch_pixels": (C.c_int, [C.POINTER(PatchSet), C.c_int, fp, fp]),
+    "idealnerf_ssim_patch_fwd": (C.c_int, [fp, fp, C.c_int, C.c_int, fp, fp]),
+    "idealnerf_ssim_patch_bwd": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_float, fp, fp]),
     "idealnerf_coarse_depths": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, fp, fp]),
     "idealnerf_composite_fwd": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int64, C.c_int, C.POINTER(CompositeOut), fp]),
     "idealnerf_sample_pdf_fwd": (C.c_int, [fp, fp, fp, C.c_int, C.c_int64, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp]),

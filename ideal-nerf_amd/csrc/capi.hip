@@ -262,6 +262,36 @@ int idealnerf_frame_scores(const float* pred, const uint8_t* truth, const uint8_
     return launch_frame_scores(pred, truth, regions, H, W, out, (double*)workspace, (hipStream_t)stream);
 }
 
+static int check_patches(int n_patches, int p) {
+    if (n_patches < 1 || n_patches > IDN_PATCH_MAX) return fail(IDN_EINVAL, "n_patches %d is outside 1..%d", n_patches, IDN_PATCH_MAX);
+    if (p < IDN_PATCH_MIN_P || p > IDN_PATCH_MAX_P)
+        return fail(IDN_EINVAL, "patch edge %d is outside %d..%d", p, IDN_PATCH_MIN_P, IDN_PATCH_MAX_P);
+    return IDN_OK;
+}
+
+int idealnerf_patch_pixels(const idn_patch_set* set, int W, int64_t* sel_out, void* stream) {
+    if (!set || !sel_out) return fail(IDN_EINVAL, "NULL pointer");
+    if (int e = check_patches(set->n_patches, set->p)) return e;
+    if (W <= 0 || W > (1 << 15)) return fail(IDN_EINVAL, "bad frame width %d", W);
+    for (int k = 0; k < set->n_patches; ++k)
+        if (set->oy[k] < 0 || set->oy[k] > (1 << 15) || set->ox[k] < 0 || set->ox[k] + set->p > W)
+            return fail(IDN_EINVAL, "patch %d at (%d, %d) with edge %d leaves a frame %d wide", k, set->oy[k], set->ox[k], set->p, W);
+    return launch_patch_pixels(*set, W, (long long*)sel_out, (hipStream_t)stream);
+}
+
+int idealnerf_ssim_patch_fwd(const float* pred, const float* truth, int n_patches, int p, double* out, void* stream) {
+    if (int e = check_patches(n_patches, p)) return e;
+    if (!pred || !truth || !out) return fail(IDN_EINVAL, "NULL pointer (pred, truth or out)");
+    if ((uintptr_t)out & 7u) return fail(IDN_EINVAL, "out is not 8-byte aligned");
+    return launch_ssim_patch_fwd(pred, truth, n_patches, p, out, (hipStream_t)stream);
+}
+
+int idealnerf_ssim_patch_bwd(const float* pred, const float* truth, int n_patches, int p, float g, float* d_pred, void* stream) {
+    if (int e = check_patches(n_patches, p)) return e;
+    if (!pred || !truth || !d_pred) return fail(IDN_EINVAL, "NULL pointer (pred, truth or d_pred)");
+    return launch_ssim_patch_bwd(pred, truth, n_patches, p, g, d_pred, (hipStream_t)stream);
+}
+
 int idealnerf_coarse_depths(const float* rays, const float* t_vals, const float* t_rand, int lindisp, int64_t n_rays,
                             int n_samples, float* z, void* stream) {
     if (n_rays < 0 || n_samples < 1) return fail(IDN_EINVAL, "bad sizes");

@@ -413,6 +413,10 @@ int launch_cull_sample_scatter(const long long* sel, int64_t m, const float* raw
 size_t frame_scores_workspace_bytes(int H, int W);
 int launch_frame_scores(const float* pred, const unsigned char* truth, const unsigned char* regions, int H, int W, double* out,
                         double* partial, hipStream_t s);
+// ssim_loss.hip: the pixel indices of a set of patches, the patch SSIM loss -> out [n_patches + 1] fp64, and its gradient
+int launch_patch_pixels(const idn_patch_set& set, int W, long long* sel, hipStream_t s);
+int launch_ssim_patch_fwd(const float* pred, const float* truth, int n_patches, int p, double* out, hipStream_t s);
+int launch_ssim_patch_bwd(const float* pred, const float* truth, int n_patches, int p, float g, float* d_pred, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Backward delta chain (mlp_f32_bwd.hip): the transposed weights as a second fragment stream.

@@ -337,10 +337,35 @@ class ResidentFrames:
 
     Raises ``ValueError`` at construction -- from the host-side populations, before anything is uploaded -- if the clip needs
     more than ``max_bytes`` of device memory or if a region of a frame holds fewer pixels than its share of ``N_rand`` (the step
-    at which upstream's ``np.random.choice`` raises)."""
+    at which upstream's ``np.random.choice`` raises).
 
-    def __init__(self, data_dir, aud_file, mode, args, skip=1, device="cuda", max_bytes=8 << 30, seed=0):
+    ``patches=(k, p)`` (no counterpart upstream; None: nothing below exists and the draw, both launches and every byte are what
+    they were): k contiguous p x p patches ride in every batch, for ``ssim_loss.ssim_patch_loss``.  The batch KEEPS its
+    ``N_rand`` rows: the k p^2 patch rays come out of the rect region's share -- ``counts = (rect - k p^2, outside, mouth,
+    torso)``, ValueError at construction if that goes negative -- so a step's network shapes do not change.  ``batch`` puts the
+    sampler's rows first and the patches' pixel indices (``ops.patch_pixels``) in the tail of the same selection buffer, and
+    ONE gather covers all rows: three launches, still no host synchronisation, no device-to-host copy, no allocation beyond the
+    outputs.  ``patch_rows()`` is the tail as a slice; ``selection()`` stays the whole buffer.  The patches' top-left corners
+    are ``ssim_loss.patch_origins(seed, index, draw, ...)``: computed on the HOST from a counter-based generator, a function
+    of (seed, frame index, draw) alone, from the frames' ``face_rect`` kept on the host.  ``patch_region`` = "rect" (default):
+    uniform over the origins for which the patch lies inside the face rect clipped to the frame (centred on the rect and
+    clamped to the frame where the rect is narrower than p); "frame": uniform over the frame.  ``patch_origins_of(index,
+    draw)`` returns them.  A patch pixel may also be one of the sampler's picks: the two draws are independent."""
+
+    _takes_patches = True
+
+    def __init__(self, data_dir, aud_file, mode, args, skip=1, device="cuda", max_bytes=8 << 30, seed=0, patches=None,
+                 patch_region="rect"):
         self.data_dir, self.aud_file, self.mode, self.args, self.device, self.seed = data_dir, aud_file, mode, args, device, int(seed)
+        self.patches = None
+        if patches is not None:
+            from .ssim_loss import PATCH_REGIONS, check_patches
+            if not self._takes_patches:
+                raise ValueError(f"{type(self).__name__} takes no patches: the torso stage has no SSIM term")
+            self.patches = check_patches(patches)
+            if patch_region not in PATCH_REGIONS:
+                raise ValueError(f"patch_region must be one of {PATCH_REGIONS}, got {patch_region!r}")
+        self.patch_region = patch_region
         with open(os.path.join(data_dir, f"transforms_exp_{mode}.json")) as fp:
             self.meta = json.load(fp)
         frames = self.meta["frames"][::skip]
@@ -354,6 +379,18 @@ class ResidentFrames:
         self.counts = self._counts(args)
         if min(self.counts) < 0:
             raise ValueError(f"N_rand {args.N_rand} is smaller than mouth_rays + torso_rays")
+        self._patch_rows = slice(sum(self.counts), sum(self.counts))
+        if self.patches is not None:
+            k, p = self.patches
+            rect = self.counts[0]
+            if k * p * p > rect:
+                raise ValueError(f"patches = ({k}, {p}) take {k} * {p}^2 = {k * p * p} rays out of the rect region's share of the "
+                                 f"batch, which is {rect} of N_rand = {args.N_rand}: fewer or smaller patches, or a larger N_rand")
+            if p > self.H or p > self.W:
+                raise ValueError(f"a patch of {p} x {p} does not fit a {self.H} x {self.W} frame")
+            self._patch_rows = slice(sum(self.counts) - k * p * p, sum(self.counts))
+            self.counts = (rect - k * p * p, *self.counts[1:])
+        self.face_rects = [np.array(f["face_rect"], dtype=np.int32) for f in frames]   # on the host: the patch origins need them
         from ._lib import SAMPLE_MAX_REGION
         if max(self.counts) > SAMPLE_MAX_REGION:
             raise ValueError(f"the split {dict(zip(REGION_NAMES, self.counts))} asks a region for more than the sampler's "
@@ -394,7 +431,9 @@ class ResidentFrames:
         self.auds = torch.tensor(np.asarray(auds), dtype=torch.float).to(device)
         self.poses = torch.tensor(np.asarray(poses), dtype=torch.float32).to(device)
         self.exprs = None if exprs and exprs[0] is None else torch.tensor(np.asarray(exprs), dtype=torch.float32).to(device)
-        self._sel = torch.empty(sum(self.counts), dtype=torch.int64, device=device)
+        self._sel = torch.empty(self._patch_rows.stop, dtype=torch.int64, device=device)
+        # (without patches the views below are the buffer itself and an empty tail)
+        self._sel_sampled, self._sel_patches = self._sel[:self._patch_rows.start], self._sel[self._patch_rows]
         self._ws = torch.zeros(4, dtype=torch.int32, device=device)
         if torch.device(device).type == "cuda":
             ops.byte_tables(device)                              # built here, so that batch() allocates nothing but its outputs
@@ -441,7 +480,22 @@ class ResidentFrames:
     def select(self, index, draw):
         """The flat pixel indices of draw `draw` on frame `index` (int64 [N_rand]; the loader's own buffer, overwritten by
         the next call in stream order)."""
-        return ops.sample_pixels(self.maps[index], self.counts, self.seed, draw, out=self._sel, workspace=self._ws)
+        if self.patches is None:
+            return ops.sample_pixels(self.maps[index], self.counts, self.seed, draw, out=self._sel, workspace=self._ws)
+        ops.sample_pixels(self.maps[index], self.counts, self.seed, draw, out=self._sel_sampled, workspace=self._ws)
+        ops.patch_pixels(self.patch_origins_of(index, draw), self.patches[1], self.W, out=self._sel_patches)
+        return self._sel
+
+    def patch_origins_of(self, index, draw):
+        """[(oy, ox)] * k: the top-left corners of the patches of draw `draw` on frame `index` (host numbers, no device read)."""
+        from .ssim_loss import patch_origins
+        k, p = self.patches
+        return patch_origins(self.seed, int(index), draw, k, p, self.H, self.W, self.face_rects[int(index)], self.patch_region)
+
+    def patch_rows(self):
+        """The rows of a batch (and of ``selection()``) that hold the patches, k p^2 of them, patch by patch and row-major inside
+        a patch: the tail of the batch.  An empty slice at its end without ``patches``."""
+        return self._patch_rows
 
     def selection(self):
         """The flat pixel indices of the latest ``select`` / ``batch`` (int64 [N_rand], row-major over H x W): row i of that
@@ -469,9 +523,11 @@ class ResidentTorsoFrames(ResidentFrames):
       sets from one launch (``ops.gather_ray_pairs``; the second camera is the clip's frame-0 pose); ``frame`` the eval 9-tuple.
 
     Beside ``ResidentFrames``' construction errors, ``ValueError`` where ``use_highlight`` is set and a frame's M exceeds its
-    outside population -- the frames on which upstream's mouth block can raise IndexError."""
+    outside population -- the frames on which upstream's mouth block can raise IndexError.  ``patches`` is not for this stage
+    (its step has no SSIM term): anything but None raises ValueError."""
 
     _no_sets = 3
+    _takes_patches = False
 
     def _counts(self, args):
         return ops.sample_counts(args.N_rand, torso_mouth_num(args.N_rand, args.use_highlight), 0, args.sample_rate)
@@ -498,9 +554,10 @@ class ResidentAggFrames(ResidentTorsoFrames):
     """``ResidentFrames`` for the feature-aggregation trainer: the resident counterpart of ``AggGetData``.  The torso stage's
     byte map, counts, construction errors and RGB images (``ResidentTorsoFrames``) with the head stage's single camera:
     ``batch`` returns the 8-tuple (batch_rays, target_s, bc_rgb, auds, raw_img, pose, expr, index) from ``ops.gather_rays``,
-    ``frame`` the eval 8-tuple (``mode="val"``)."""
+    ``frame`` the eval 8-tuple (``mode="val"``).  ``patches`` / ``patch_region``: as ``ResidentFrames``."""
 
     _no_sets = 2
+    _takes_patches = True
     _gather = ResidentFrames._gather
 
 

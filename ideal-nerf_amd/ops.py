@@ -1164,6 +1164,85 @@ def gather_ray_pairs(sel, c2w, c2w_torso, H, W, focal, image, background, cx=Non
     return gather_rays(sel, c2w, H, W, focal, image, background, cx, cy, c2w_torso=c2w_torso)
 
 
+PATCH_MAX, PATCH_MIN_P, PATCH_MAX_P = _lib.PATCH_MAX, _lib.PATCH_MIN_P, _lib.PATCH_MAX_P
+
+
+def _check_patches(n_patches, p):
+    n_patches, p = int(n_patches), int(p)
+    if not 1 <= n_patches <= PATCH_MAX:
+        raise IdealNerfError(f"n_patches {n_patches} is outside 1..{PATCH_MAX}")
+    if not PATCH_MIN_P <= p <= PATCH_MAX_P:
+        raise IdealNerfError(f"patch edge {p} is outside {PATCH_MIN_P}..{PATCH_MAX_P}")
+    return n_patches, p
+
+
+def patch_set(origins, p):
+    """[(oy, ox), ...] top-left corners (host numbers) and the edge p -> the idn_patch_set the kernel takes as arguments."""
+    origins = [(int(oy), int(ox)) for oy, ox in origins]
+    k, p = _check_patches(len(origins), p)
+    s = _lib.PatchSet()
+    s.n_patches, s.p = k, p
+    for i, (oy, ox) in enumerate(origins):
+        s.oy[i], s.ox[i] = oy, ox
+    return s
+
+
+def patch_pixels(origins, p, W, out=None, device=None) -> torch.Tensor:
+    """The flat row-major pixel indices of k p x p patches (idealnerf_patch_pixels): origins [(oy, ox), ...] on the HOST (they
+    travel as kernel arguments) or a ``patch_set`` of them -> int64 [k p p], patch by patch, row-major inside a patch.  `out`:
+    the caller's buffer (e.g. the tail of a loader's selection), for a call that allocates nothing; without it the result is
+    allocated on `device` (default: the current GPU).  k outside 1..16, p outside 11..48 or a patch that leaves the W columns
+    raise IdealNerfError."""
+    lib = _lib.load()
+    s = origins if isinstance(origins, _lib.PatchSet) else patch_set(origins, p)
+    k, p = _check_patches(s.n_patches, s.p)
+    _shape(out, "out", k * p * p)
+    with _Launch(out, device=None if out is not None else (device or "cuda")) as L:
+        if out is None:
+            out = torch.empty(k * p * p, dtype=torch.int64, device=L.device)
+        check(lib.idealnerf_patch_pixels(C.byref(s), int(W), _ptr(out, "out", torch.int64), L.stream))
+    return out
+
+
+def _patch_rows(t, name, n_patches, p):
+    if t.numel() != n_patches * p * p * 3 or t.shape[-1] != 3:
+        raise IdealNerfError(f"{name} must hold [{n_patches}, {p}, {p}, 3] values in rows of 3, got {list(t.shape)}")
+
+
+def ssim_patch_fwd(pred, truth, n_patches, p, out=None) -> torch.Tensor:
+    """The patch SSIM loss (idealnerf_ssim_patch_fwd): pred, truth fp32 [n_patches, p, p, 3] (or the [n_patches p p, 3] rows a
+    render and a gather return for ``patch_pixels``) -> float64 [n_patches + 1] on the device: each patch's mean SSIM index over
+    its 3 (p - 10)^2 windows, then the loss 1 - mean.  ``frame_scores``' index; fp64 sums in a fixed order, no atomics."""
+    lib = _lib.load()
+    n_patches, p = _check_patches(n_patches, p)
+    _patch_rows(pred, "pred", n_patches, p)
+    _patch_rows(truth, "truth", n_patches, p)
+    _shape(out, "out", n_patches + 1)
+    with _Launch(pred, truth, out) as L:
+        ptrs = (_ptr(pred, "pred"), _ptr(truth, "truth"))
+        if out is None:
+            out = torch.empty(n_patches + 1, dtype=torch.float64, device=pred.device)
+        check(lib.idealnerf_ssim_patch_fwd(*ptrs, n_patches, p, _ptr(out, "out", torch.float64), L.stream))
+    return out
+
+
+def ssim_patch_bwd(pred, truth, n_patches, p, g=1.0, out=None) -> torch.Tensor:
+    """g * d loss / d pred of ``ssim_patch_fwd``'s loss (idealnerf_ssim_patch_bwd) -> fp32, pred's shape, each element rounded
+    once from fp64; g is a host number.  truth gets no gradient."""
+    lib = _lib.load()
+    n_patches, p = _check_patches(n_patches, p)
+    _patch_rows(pred, "pred", n_patches, p)
+    _patch_rows(truth, "truth", n_patches, p)
+    if out is not None:
+        _shape(out, "out", *pred.shape)
+    with _Launch(pred, truth, out) as L:
+        ptrs = (_ptr(pred, "pred"), _ptr(truth, "truth"))
+        if out is None:
+            out = torch.empty_like(pred)
+        check(lib.idealnerf_ssim_patch_bwd(*ptrs, n_patches, p, float(g), _ptr(out, "out"), L.stream))
+    return out
+
+
 def render_rays_fwd(rays, bc_rgb, packed_c, folded_c, packed_f, folded_f, t_vals, u, n_importance,
                     t_rand=None, with_fg=False, taps=False, precision=IDN_PREC_F32, precision_fine=None, lindisp=False,
                     white_bkgd=False, noise_coarse=None, noise_fine=None, fused=None, frame=None, draws=None,

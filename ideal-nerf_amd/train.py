@@ -25,9 +25,20 @@ def decayed_lr(lrate, lrate_decay, global_step, decay_rate=0.1):
     return lrate * (decay_rate ** (global_step / (lrate_decay * 1500)))
 
 
-def train_step(network, optimizer, data, latent_codes, global_step, dataset_size, lrate=8e-4, lrate_decay=500):
+def _ssim_term(ssim, rgb, target):
+    """``ssim`` = (weight, rows, k, p) of a step (``train(ssim_weight=, patches=)``) -> (weight * ssim_patch_loss on the FINE
+    image's patch rows, the unweighted loss detached)."""
+    from .ssim_loss import ssim_patch_loss
+    weight, rows, k, p = ssim
+    term = ssim_patch_loss(rgb[rows], target[rows], k, p)
+    return weight * term, term.detach()
+
+
+def train_step(network, optimizer, data, latent_codes, global_step, dataset_size, lrate=8e-4, lrate_decay=500, ssim=None):
     """One iteration of the loop at audio_exp_nerf.py:530-558.  ``data`` is the reference's
-    8-tuple (batch_rays, target_s, bg_img, auds, raw_img, pose, expr, index)."""
+    8-tuple (batch_rays, target_s, bg_img, auds, raw_img, pose, expr, index).  ssim = (weight, rows, k, p) (no counterpart
+    upstream; None: the step is what it was): ``weight * ssim_patch_loss`` of the fine image on the batch's patch rows
+    (``ResidentFrames.patch_rows``) joins the loss, and the returned dict gains ``ssim_loss``, the unweighted term."""
     batch_rays, target_s, bg_img, auds, raw_img, pose, expr, index = data
     latent_code = latent_codes[int(index)]
     rgb, _, _, _, extras = network([(batch_rays, target_s, bg_img, auds, raw_img, pose, expr, latent_code, index),
@@ -41,14 +52,20 @@ def train_step(network, optimizer, data, latent_codes, global_step, dataset_size
         loss = loss + img2mse(extras['rgb0'], target)
     latent_code_loss = torch.norm(latent_code) * network.args.lc_weight
     loss = loss + latent_code_loss * 10
+    if ssim is not None:
+        term, ssim_loss = _ssim_term(ssim, rgb, target)
+        loss = loss + term
     new_lrate = _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay)
-    return dict(loss=loss.detach(), psnr=psnr, latent_code_loss=latent_code_loss.detach(), lr=new_lrate)
+    info = dict(loss=loss.detach(), psnr=psnr, latent_code_loss=latent_code_loss.detach(), lr=new_lrate)
+    if ssim is not None:
+        info["ssim_loss"] = ssim_loss
+    return info
 
 
-def baseline_train_step(network, optimizer, data, global_step, dataset_size, lrate=5e-4, lrate_decay=500):
+def baseline_train_step(network, optimizer, data, global_step, dataset_size, lrate=5e-4, lrate_decay=500, ssim=None):
     """One iteration of the AD-NeRF baseline's loop (NeRFs/HeadNeRF/train/head_baseline.py:466-491) on ``head_baseline.Network``:
     ``data`` is the baseline loader's 7-tuple (batch_rays, target_s, bg_img, auds, raw_img, pose, index); the loss is
-    mse(rgb, target) + mse(rgb0, target) (:475-481) -- there is no latent code and so no latent term."""
+    mse(rgb, target) + mse(rgb0, target) (:475-481) -- there is no latent code and so no latent term.  ssim: as ``train_step``."""
     target_s = data[1]
     rgb, _, _, _, extras = network([data, global_step, dataset_size])
     target = target_s.reshape(-1, 3).to(rgb.device, torch.float32)
@@ -58,8 +75,14 @@ def baseline_train_step(network, optimizer, data, global_step, dataset_size, lra
     psnr = mse2psnr(img_loss.detach())
     if 'rgb0' in extras:
         loss = loss + img2mse(extras['rgb0'], target)
+    if ssim is not None:
+        term, ssim_loss = _ssim_term(ssim, rgb, target)
+        loss = loss + term
     new_lrate = _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay)
-    return dict(loss=loss.detach(), psnr=psnr, lr=new_lrate)
+    info = dict(loss=loss.detach(), psnr=psnr, lr=new_lrate)
+    if ssim is not None:
+        info["ssim_loss"] = ssim_loss
+    return info
 
 
 def _backward_and_update(loss, optimizer, global_step, lrate, lrate_decay):
@@ -126,7 +149,7 @@ def _summary_writer(logdir):
 
 def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, on_log=None, on_step=None, max_bytes=8 << 30,
           val="reference", refine_poses=False, pose_lrate=None, refine_expr=False, expr_lrate=None, learn_background=False,
-          bg_lrate=None):
+          bg_lrate=None, ssim_weight=0.0, patches=None, patch_region="rect"):
     """The reference's ``train()`` (audio_exp_nerf.py:451-593) on the flags ``args`` (``helper.config_parser().parse_args()``):
     write_config, the train and validation datasets, ``Network`` + ``init_weights``, ``latent_codes = ones[n_frames, 32]``, Adam,
     warm start from ``ft_path`` or resume from the newest ``*.tar`` of ``basedir/expname``, then epochs over the frames in
@@ -175,23 +198,37 @@ def train(args, *, loader="resident", sample_seed=0, device="cuda", steps=None, 
     continues bit for bit under the conditions above as long as no pixel is drawn more than twice in a batch: two addends
     commute).  Validation frames keep their own expressions and are rendered over the learned background.  A model without an
     expression (the AD-NeRF baseline) raises ValueError for refine_expr.  The torso stage has neither option.
+
+    ssim_weight / patches / patch_region (no counterpart upstream, whose image-level terms need external weights; off -- the
+    defaults --: the draw, every launch, the checkpoint's keys and every byte of the run are what they were): SSIM, the
+    structural score ``val/ssim`` reports, as a training term.  patches = (k, p): every batch carries k contiguous p x p patches
+    in its last k p^2 rows (``ResidentFrames(patches=, patch_region=)``: the batch keeps N_rand rows, the patch rays come out of
+    the rect region's share; patch_region "rect" or "frame" is where their corners are drawn) -- which only the resident loader
+    can do: with loader = "reference" it raises ValueError.  Upstream's terms run over all N_rand rows as before, and the step
+    adds ``ssim_weight * ssim_patch_loss(rgb[patch rows], target[patch rows])`` on the FINE image alone (``ssim_loss.py``:
+    1 - mean SSIM over the patches, the scorer's index, on the device in fp64).  ssim_weight > 0 needs patches (ValueError);
+    patches with ssim_weight = 0 only changes the draw.  ``ssim_weight`` has no tuned default: nobody has measured what it does
+    to a trained model.  ``info`` of ``on_step`` and the "train" payload of ``on_log`` gain ``ssim_loss`` (the unweighted term).
+    The option composes with the three above, adds no parameter and no checkpoint key, and a resumed run reproduces the patch
+    positions: they are a function of (sample_seed, frame, draw index) alone.  The torso stage does not have it.
     -> dict(network, optimizer, latent_codes, global_step, data_size[, pose_refiner][, expr_refiner][, background])."""
     from . import dataset
     return _train_head_model(args, "head", dataset.ResidentFrames, dataset.GetData, lambda epoch: 'head.tar', True, loader=loader,
                              sample_seed=sample_seed, device=device, steps=steps, on_log=on_log, on_step=on_step,
                              max_bytes=max_bytes, val=val, refine_poses=refine_poses, pose_lrate=pose_lrate,
-                             refine_expr=refine_expr, expr_lrate=expr_lrate, learn_background=learn_background, bg_lrate=bg_lrate)
+                             refine_expr=refine_expr, expr_lrate=expr_lrate, learn_background=learn_background, bg_lrate=bg_lrate,
+                             ssim_weight=ssim_weight, patches=patches, patch_region=patch_region)
 
 
 def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name, flip, *, loader, sample_seed, device, steps,
                       on_log, on_step, max_bytes, val, with_codes=True, refine_poses=False, pose_lrate=None, refine_expr=False,
-                      expr_lrate=None, learn_background=False, bg_lrate=None):
+                      expr_lrate=None, learn_background=False, bg_lrate=None, ssim_weight=0.0, patches=None, patch_region="rect"):
     """The body of ``train`` for a head-stage model (``agg_aud_exp_nerf.HEAD_MODELS``): its two loader classes, its checkpoint
     name per epoch, and whether the validation image is channel-flipped (the loader reads BGR).  with_codes=False (the AD-NeRF
     baseline): no per-frame latent codes exist -- Adam runs over the network alone, the step is ``baseline_train_step`` on the
     loaders' 7-tuples, ``ft_path`` is read in full (``checkpoint.load_adnerf``) and the run file is
     ``checkpoint.save_baseline_checkpoint``'s; the returned ``latent_codes`` is None.  refine_poses / pose_lrate, refine_expr / expr_lrate,
-    learn_background / bg_lrate: as ``train``."""
+    learn_background / bg_lrate, ssim_weight / patches / patch_region: as ``train``."""
     import numpy as np
     from . import checkpoint
     from .agg_aud_exp_nerf import build_head_network
@@ -212,14 +249,28 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
     if learn_background and loader != "resident":
         raise ValueError("learn_background needs the step's pixel indices, which the resident loader alone hands over "
                          "(loader='resident')")
+    ssim_weight = float(ssim_weight)
+    if ssim_weight < 0:
+        raise ValueError(f"ssim_weight must not be negative, got {ssim_weight}")
+    if patches is not None:
+        from .ssim_loss import PATCH_REGIONS, check_patches
+        if loader != "resident":
+            raise ValueError("patches are put into the batch by the resident loader alone (loader='resident')")
+        patches = check_patches(patches)
+        if patch_region not in PATCH_REGIONS:
+            raise ValueError(f"patch_region must be one of {PATCH_REGIONS}, got {patch_region!r}")
+    elif ssim_weight > 0:
+        raise ValueError("ssim_weight > 0 needs patches=(k, p): SSIM is a statistic of 11 x 11 windows, which scattered pixels "
+                         "cannot carry")
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
     rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if dist_on else (0, 1)
     basedir, expname = args.basedir, args.expname
     run_dir = os.path.join(basedir, expname)
 
     if loader == "resident":
+        patch_kw = {} if patches is None else dict(patches=patches, patch_region=patch_region)
         dataset_train = resident_cls(args.datadir, args.aud_file, "train", args, device=device, max_bytes=max_bytes,
-                                     seed=sample_seed)
+                                     seed=sample_seed, **patch_kw)
     else:
         dataset_train = reference_cls(args.datadir, args.aud_file, mode="train", args=args, device=device)
     dataset_val = reference_cls(args.datadir, args.aud_file, mode="val", args=args, skip=args.testskip, device=device)
@@ -289,19 +340,25 @@ def _train_head_model(args, model, resident_cls, reference_cls, checkpoint_name,
             return validation_frame(network, dataset_val, latent_codes, step, sample_seed, flip=flip, background=bg), None
         return resident_validation_frame(network, frames_val, latent_codes, step, sample_seed, flip=flip, background=bg)
 
+    # the SSIM term of a step: its weight and where the loader has put the patches (off: the steps are called as they were)
+    ssim_kw = {} if not ssim_weight > 0 else dict(ssim=(ssim_weight, dataset_train.patch_rows(), *patches))
     if with_codes:
         step_fn = lambda data, step: train_step(network, optimizer, data, latent_codes, step, data_size, lrate=args.lrate,
-                                                lrate_decay=args.lrate_decay)
+                                                lrate_decay=args.lrate_decay, **ssim_kw)
         scalars_of = lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"],
                                        latent_code_loss=info["latent_code_loss"].item())
         log_line = lambda sc: f"LatentLoss: {sc['latent_code_loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}"
         save = checkpoint.save_checkpoint
     else:
         step_fn = lambda data, step: baseline_train_step(network, optimizer, data, step, data_size, lrate=args.lrate,
-                                                         lrate_decay=args.lrate_decay)
+                                                         lrate_decay=args.lrate_decay, **ssim_kw)
         scalars_of = lambda info: dict(loss=info["loss"].item(), psnr=info["psnr"].item(), learning_rate=info["lr"])
         log_line = lambda sc: f"Loss: {sc['loss']}  PSNR: {sc['psnr']} LR: {sc['learning_rate']}"
         save = lambda path, net, opt, codes, step: checkpoint.save_baseline_checkpoint(path, net, opt, step)
+    if ssim_kw:
+        plain_scalars, plain_line = scalars_of, log_line
+        scalars_of = lambda info: dict(plain_scalars(info), ssim_loss=info["ssim_loss"].item())
+        log_line = lambda sc: f"{plain_line(sc)} SSIMLoss: {sc['ssim_loss']}"
     if refiner is not None:
         # the frame's correction on the step's ray batch (the tuples begin with batch_rays and end with the frame index), and
         # the deltas beside everything else in the checkpoint

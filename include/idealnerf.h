@@ -377,6 +377,43 @@ size_t idealnerf_frame_scores_workspace_bytes(int H, int W);
 int idealnerf_frame_scores(const float* pred, const uint8_t* truth, const uint8_t* regions, int H, int W, double* out,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * SSIM as a training loss, on contiguous patches of a ray batch.  Additive entries: the ABI version is unchanged.
+ *
+ * idealnerf_patch_pixels: sel_out receives the n_patches * p * p flat row-major pixel indices (y * W + x) of the p x p patches
+ * whose top-left corners are (oy[k], ox[k]): patch by patch, row-major inside a patch -- the rows a [n_patches, p, p, 3] tensor
+ * has.  The set travels by value as kernel arguments, as cameras do.  n_patches outside 1..IDN_PATCH_MAX, p outside
+ * IDN_PATCH_MIN_P..IDN_PATCH_MAX_P, a negative origin, ox[k] + p > W, W <= 0 or a NULL pointer return IDN_EINVAL before any launch.
+ * (The frame's height is the caller's: idealnerf_gather_rays turns indices past the frame into zero rows.)
+ *
+ * idealnerf_ssim_patch_fwd: pred, truth [n_patches, p, p, 3] fp32 -> out [n_patches + 1] float64: out[k] is patch k's mean SSIM
+ * index over its 3 (p - 10)^2 windows (three channels, "valid" windows), out[n_patches] = 1 - mean(out[0 .. n_patches)), the
+ * loss.  The index is idealnerf_frame_scores': the same eleven fp32 weights widened to fp64, C1 = 1e-4, C2 = 9e-4, weighted
+ * biased variances, all five window moments and the index in fp64.
+ *
+ * idealnerf_ssim_patch_bwd: d_pred [n_patches, p, p, 3] fp32 is OVERWRITTEN with g * d loss / d pred, rounded once to fp32.  With
+ * the window's moments mu_x, mu_t, E[xx], E[tt], E[xt] recomputed as the forward computes them and A = dS / d mu_x,
+ * B = dS / d E[xx], C = dS / d E[xt] per window, every pixel gathers from the at most 121 windows that cover it:
+ *     d_pred = -((g / n_patches) / (3 (p - 10)^2)) (sum w A + 2 x sum w B + t sum w C),   w = the pixel's weight in the window.
+ * truth gets no gradient.
+ *
+ * Both: arithmetic beyond the loads is fp64; no floating-point atomics; every sum runs in a fixed order (a lane's items in index
+ * order, a fixed shuffle tree, waves and patches in index order): the same inputs give the same bytes, and a patch's result
+ * does not depend on the other patches of the call.  Limits and NULL pointers as idealnerf_patch_pixels: IDN_EINVAL.
+ */
+#define IDN_PATCH_MAX 16   /* patches of one set */
+#define IDN_PATCH_MIN_P 11 /* one SSIM window */
+#define IDN_PATCH_MAX_P 48 /* what one workgroup's 64 KiB of LDS hold: two fp32 tiles and three fp64 planes of 38^2 */
+typedef struct idn_patch_set {
+    int n_patches;
+    int p;                 /* edge of every patch */
+    int oy[IDN_PATCH_MAX]; /* top-left corners: row, */
+    int ox[IDN_PATCH_MAX]; /* column */
+} idn_patch_set;
+int idealnerf_patch_pixels(const idn_patch_set* set, int W, int64_t* sel_out, void* stream);
+int idealnerf_ssim_patch_fwd(const float* pred, const float* truth, int n_patches, int p, double* out, void* stream);
+int idealnerf_ssim_patch_bwd(const float* pred, const float* truth, int n_patches, int p, float g, float* d_pred, void* stream);
+
 size_t idealnerf_render_workspace_bytes(int64_t n_rays, int n_samples, int n_importance);
 int idealnerf_render_rays_fwd(const idn_render_args* a, void* stream);
 

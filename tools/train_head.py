@@ -13,6 +13,8 @@
     python tools/train_head.py --refine_poses --timing-json profiles/pose_refine.json --generate 300   # the option's cost per step
     python tools/train_head.py --config <file> --refine_expr [--expr_lrate R] --learn_background [--bg_lrate R]
     python tools/train_head.py --refine_expr --learn_background --timing-json profiles/cond_refine.json --generate 40 --steps 40
+    python tools/train_head.py --config <file> --ssim_weight 0.2 --patches 1x32 [--patch_region rect|frame]   # an SSIM term on patches
+    python tools/train_head.py --ssim_weight 0.2 --patches 1x32 --timing-json profiles/ssim_loss.json --generate 40 --steps 40
 
 ``--model agg`` trains ``agg_aud_exp_nerf.Network`` (NeRFs/HeadNeRF/train/agg_aud_exp_nerf.py) with its own loaders, flags
 (the head stage's plus ``use_highlight``) and ``{epoch:06d}_head.tar`` checkpoints.  Its ``--timing-json`` measures what the
@@ -74,6 +76,11 @@ def parse(argv):
     p.add_argument("--learn_background", action="store_true",
                    help="train the background image with the model (cond_refine.Background; resident loader); head.tar gains background")
     p.add_argument("--bg_lrate", type=float, default=None, help="Adam rate of the background (default lrate, untuned)")
+    p.add_argument("--ssim_weight", type=float, default=0.0,
+                   help="weight of the patch SSIM term, 1 - mean SSIM on the fine image (ssim_loss.ssim_patch_loss; needs --patches; untuned)")
+    p.add_argument("--patches", type=str, default=None, metavar="KxP",
+                   help="K contiguous P x P patches ride in every batch, out of the rect region's share (resident loader)")
+    p.add_argument("--patch_region", type=str, default="rect", choices=("rect", "frame"), help="where the patches' corners are drawn")
     p.add_argument("--pose_noise", type=str, default=None, metavar="DEG,LEN",
                    help="with --generate: seeded noise of this size (degrees, scene units) on the generated TRAINING cameras; "
                         "the clean poses are kept as transforms_exp_train_clean.json")
@@ -444,6 +451,99 @@ def cond_timing(args):
     return {"step_cost": out}
 
 
+def _patches(text):
+    """"KxP" -> (K, P); None stays None."""
+    if text is None:
+        return None
+    try:
+        k, p = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise SystemExit(f"--patches takes KxP, e.g. 1x32 (got {text!r})") from None
+    return k, p
+
+
+def ssim_timing(args):
+    """What --ssim_weight W --patches KxP costs per step: the head model's train_step fed by the resident loader in two arms --
+    off, and the option on -- alternating window by window in one process from equal initial weights, each window warmed and
+    ended by one synchronise; then the three new launches alone (patch_pixels, the loss's forward, its backward) by HIP events
+    over repeated calls on one batch's patch rows."""
+    import torch
+    from idealnerf_amd import dataset, ops, synthetic, train as T_
+    from idealnerf_amd.agg_aud_exp_nerf import build_head_network, init_weights
+    if not torch.cuda.is_available():
+        raise SystemExit("--timing-json measures on a GPU; none is visible")
+    dev = torch.device("cuda", 0)
+    if args.generate and not os.path.isdir(args.datadir):
+        os.makedirs(args.datadir)
+        synthetic.write_clip_directory(args.datadir, SIZE, args.generate, seed=0)
+    steps = args.steps or 60
+    k, p = _patches(args.patches)
+    arms = {}
+    for arm, kw in (("off", {}), ("on", dict(patches=(k, p), patch_region=args.patch_region))):
+        frames = dataset.ResidentFrames(args.datadir, args.aud_file, "train", args, device=dev, seed=args.sample_seed, **kw)
+        torch.manual_seed(0)
+        net = build_head_network(args, frames.H, frames.W, frames.focal, "head").to(dev)
+        lat = torch.ones(len(frames), 32, dtype=torch.float32, device=dev)
+        net.apply(init_weights)
+        lat.requires_grad = True
+        net.train()
+        ssim = dict(ssim=(args.ssim_weight, frames.patch_rows(), k, p)) if kw else {}
+        arms[arm] = (frames, net, T_.make_optimizer(net, lat, args.lrate), lat, ssim)
+    n = len(arms["off"][0])
+    step = {a: 0 for a in arms}
+
+    def window(arm, count):
+        frames, net, opt, lat, ssim = arms[arm]
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(count):
+            s = step[arm]
+            T_.train_step(net, opt, frames.batch(s % n, s), lat, s, n, lrate=args.lrate, lrate_decay=args.lrate_decay, **ssim)
+            step[arm] += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / count * 1e3
+
+    per_round = {a: [] for a in arms}
+    for _ in range(ROUNDS):
+        for arm in arms:                         # the same order in every round: off, on
+            window(arm, WARMUP)
+            per_round[arm].append(window(arm, steps))
+
+    frames = arms["on"][0]
+    batch = frames.batch(0, 0)
+    rows = frames.patch_rows()
+    truth = batch[1][rows].contiguous()
+    pred = (truth + 0.05 * torch.randn_like(truth)).contiguous()
+    origins, tail = frames.patch_origins_of(0, 0), torch.empty(k * p * p, dtype=torch.int64, device=dev)
+    out64, d_pred = torch.empty(k + 1, dtype=torch.float64, device=dev), torch.empty_like(pred)
+
+    def event_us(fn, reps=200):
+        for _ in range(20):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / reps * 1e3
+
+    launches = {"patch_pixels_us": event_us(lambda: ops.patch_pixels(origins, p, frames.W, out=tail)),
+                "ssim_patch_fwd_us": event_us(lambda: ops.ssim_patch_fwd(pred, truth, k, p, out=out64)),   # both of its launches
+                "ssim_patch_bwd_us": event_us(lambda: ops.ssim_patch_bwd(pred, truth, k, p, g=args.ssim_weight, out=d_pred))}
+    med = lambda v: float(statistics.median(v))
+    out = {"device": torch.cuda.get_device_name(0), "size": [frames.H, frames.W], "frames": n, "N_rand": args.N_rand,
+           "mouth_rays": args.mouth_rays, "N_samples": args.N_samples, "N_importance": args.N_importance, "perturb": args.perturb,
+           "steps_per_window": steps, "warmup_steps": WARMUP, "rounds": ROUNDS, "ssim_weight": args.ssim_weight, "patches": [k, p],
+           "patch_region": args.patch_region, "launches_back_to_back": launches}
+    for arm in arms:
+        out["step_ms_" + arm] = per_round[arm]
+        out["step_ms_" + arm + "_median"] = med(per_round[arm])
+    out["on_minus_off_ms"] = med(per_round["on"]) - med(per_round["off"])
+    return {"step_cost": out}
+
+
 def main(argv=None):
     args = parse(argv)
     if args.timing_json is not None:
@@ -458,7 +558,11 @@ def main(argv=None):
         cond = args.refine_expr or args.learn_background   # either flag: the four arms off / refine_expr / learn_background / both
         if cond and (args.model != "head" or args.refine_poses):
             raise SystemExit("--timing-json --refine_expr / --learn_background measures the head model, without --refine_poses")
-        if cond:
+        if args.patches is not None:
+            if cond or args.refine_poses or args.model != "head" or not args.ssim_weight > 0:
+                raise SystemExit("--timing-json --patches measures the head model with --ssim_weight > 0 and no other option")
+            out = ssim_timing(args)
+        elif cond:
             out = cond_timing(args)
         else:
             out = pose_timing(args) if args.refine_poses else {"agg": agg_timing, "baseline": baseline_timing}.get(args.model, timing)(args)
@@ -483,7 +587,8 @@ def main(argv=None):
         raise SystemExit("--pose_noise perturbs a directory --generate writes; this one exists or --generate is missing")
     t0 = time.perf_counter()
     pose = dict(refine_poses=args.refine_poses, pose_lrate=args.pose_lrate, refine_expr=args.refine_expr, expr_lrate=args.expr_lrate,
-                learn_background=args.learn_background, bg_lrate=args.bg_lrate)
+                learn_background=args.learn_background, bg_lrate=args.bg_lrate, ssim_weight=args.ssim_weight,
+                patches=_patches(args.patches), patch_region=args.patch_region)
     if args.model == "agg":
         from idealnerf_amd import train_agg
         run = train_agg.train(args, loader=args.loader, sample_seed=args.sample_seed, steps=args.steps, **pose)
